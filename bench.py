@@ -27,6 +27,12 @@ prune events, so the images/sec figure is the same quantity.
 A "step" is one minibatch through the hot path (zero_grad, forward, loss, backward, gradient routing, SGD step, prune
 event when due, statistics); validates are inside the timed region.  value = global_batch * K / wall, wall = max over
 ranks of the barrier-bracketed timed region.
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, the cycle's own counts and its
+finite-weights check).  Everything else the bench measures or checks -- the per-kernel HIP-event clock (roofline,
+kernel_families, whole_step), the phase report, the oracle parity check, the opt-in conv arithmetics, the other workloads,
+the CPU baseline, the task-2 finetune_again leg and the multi-GPU replica check -- runs only under `--full`.
+`--dump-outputs DIR` writes what the timed path computed in its last step (see dump_outputs), after the timed region.
 """
 import argparse
 import json
@@ -976,11 +982,11 @@ def other_workloads(steps, warmup, timeout_s=240):
     after the headline's timed region (this process idles meanwhile; nothing of it is inside any timed region): configs[3]'s topology
     (ResNet-50), configs[4]'s (SphereNet-20, at the reference's lrs), the GROWN VGG16 (raw multiplier 1.5: where most of configs[1]'s 20
     tasks run) and the task-2 cycle (piggymasks + Adam).  A summary of each child's own JSON line; the full line is what
-    `python bench.py <flags>` prints."""
+    `python bench.py <flags> --full` prints."""
     import subprocess
     res = {}
     for name, flags in OTHER_WORKLOADS:
-        cmd = [sys.executable, os.path.abspath(__file__)] + flags + ['--steps', str(steps), '--warmup', str(warmup), '--no-cpu-baseline',
+        cmd = [sys.executable, os.path.abspath(__file__)] + flags + ['--steps', str(steps), '--warmup', str(warmup), '--full', '--no-cpu-baseline',
                                                                      '--optin-steps', '0', '--no-other-workloads']
         t0 = time.perf_counter()
         try:
@@ -1005,6 +1011,39 @@ def other_workloads(steps, warmup, timeout_s=240):
         except Exception as e:                                # a broken child must not take the headline line with it
             res[name] = {'error': repr(e)[:300], 'flags': flags}
     return res
+
+
+DUMP_SAMPLE = 1 << 16               # --dump-outputs: elements kept of a tensor (larger ones: a fixed, seeded sample)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, logits, net, masks):
+    """--dump-outputs DIR: what the timed path hands its caller after its last step -- the train-mode logits of the last train step and
+    the state the cycle left (every tensor of the model's state_dict, the owner masks) -- as DIR/<name>.npy.  Floating tensors and small
+    integer ones are written as float32, wider integers as float64.  A tensor of more than DUMP_SAMPLE elements is written flattened at
+    DUMP_SAMPLE sorted indices drawn by a CPU generator seeded with the crc32 of its name, the same in every run.  Returns the file names."""
+    import zlib
+    import numpy as np
+    arrays = [('logits' if len(logits) == 1 else 'logits_%d' % i, o) for i, o in enumerate(logits)]
+    arrays += [('state.' + k, v) for k, v in net.state_dict().items()]
+    arrays += [('owner_mask.' + k, v) for k, v in masks.items()]
+    os.makedirs(path, exist_ok=True)
+    out, total = [], 0
+    for name, t in arrays:
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        wide = not (t.is_floating_point() or t.element_size() <= 2)
+        a = t.cpu().to(torch.float64 if wide or t.dtype == torch.float64 else torch.float32).numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise RuntimeError('bench.py --dump-outputs: more than %d bytes' % DUMP_LIMIT_BYTES)
+        fname = name.replace(os.sep, '_') + '.npy'
+        np.save(os.path.join(path, fname), a)
+        out.append(fname)
+    return out
 
 
 def _free_port():
@@ -1051,22 +1090,32 @@ def main():
     ap.add_argument('--math', default='fp32', choices=['fp32', 'bf16', 'bf16x3'],
                     help="arithmetic of the 3x3 conv forward / input gradient: 'fp32' (default, the reference's precision) or the "
                          "OPT-IN 'bf16' MFMA path (never the headline: it does not meet north_star's 1e-4 parity bar)")
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond the headline figure: the kernel clock (roofline, kernel_families, '
+                         'whole_step), the phase report, the oracle parity check, the opt-in conv arithmetics, the other workloads, the CPU '
+                         'baseline, the task-2 finetune_again leg, the multi-GPU replica check.  Without it a run sets up, warms up, times '
+                         'the steps, writes --dump-outputs and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps write what the timed path computed in its last step (the last train step's logits, the "
+                         'model state and owner masks the cycle left; larger tensors as a fixed seeded sample) as DIR/<name>.npy')
     ap.add_argument('--optin-steps', type=int, default=8,
-                    help='after the timed cycle, also time this many train steps in each opt-in conv arithmetic (reported beside the '
+                    help='--full: after the timed cycle, also time this many train steps in each opt-in conv arithmetic (reported beside the '
                          'headline as opt_in_conv_math, never as value); 0 = skip')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-other-workloads', action='store_true',
-                    help='the default headline run (vgg16, task 1, width 1.0, one GPU) also runs 20-step cycles of the other single-GPU '
+                    help='the --full headline run (vgg16, task 1, width 1.0, one GPU) also runs 20-step cycles of the other single-GPU '
                          "workloads (resnet50, spherenet20, the grown VGG16, task 2) in child processes after its own timed region and reports "
                          'them under "other_workloads"; this flag skips that')
     ap.add_argument('--cpu-baseline', default='full', choices=['full', 'quick'],
-                    help="'full' (default, ~6 min of host time): SURVEY 8d's CPU baseline -- 2 timed train steps at batch 256 on the faster thread "
-                         "setting + BASELINE.md section 4's configs[0] plumbing cycle; 'quick': the batch-64 probe only (~1.5 min)")
+                    help="--full: 'full' (default, ~6 min of host time): SURVEY 8d's CPU baseline -- 2 timed train steps at batch 256 on the faster "
+                         "thread setting + BASELINE.md section 4's configs[0] plumbing cycle; 'quick': the batch-64 probe only (~1.5 min)")
     ap.add_argument('--no-kernel-clock', action='store_true')
     ap.add_argument('--clock-every', type=int, default=4,
-                    help='HIP events around the masked-layer launches of every N-th train step of the timed cycle and of every validate '
+                    help='--full: HIP events around the masked-layer launches of every N-th train step of the timed cycle and of every validate '
                          '(1 = every launch; the launches of the other steps are counted, not timed)')
     a = ap.parse_args()
+    if a.steps < 1:
+        sys.exit('bench.py: --steps must be >= 1')
 
     if a.global_batch:
         if a.global_batch % a.gpus:
@@ -1103,6 +1152,8 @@ def main():
     if a.task_sequence > 0:
         if world != 1:
             sys.exit('bench.py: --task-sequence runs on one GPU')
+        if a.dump_outputs:
+            sys.exit('bench.py: --dump-outputs applies to the cycle bench, not to --task-sequence')
         print(json.dumps(run_task_sequence(a, device)), flush=True)
         return
     global DATASET, WIDTH, LRS
@@ -1118,7 +1169,7 @@ def main():
         # under `rocprofv3 --pmc` a queue that carries events on some steps only was aborted with HSA_STATUS_ERROR_INVALID_PACKET_FORMAT
         # (ResNet-50, ROCm 7.2; every launch clocked, or none, runs): counter passes clock every launch
         clock.every = 1
-    if not a.no_kernel_clock and rank == 0:
+    if a.full and not a.no_kernel_clock and rank == 0:
         proxy = clock.wrap(_lib.lib())
         _lib._lib = proxy                                  # route the Python mirror's calls through the timers
 
@@ -1185,22 +1236,35 @@ def main():
             model.sync_events = []
         settle_host_gc()
 
+    last_logits = []
+    if a.dump_outputs:
+        # (train-mode forwards only: the validates run in eval mode; detached, so no step's autograd graph outlives the step)
+        def keep_logits(mod, inp, out):
+            if mod.training:
+                last_logits[:] = [o.detach() for o in (out if isinstance(out, tuple) else (out,))]
+        hook = net.register_forward_hook(keep_logits)
     barrier()
     clock.enabled = True
     t0 = time.perf_counter()
-    marks, counts = [], {}
-    done = run_cycle(model, masks, pool, val_pool, a.steps, clock, marks, counts, task=a.task)
+    marks, counts = [] if a.full else None, {}
+    done = run_cycle(model, masks, pool, val_pool, a.steps, clock if a.full else None, marks, counts, task=a.task)
     barrier()
     dt_local = dt = time.perf_counter() - t0
     clock.enabled = False
     assert done == a.steps
+    if a.dump_outputs:
+        hook.remove()
+        if rank == 0:
+            dump_outputs(a.dump_outputs, last_logits, net, masks)
     per_rank_ms = [1000.0 * dt / a.steps]
+    replicas_identical = None
     if world > 1:
         tt = torch.zeros(world, device=device, dtype=torch.float64)
         tt[rank] = dt_local
         dist.all_reduce(tt, op=dist.ReduceOp.SUM)
         per_rank_ms = [round(1000.0 * float(v) / a.steps, 3) for v in tt.tolist()]
         dt = float(tt.max().item())
+    if world > 1 and a.full:
         # replicated state must still be identical: compare a checksum of the weights and owner masks across ranks
         chk = torch.stack([sum(p.detach().double().sum() for p in net.parameters()),
                            sum(m.double().sum() for m in masks.values())])
@@ -1209,7 +1273,7 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         replicas_identical = bool(torch.equal(lo, hi))
     again_ms = phases = None
-    if a.task == 2:
+    if a.task == 2 and a.full:
         # (every rank: the leg's train steps exchange gradients; after the timed region, the replica checksum and the phase report,
         # which prices a rank-prune event on the cycle's final masks)
         phases = phase_report(marks, model, masks, a.batch) if rank == 0 else None
@@ -1336,7 +1400,8 @@ def main():
             if os.environ.get('CPG_BENCH_DETAIL'):
                 out['kernel_detail'] = {k: {'n': v[0], 'ms': round(v[1], 2), 'tflops': round(v[2] / (v[1] * 1e-3) / 1e12, 2), 'winograd': v[3] < v[2]}
                                         for k, v in sorted(agg.items())}
-        out['phases'] = phases if phases is not None else phase_report(marks, model, masks, a.batch)
+        if a.full:
+            out['phases'] = phases if phases is not None else phase_report(marks, model, masks, a.batch)
         # in-run correctness evidence (outside the timed region): finite loss, the sparsity the cycle's rank-prune events must have reached,
         # and the timed model's logits against the CPU oracle
         spars = SparsePruner(model, masks, make_args('prune', 1), 0, 1, 1).calculate_sparsity() if a.task == 1 else None
@@ -1349,19 +1414,20 @@ def main():
             # value null, the measured number under invalid_value) and the metric string says so too
             out['metric'] += ' (INVALID RUN: non-finite weights after the cycle)'
             out['valid'], out['invalid_value'], out['value'] = False, out['value'], None
-        out['parity_check'] = parity_check(net, pool[0][0], WIDTH) if world == 1 else None
+        if a.full:
+            out['parity_check'] = parity_check(net, pool[0][0], WIDTH) if world == 1 else None
         if a.task == 2:
             out['task2'] = {'task1_ms_per_step': round(task1_ms, 3), 'task2_over_task1': round(1000.0 * dt / a.steps / task1_ms, 4),
                             'free_share_handed_to_task2': round(free_share, 4), 'lr_mask_finetune': 5e-4, 'lr_mask_prune': 0.0,
-                            'finetune_again_ms_per_step': round(again_ms, 3),
+                            'finetune_again_ms_per_step': round(again_ms, 3) if again_ms is not None else None,
                             'note': 'task1_ms_per_step = the task-1 cycle of the same K in the same process, before the switch; the timed '
                                     'region is the task-2 cycle alone; finetune_again = the piggymask retrain leg (lr 1e-3, lr_mask 1e-4, '
                                     'fresh piggymasks), train steps only, timed after the cycle'}
-        if a.math == 'fp32' and world == 1 and a.optin_steps > 0 and a.arch == 'vgg16' and a.task == 1 and a.batch == 256 and a.width_multiplier == 1.0:
+        if a.full and a.math == 'fp32' and world == 1 and a.optin_steps > 0 and a.arch == 'vgg16' and a.task == 1 and a.batch == 256 and a.width_multiplier == 1.0:
             out['opt_in_conv_math'] = optin_modes(model, masks, pool, a.optin_steps, a.batch)
-        if (not a.no_other_workloads and not a.no_cpu_baseline and world == 1 and a.arch == 'vgg16' and a.task == 1 and a.width_multiplier == 1.0
+        if (a.full and not a.no_other_workloads and not a.no_cpu_baseline and world == 1 and a.arch == 'vgg16' and a.task == 1 and a.width_multiplier == 1.0
                 and a.batch == 256 and a.math == 'fp32'):
-            # (the full default line only: tooling runs -- profilers, A/B scripts -- pass --no-cpu-baseline and get the headline cycle alone)
+            # (the --full headline line only: tooling runs -- profilers, A/B scripts -- pass --no-cpu-baseline and get the headline cycle alone)
             # free this process's cached blocks first: the children allocate their own pools on the same GPU
             torch.cuda.empty_cache()
             out['other_workloads'] = other_workloads(20, a.warmup)
@@ -1372,7 +1438,7 @@ def main():
                 out['config']['other_%s_images_per_sec' % name] = w_.get('value')
                 out['config']['other_%s_whole_step_frac_of_dense_peak' % name] = (w_.get('whole_step') or {}).get('frac_of_dense_fp32_mfma_peak')
                 out['config']['other_%s_parity_and_finite' % name] = ok
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             if a.task == 1 and a.width_multiplier == 1.0:
                 out['cpu_baseline'] = cpu_baseline(steps=a.steps, batch=a.batch, validates=counts['validates'],
                                                    prune_events=counts['prune_events'], level=a.cpu_baseline, arch=a.arch)

@@ -548,6 +548,33 @@ def test_bench_cycle_plan_and_scaling_table():
 
 
 
+def test_bench_dump_outputs_writes_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: one float32 / float64 .npy per array (logits, every state_dict tensor, every owner mask); a tensor larger
+    than DUMP_SAMPLE is written as the same seeded sample in every run, and the sample is a sample of THAT tensor."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod3', os.path.join(ROOT, 'bench.py'))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    torch.manual_seed(0)
+    net = nn.Sequential(nn.Linear(300, 400), nn.BatchNorm1d(400))
+    masks = {'module.0': torch.randint(0, 3, (400, 300), dtype=torch.uint8)}
+    logits = [torch.randn(4, 5)]
+    for d in ('a', 'b'):
+        b.dump_outputs(str(tmp_path / d), logits, net, masks)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['logits.npy', 'owner_mask.module.0.npy', 'state.0.bias.npy', 'state.0.weight.npy', 'state.1.bias.npy',
+                     'state.1.num_batches_tracked.npy', 'state.1.running_mean.npy', 'state.1.running_var.npy', 'state.1.weight.npy']
+    for n in names:
+        x = np.load(tmp_path / 'a' / n)
+        np.testing.assert_array_equal(x, np.load(tmp_path / 'b' / n))
+    np.testing.assert_array_equal(np.load(tmp_path / 'a' / 'logits.npy'), logits[0].numpy())
+    assert np.load(tmp_path / 'a' / 'state.1.num_batches_tracked.npy').dtype == np.float64
+    w = np.load(tmp_path / 'a' / 'state.0.weight.npy')
+    assert w.shape == (b.DUMP_SAMPLE,) and w.dtype == np.float32 and np.isin(w, net[0].weight.detach().numpy()).all()
+    m = np.load(tmp_path / 'a' / 'owner_mask.module.0.npy')
+    assert m.shape == (b.DUMP_SAMPLE,) and m.dtype == np.float32 and set(np.unique(m)) <= {0.0, 1.0, 2.0}
+
+
 def test_bench_kernel_clock_weights_the_sampled_train_steps():
     """bench.py --clock-every N: events on some train steps only, on every validate; the summary weights a train-step record by
     train steps / clocked train steps, so family averages estimate the all-launch figures (launch counts included)."""

@@ -240,7 +240,7 @@ def test_bench_self_launches_two_ranks(tmp_path):
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--batch', '4',
-                        '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
+                        '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1]
     out = json.loads(line)
@@ -275,12 +275,46 @@ def test_bench_json_line_is_the_last_stdout_line_with_rccl(tmp_path):
     import subprocess
     env = dict(os.environ, CPG_DP_FORCE='1', RANK='0', LOCAL_RANK='0', WORLD_SIZE='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(_free_port()))
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '4',
-                        '--no-cpu-baseline', '--optin-steps', '0'], env=env, capture_output=True, text=True, timeout=900)
+                        '--full', '--no-cpu-baseline', '--optin-steps', '0'], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert lines[-1].startswith('{'), lines[-5:]
     out = json.loads(lines[-1])
     assert out['n_gpus'] == 1 and out['steps'] == 3 and 'roofline' in out
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps and prints the headline fields only -- none of the kernel clock, the
+    parity check or the baselines; --dump-outputs writes the last step's logits and the cycle's state, the same in two runs of the same
+    arguments."""
+    import json
+    import subprocess
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
+        env.pop(k, None)
+    outs = []
+    for run in ('a', 'b'):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '4',
+                            '--dump-outputs', str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+        outs.append(json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1]))
+    out = outs[0]
+    assert out['steps'] == 3 and out['ms_per_step'] > 0 and out['valid'] is True and out['unit'] == 'images/sec'
+    assert abs(out['value'] - 4 * 1000.0 / out['ms_per_step']) <= 1e-3 * out['value']
+    for k in ('roofline', 'kernel_families', 'whole_step', 'phases', 'parity_check', 'cpu_baseline', 'other_workloads', 'opt_in_conv_math'):
+        assert k not in out, k
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == sorted(os.listdir(tmp_path / 'b')) and 'logits.npy' in names
+    assert 'state.classifiers.0.weight.npy' in names and 'owner_mask.module.features.0.npy' in names
+    logits = np.load(tmp_path / 'a' / 'logits.npy')
+    assert logits.shape == (4, 5) and logits.dtype == np.float32 and np.isfinite(logits).all()
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert x.dtype in (np.float32, np.float64) and x.size <= 1 << 16, n
+        np.testing.assert_array_equal(x, y, err_msg=n)
+        total += x.nbytes
+    assert total <= 64 << 20
 
 
 @pytest.mark.parametrize('arch', ['resnet50', 'vgg16'])
@@ -294,7 +328,7 @@ def test_bench_task2_line(arch):
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--arch', arch, '--task', '2', '--steps', '4', '--warmup', '1', '--batch', '8',
-                        '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
+                        '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{')][-1])
     assert out['config']['task'] == 2 and 'NOT the headline' in out['metric'] and out['n_gpus'] == 1
