@@ -44,8 +44,20 @@ class AdamItem(ctypes.Structure):                 # cpg_adam_item
                 ('owner', ctypes.c_void_p), ('n', ctypes.c_int64)]
 
 
+class ResampleItem(ctypes.Structure):            # cpg_resample_item
+    _fields_ = [('src_off', ctypes.c_int64), ('src_h', ctypes.c_int32), ('src_w', ctypes.c_int32), ('crop_y', ctypes.c_int32),
+                ('crop_x', ctypes.c_int32), ('crop_h', ctypes.c_int32), ('crop_w', ctypes.c_int32), ('dst_off', ctypes.c_int64),
+                ('out_h', ctypes.c_int32), ('out_w', ctypes.c_int32)]
+
+
+class TensorItem(ctypes.Structure):             # cpg_tensor_item
+    _fields_ = [('src_off', ctypes.c_int64)] + [(n, ctypes.c_int32) for n in
+                                                ('src_h', 'src_w', 'y0', 'x0', 'flip', 'cut_y0', 'cut_y1', 'cut_x0', 'cut_x1', 'reserved')]
+
+
 PRUNE_RESULT_BYTES = ctypes.sizeof(PruneResult)
 assert PRUNE_RESULT_BYTES == 32
+assert ctypes.sizeof(ResampleItem) == ctypes.sizeof(TensorItem) == 48
 
 # name -> (restype, argtypes); mirrors include/cpg_hip.h one to one
 _SIGNATURES = {
@@ -151,6 +163,11 @@ _SIGNATURES = {
     'cpg_prelu_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     'cpg_prelu_bwd': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp,
                                      ctypes.c_size_t, _vp]),
+    'cpg_image_resample_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(ResampleItem), ctypes.c_int32]),
+    'cpg_image_resample': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(ResampleItem), ctypes.c_int32, _vp, ctypes.c_int64, _vp,
+                                          ctypes.c_size_t, _vp]),
+    'cpg_image_to_tensor': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(TensorItem), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _vp, ctypes.c_int64, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -477,6 +477,47 @@ int cpg_prelu_bwd_bias(const float *x, const float *gy, const float *slope, floa
 int cpg_prelu_fwd(const float *x, const float *residual, const float *slope, float *y, int32_t N, int32_t C, int32_t HW,
                   int32_t n_slopes, void *stream);
 
+/* ---- image batches: the reference's data transforms on a uint8 image store in device memory (cpg_amd/data.py) ----
+ * Images are RGB, HWC, uint8 (3 bytes per pixel), each at its own byte offset of one flat device buffer `src` of src_bytes bytes.
+ * `items_host` is a HOST array, as in cpg_sgd_route_step_multi: the library checks every item against the buffer sizes it is
+ * given BEFORE it launches anything (a bad item returns CPG_E_INVALID, a short workspace CPG_E_WORKSPACE, cpg_last_error names the
+ * item), then passes the items to the kernels by value, so the table may be freed when the call returns.  Compatible additions:
+ * the ABI version stays 3.
+ *
+ * cpg_image_resample: per item, crop rows [crop_y, crop_y + crop_h) x columns [crop_x, crop_x + crop_w) of the image, then resize
+ * the crop to out_h x out_w with PIL's 8-bit BILINEAR filter, written HWC at dst + dst_off (dst_bytes bytes in all).  Bit-identical
+ * to PIL.Image.crop(box).resize((out_w, out_h), Image.BILINEAR) (Resample.c: fp64 coefficients, 22-bit fixed point, horizontal pass
+ * then vertical pass, a pass skipped when its axis keeps its size; the filter never reads outside the crop).  This is what
+ * torchvision's RandomSizedCrop / Resize(int) / Scale compute on PIL images (utils/fine_grained_dataset.py:36-70,117-155,
+ * utils/face_dataset.py:14-19).  Items that change both sizes need workspace for their horizontal pass:
+ * cpg_image_resample_workspace_bytes(items) bytes for the same table.
+ *
+ * cpg_image_to_tensor: item i writes sample i of dst, fp32 NCHW [n_items][3][out_h][out_w] (dst_bytes bytes at least): output
+ * pixel (y, x) is image pixel (y0 + y, x0 + x') with x' = flip ? out_w - 1 - x : x, byte 0 where that lies outside the image
+ * (RandomCrop(padding)'s zero fill), then ((float)u / 255 - mean[c]) / std[c] with IEEE divisions (ToTensor + Normalize), times
+ * 0.0f inside the Cutout rectangle [cut_y0, cut_y1) x [cut_x0, cut_x1) (empty when cut_y0 >= cut_y1 or cut_x0 >= cut_x1; the
+ * multiply keeps -0.0 as `img *= mask` does, utils/fine_grained_dataset.py:33).  mean_host / std_host: 3 host floats each. */
+typedef struct cpg_resample_item {
+    int64_t src_off;                          /* byte offset of the image in src                 */
+    int32_t src_h, src_w;
+    int32_t crop_y, crop_x, crop_h, crop_w;   /* crop rectangle inside the image                 */
+    int64_t dst_off;                          /* byte offset of the out_h x out_w x 3 result     */
+    int32_t out_h, out_w;
+} cpg_resample_item;                          /* 48 bytes */
+typedef struct cpg_tensor_item {
+    int64_t src_off;
+    int32_t src_h, src_w;
+    int32_t y0, x0;                           /* top-left of the out_h x out_w window; may lie outside the image */
+    int32_t flip;                             /* 0 or 1 */
+    int32_t cut_y0, cut_y1, cut_x0, cut_x1;   /* Cutout rectangle in output coordinates */
+    int32_t reserved;
+} cpg_tensor_item;                            /* 48 bytes */
+size_t cpg_image_resample_workspace_bytes(const cpg_resample_item *items_host, int32_t n_items);
+int cpg_image_resample(const uint8_t *src, int64_t src_bytes, const cpg_resample_item *items_host, int32_t n_items, uint8_t *dst,
+                       int64_t dst_bytes, void *workspace, size_t workspace_bytes, void *stream);
+int cpg_image_to_tensor(const uint8_t *src, int64_t src_bytes, const cpg_tensor_item *items_host, int32_t n_items, int32_t out_h,
+                        int32_t out_w, const float *mean_host, const float *std_host, float *dst, int64_t dst_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
