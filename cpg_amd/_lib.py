@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get('CPG_HIP_LIB') or os.path.join(_HERE, 'lib', 'libcpg_h
 ABI_VERSION = 3         # include/cpg_hip.h: CPG_ABI_VERSION
 CPG_OK = 0
 CPG_E_KRANGE = 2
+CPG_E_INVALID = -1
 MODE_FINETUNE = 0
 MODE_PRUNE = 1
 
@@ -168,6 +169,10 @@ _SIGNATURES = {
                                           ctypes.c_size_t, _vp]),
     'cpg_image_to_tensor': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(TensorItem), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                            ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _vp, ctypes.c_int64, _vp]),
+    'cpg_pair_distance': (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _vp, _vp,
+                                         _vp]),
+    'cpg_pair_sweep': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.c_int32, _vp, _vp,
+                                      _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -285,13 +285,18 @@ class CPGSession(object):
     def _validate(self, mgr, epoch):
         """Manager.validate -- except for the `face_verification` task, whose evaluation in the reference is evalLFW
         (CPG_face_main.py:337-341,370-373,403-404,417; utils/manager.py:156-195): apply_mask + eval-mode embeddings.  The embeddings are
-        kept in `self.last_embeddings`; `self.embedding_scorer` (a callable taking that list, e.g. an LFW pair scorer on the host) turns
-        them into the accuracy the goal / early-stop logic compares -- without one the phase reports 0.0."""
+        kept in `self.last_embeddings`; `self.embedding_scorer` (a callable taking that list) turns them into the accuracy the goal /
+        early-stop logic compares.  Without one, a loader of (a, p, issame) pair batches is scored as evalLFW scores it
+        (Manager.score_pairs: the 10-fold LFW accuracy); a loader of single images reports 0.0."""
         if mgr.args.dataset != 'face_verification':
             return mgr.validate(epoch)
         self.last_embeddings = mgr.eval_embeddings(epoch)
         scorer = getattr(self, 'embedding_scorer', None)
-        return float(scorer(self.last_embeddings)) if scorer is not None else 0.0
+        if scorer is not None:
+            return float(scorer(self.last_embeddings))
+        if self.last_embeddings and all(isinstance(b, tuple) and len(b) == 3 for b in self.last_embeddings):
+            return float(mgr.score_pairs(self.last_embeddings, epoch))
+        return 0.0
 
     def finetune(self, args, train_loader, val_loader, epochs, lr_drops=(50, 80), patience=5, pass_through=False):
         """`--mode finetune` (:386-388, :401-444).  Returns (manager, last train acc, last val acc).  With
@@ -369,7 +374,8 @@ class CPGSession(object):
         crop=False serves the task from a model of the CURRENT (grown) width instead -- what a server that keeps one
         resident network for all tasks does: apply_mask zeroes every slot of later tasks, the inference conv kernels skip
         the channels that died with them (cpg_conv2d_fwd_bn_eval), and the head reads the task's own share of the features.
-        The `face_verification` task returns (0.0 or the scorer's value, embeddings of every batch): its evaluation is evalLFW's."""
+        The `face_verification` task returns (its evalLFW accuracy -- 0.0 for a loader of single images -- or the scorer's value,
+        embeddings of every batch): its evaluation is evalLFW's."""
         info = self.shared_layer_info[dataset]
         width = info.get('network_width_multiplier', self.width) if crop else self.width
         saved_info = self.shared_layer_info

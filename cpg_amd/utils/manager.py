@@ -10,8 +10,8 @@ What is not reproduced is the reference's per-step host stall: loss / accuracy a
 device and the progress line (tqdm postfix with the mask statistics) is refreshed on a wall-clock
 interval instead of forcing `.item()` + 15 reductions + `.cpu()` every step; the statistics themselves
 ARE evaluated every step / validation batch (one cached histogram pass).  Returned values are identical.  Checkpoint save / load (utils/manager.py:198-320) delegate to
-utils/checkpoint.py and keep the reference's file format; LFW evaluation (:156-195) needs real face pairs and
-sklearn and is out of scope.
+utils/checkpoint.py and keep the reference's file format.  LFW evaluation (evalLFW, :156-195) scores the pair embeddings on the
+device (cpg_amd/utils/metrics.py).
 """
 import logging
 import time
@@ -70,6 +70,7 @@ class Manager(object):
             settle_host_gc()
         self.progress = bool(getattr(args, 'progress', True)) and tqdm is not None
         self.last_stats = {}
+        self.last_lfw = None
         self.postfix_interval = float(getattr(args, 'postfix_interval', 0.5))
         if args.dataset == 'face_verification':
             from ..models.spherenet import AngleLoss
@@ -197,9 +198,9 @@ class Manager(object):
     def eval_embeddings(self, epoch_idx=0):
         """The device half of the reference's evalLFW (utils/manager.py:156-175), which is what CPG_face_main.py runs instead of
         `validate` for the `face_verification` task (:337-341,:370-373,:417): apply_mask() first, eval mode, then
-        `forward_to_embeddings` of every validation batch.  Returns the list of embedding tensors (on the device); scoring them as
-        LFW pairs (utils/metrics.py: 10-fold ROC on the host with sklearn) needs the real pairs and is out of scope.  A loader
-        that yields (a, p, label) pairs, as the reference's LFWDataset does, gives a list of (emb_a, emb_p, label)."""
+        `forward_to_embeddings` of every validation batch.  Returns the list of embedding tensors (on the device).  A loader
+        that yields (a, p, label) pairs, as the reference's LFWDataset does, gives a list of (emb_a, emb_p, label), which evalLFW
+        scores."""
         self.pruner.apply_mask()
         if hasattr(self.model, 'sync_buffers'):
             self.model.sync_buffers()
@@ -218,6 +219,36 @@ class Manager(object):
                 self.last_stats = {'sparsity': self.pruner.calculate_sparsity(),
                                    'task{} ratio'.format(self.inference_dataset_idx): self.pruner.calculate_curr_task_ratio()}
         return out
+
+    def evalLFW(self, epoch_idx):
+        """utils/manager.py:156-195: apply_mask(), eval mode, `forward_to_embeddings` of both images of every (a, p, issame) batch
+        (eval_embeddings), then fv_evaluate(distance_metric=True, subtract_mean=False) over the reference's thresholds
+        np.arange(0, 4, 0.01) -- distances and the 10-fold threshold search on the device, the embeddings never leave it.  Logs
+        `Accuracy mean+-std` as the reference does and returns np.mean(accuracy).  args.lfw_threshold_dtype = 'float32' compares
+        as numpy 1.x did (cpg_amd/utils/metrics.py); the default is numpy >= 2's fp64 comparison.  Under data parallelism with a
+        replicated pair loader every rank scores every pair and returns the same value."""
+        return self.score_pairs(self.eval_embeddings(epoch_idx), epoch_idx)
+
+    def score_pairs(self, embeddings, epoch_idx=0):
+        """The scoring half of evalLFW on eval_embeddings' list of (emb_a, emb_p, issame) batches."""
+        from .metrics import fv_evaluate
+        if not embeddings or not all(isinstance(b, tuple) and len(b) == 3 for b in embeddings):
+            raise ValueError('evalLFW needs a validation loader of (a, p, issame) batches')
+        emb_a = torch.cat([b[0] for b in embeddings])
+        emb_p = torch.cat([b[1] for b in embeddings])
+        labels = torch.cat([torch.as_tensor(b[2]).reshape(-1).to(emb_a.device) for b in embeddings])
+        tpr, fpr, accuracy, val, val_std, far = fv_evaluate(emb_a, emb_p, labels, distance_metric=True, subtract_mean=False,
+                                                            threshold_dtype=getattr(self.args, 'lfw_threshold_dtype', 'float64'))
+        mean, std = np.mean(accuracy), np.std(accuracy)
+        self.last_lfw = {'tpr': tpr, 'fpr': fpr, 'accuracy': accuracy}
+        self.last_stats = dict(self.last_stats, accuracy=float(mean), accuracy_std=float(std))
+        if self.progress:
+            print('In evalLFW(): Test set: Accuracy: {:.5f}+-{:.5f}'.format(mean, std))
+        if getattr(self.args, 'log_path', None):
+            logging.info(('In evalLFW()-> Validate Epoch #{} '.format(epoch_idx + 1)
+                          + 'Test set: Accuracy: {:.5f}+-{:.5f}, '.format(mean, std)
+                          + 'task_ratio: {:.2f}'.format(self.pruner.calculate_curr_task_ratio())))
+        return mean
 
     # ------------------------------------------------------------------ checkpoints (utils/manager.py:198-320)
     def _path(self, folder, epoch):

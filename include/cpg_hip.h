@@ -518,6 +518,32 @@ int cpg_image_resample(const uint8_t *src, int64_t src_bytes, const cpg_resample
 int cpg_image_to_tensor(const uint8_t *src, int64_t src_bytes, const cpg_tensor_item *items_host, int32_t n_items, int32_t out_h,
                         int32_t out_w, const float *mean_host, const float *std_host, float *dst, int64_t dst_bytes, void *stream);
 
+/* ---- pair verification: the reference's LFW scoring (utils/metrics.py: distance, then calculate_roc's 10-fold threshold search;
+ * utils/manager.py:156-195 evalLFW) on embeddings in device memory (cpg_amd/utils/metrics.py).  Compatible additions: the ABI
+ * version stays 3.
+ *
+ * cpg_pair_distance: dist[i] for the pairs (row i of a, row i of b), i < n; a and b are fp32 row-major [n][d] with leading
+ * dimensions lda, ldb >= d; 1 <= d <= 4096.  metric 0: sum((a - b)^2); metric 1: dot / (|a| * |b|), clipped to [0, 1] (NaN stays
+ * NaN: a zero row gives NaN), float32(acos) * 4 / float32(pi).  Every row sum is numpy's float32 pairwise summation in numpy's order
+ * (np.sum / np.linalg.norm along axis 1 of a C-contiguous float32 matrix), every product and sum rounded to fp32 (no FMA), sqrt and
+ * divisions IEEE: metric 0 and the cosine are bit-identical to the reference; metric 1's arccos is fp64's, rounded once to fp32
+ * (numpy's float32 arccos is within an ulp or two of it).  sim (may be NULL): metric 1 writes dot / (|a| * |b|) before the clip.
+ * n == 0 launches nothing.
+ *
+ * cpg_pair_sweep: the test-set counts of calculate_accuracy (utils/metrics.py:63-74) for every fold of KFold(nfolds, shuffle=False)
+ * over the n pairs (contiguous folds, the first n % nfolds one pair longer) and every threshold of thr_host, a HOST table of n_thr
+ * strictly ascending fp64 values (1 <= n_thr <= 480; it travels to the kernel by value).  A pair is predicted "same" at threshold t
+ * when (double)dist < thr[t] -- numpy >= 2's comparison of a float32 distance with a float64 threshold; numpy 1.x compared in fp32,
+ * which is this call with the table rounded to float32 first.  A NaN distance is never "same".  issame: n bytes, nonzero = same.
+ * counts: int64 [nfolds][n_thr][4] = {tp, fp, tn, fn} of the fold's test pairs (the train counts are the totals minus these).
+ * best: int64 [nfolds], the first threshold index that maximises the TRAIN set's tp + tn (np.argmax(acc_train)).  Integer work:
+ * bit-exact given the distances.  Refused before any launch (CPG_E_INVALID): a table that is not strictly ascending or holds NaN,
+ * nfolds < 2, n < nfolds, n_thr outside [1, 480], n > 2^31 - 1. */
+int cpg_pair_distance(const float *a, int64_t lda, const float *b, int64_t ldb, int64_t n, int32_t d, int32_t metric, float *dist, float *sim,
+                      void *stream);
+int cpg_pair_sweep(const float *dist, const uint8_t *issame, int64_t n, const double *thr_host, int32_t n_thr, int32_t nfolds, int64_t *counts,
+                   int64_t *best, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
