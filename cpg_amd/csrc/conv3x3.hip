@@ -1274,7 +1274,7 @@ int cpg_conv3x3_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float 
     int rc = run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, x, w, pm, thr, bias, y, ws, ws_bytes, stream, nullptr, nullptr, false,
                      &bn);
     if (rc == CPG_OK && skip_stats != nullptr) {
-        // {1 + last live input channel, output tiles skipped}: device-to-device copy of the two words behind live[Mp]
+        // {4 * (input chunks up to the last live one), output blocks skipped}: device-to-device copy of the two words behind live[Mp]
         if (skip) {
             const int *live = reinterpret_cast<const int *>((const float *)ws + pack_floats(d->C, d->K));
             hipError_t e = hipMemcpyAsync(skip_stats, live + pad_to(d->K, 128), 2 * sizeof(int), hipMemcpyDeviceToDevice, stream);

@@ -613,7 +613,7 @@ class FusedSequential(nn.Sequential):
     fuse_stats = True       # conv -> BatchNorm2d: the conv kernel's epilogue produces the batch-statistics partial sums
     fuse_eval = True        # inference: conv -> BatchNorm2d(eval) -> ReLU as one kernel (BatchNorm folded into the conv epilogue)
     skip_log = None         # diagnostics: set to a list to collect one int32[2] tensor per fused inference conv --
-    #                         {1 + last live input channel, output tiles skipped by the dead-channel test}
+    #                         {4 * (4-channel input chunks up to the last live one), output blocks skipped by the dead-channel test}
 
     def forward(self, input):
         mods = list(self._modules.values())

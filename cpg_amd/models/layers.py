@@ -484,7 +484,7 @@ class SharableConv2d(_Sharable):
         """relu(bn(conv(input))) with `bn` an eval-mode nn.BatchNorm2d, as ONE kernel (cpg_conv2d_fwd_bn_eval): the path of
         Manager.validate.  Inference only -- call it under torch.no_grad(); returns None when this shape has no fused
         kernel (the caller then runs the layers one by one).  skip_stats: optional int32[2] device tensor that receives
-        {1 + last live input channel, output tiles skipped} (dead-channel skip, see include/cpg_hip.h)."""
+        {4 * (4-channel input chunks up to the last live one), output blocks skipped} (dead-channel skip, see include/cpg_hip.h)."""
         if (torch.is_grad_enabled() or input.dim() != 4 or input.shape[0] == 0 or input.shape[1] != self.weight.shape[1] * self.groups
                 or self._math() != 'fp32' or self.groups != 1):
             return None

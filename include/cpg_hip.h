@@ -337,7 +337,13 @@ int cpg_bn_stats_finalize_count(const float *stats, int32_t tiles, int32_t N, in
  * ballots), a block whose output channels are all dead skips its MFMA loop (conv output exactly 0 -> it writes BatchNorm(bias))
  * and every block stops after the last live input channel: serving an old task from the resident wide model costs what
  * the reference's cropped model (CPG_cifar100_main_normal.py:233-249) costs.  skip_stats (device, may be NULL) receives
- * {1 + last live input channel, number of output tiles skipped}. */
+ * {4 * (number of 4-channel input chunks up to the last one with a live weight) -- 4 * (c_last / 4 + 1) for c_last the last
+ * live input channel, 0 when no weight is live (C = 78 with channel 77 live: 80) --, number of output blocks that skipped their
+ * MFMA loop (32 output channels per block in the Winograd one-wave kernels, 64 in the two-wave kernel, 64 or 128 in the direct
+ * tiles; a block also spans a pixel tile, so the count is a diagnostic, not a channel count)}; {0, 0} with CPG_NO_DEAD_SKIP.
+ * One deliberate difference from the reference: a NaN or Inf in an input channel past the last live chunk, or in any input of an
+ * output block with no live weight, does not reach the output (that work is skipped; the reference computes 0 * Inf = NaN).
+ * CPG_NO_DEAD_SKIP=1 restores the propagation; skipped work otherwise only ever drops exact zeros. */
 int32_t cpg_conv2d_fwd_bn_eval_supported(const cpg_conv_desc *desc);
 int cpg_conv2d_fwd_bn_eval(const cpg_conv_desc *desc, const float *x, const float *w, const float *piggymask, float threshold,
                            const float *bias, const float *gamma, const float *beta, const float *running_mean,
