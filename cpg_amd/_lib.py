@@ -79,6 +79,9 @@ _SIGNATURES = {
     'cpg_conv2d_pack': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, ctypes.c_float, ctypes.c_int32, _vp, ctypes.c_size_t, ctypes.c_int32, _vp,
                                        ctypes.c_size_t, _vp]),
     'cpg_conv2d_use_packed': (ctypes.c_int, [_vp, ctypes.c_size_t]),
+    'cpg_bn_relu_bwd_reduce': (ctypes.c_int, [_vp] * 9 + [ctypes.c_int32] * 3 + [_vp, ctypes.c_size_t, _vp]),
+    'cpg_conv2d_wgrad_rider_supported': (ctypes.c_int32, [ctypes.POINTER(ConvDesc)]),
+    'cpg_conv2d_wgrad_attach_bn_bwd': (ctypes.c_int, [_vp] * 4 + [ctypes.c_int32] * 3),
     'cpg_linear_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     'cpg_linear_fwd': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_size_t, _vp]),
     'cpg_linear_dgrad': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_size_t, _vp]),

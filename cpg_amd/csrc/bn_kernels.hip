@@ -26,10 +26,6 @@ struct BnDims {
     int imgs_per_slice;
 };
 
-__device__ __forceinline__ float bn_affine(float x, float mean, float invstd, float gamma, float beta) {
-    return (x - mean) * invstd * gamma + beta;
-}
-
 __device__ __forceinline__ double block_sum(double v, double *red) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
@@ -262,8 +258,12 @@ __global__ __launch_bounds__(kThreads) void k_bn_bwd_reduce(const float *__restr
 }
 
 // one thread per channel: dgamma = sum g*xhat, dbeta = sum g; coefficients for the apply pass
+// table (may be NULL): the [C][8] per-channel record of the apply pass when it rides in the weight-gradient kernel (cpg_common.h: WgradRider)
 __global__ void k_bn_bwd_finalize(const double *__restrict__ partial, BnDims d, float *__restrict__ dgamma,
-                                  float *__restrict__ dbeta, float *__restrict__ coef /* [C][2]: mean(g), mean(g*xhat) */) {
+                                  float *__restrict__ dbeta, float *__restrict__ coef /* [C][2]: mean(g), mean(g*xhat) */,
+                                  float *__restrict__ table = nullptr, const float *__restrict__ mean = nullptr,
+                                  const float *__restrict__ invstd = nullptr, const float *__restrict__ gamma = nullptr,
+                                  const float *__restrict__ beta = nullptr) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= d.C) return;
     double sg = 0.0, sgx = 0.0;
@@ -276,6 +276,11 @@ __global__ void k_bn_bwd_finalize(const double *__restrict__ partial, BnDims d, 
     dgamma[c] = (float)sgx;
     coef[2 * c + 0] = (float)(sg / n);
     coef[2 * c + 1] = (float)(sgx / n);
+    if (table != nullptr) {
+        float *t = table + 8 * c;
+        t[0] = mean[c], t[1] = invstd[c], t[2] = gamma[c], t[3] = beta[c];
+        t[4] = (float)(sg / n), t[5] = (float)(sgx / n), t[6] = invstd[c] * gamma[c], t[7] = 0.f;
+    }
 }
 
 // TRAIN: dx = (g - mean(g) - xhat * mean(g xhat)) * invstd * gamma ; EVAL (fixed statistics): dx = g * invstd * gamma
@@ -295,10 +300,7 @@ __global__ __launch_bounds__(kThreads) void k_bn_bwd_apply(const float *__restri
         const float mg = TRAIN ? coef[2 * c] : 0.f, mgx = TRAIN ? coef[2 * c + 1] : 0.f;
         const float scale = is * ga;
         const int64_t off = pl * d.HW;
-        auto one = [&](float xv, float gv) {
-            if (RELU && !(bn_affine(xv, m, is, ga, be) > 0.f)) gv = 0.f;
-            return TRAIN ? (gv - mg - ((xv - m) * is) * mgx) * scale : gv * scale;
-        };
+        auto one = [&](float xv, float gv) { return bn_bwd_apply_one<RELU, TRAIN>(xv, gv, m, is, ga, be, mg, mgx, scale); };
         if (vec) {
             for (int i = gl; i < d.HW / 4; i += GROUP) {
                 const float4 xv = reinterpret_cast<const float4 *>(x + off)[i];
@@ -581,6 +583,26 @@ extern "C" int cpg_bn_relu_bwd(const float *x, const float *gy, const float *gam
     else if (train) launch_bwd_apply<false, true>(d, x, gy, gx, mean, invstd, gamma, beta, coef, stream);
     else launch_bwd_apply<false, false>(d, x, gy, gx, mean, invstd, gamma, beta, coef, stream);
     CPG_CHECK_LAUNCH("cpg_bn_relu_bwd");
+    return CPG_OK;
+}
+
+// The first two launches of cpg_bn_relu_bwd(relu = 1, train = 1) alone -- reduce and finalize: dgamma, dbeta -- and the [C][8] table
+// with which the weight-gradient kernel of the consuming conv runs the apply pass as a side job (cpg_conv2d_wgrad_attach_bn_bwd).
+extern "C" int cpg_bn_relu_bwd_reduce(const float *x, const float *gy, const float *gamma, const float *beta, const float *mean,
+                                      const float *invstd, float *dgamma, float *dbeta, float *table, int32_t N, int32_t C, int32_t HW,
+                                      void *ws, size_t ws_bytes, void *stream_v) {
+    BnDims d;
+    int rc = make_dims(N, C, HW, d);
+    if (rc) return rc;
+    CPG_REQUIRE(x && gy && gamma && beta && mean && invstd && dgamma && dbeta && table && ws, "cpg_bn_relu_bwd_reduce: null pointer");
+    if (ws_bytes < cpg_bn_workspace_bytes(N, C, HW)) return fail(CPG_E_WORKSPACE, "cpg_bn_relu_bwd_reduce: workspace too small");
+    hipStream_t stream = (hipStream_t)stream_v;
+    double *partial = (double *)ws;
+    float *coef = (float *)(partial + (size_t)C * d.slices * 2);
+    hipLaunchKernelGGL(k_bn_bwd_reduce<true>, dim3(C, d.slices), dim3(kThreads), 0, stream, x, gy, d, mean, invstd, gamma, beta, partial);
+    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((C + 63) / 64), dim3(64), 0, stream, partial, d, dgamma, dbeta, coef, table, mean, invstd,
+                       gamma, beta);
+    CPG_CHECK_LAUNCH("cpg_bn_relu_bwd_reduce");
     return CPG_OK;
 }
 

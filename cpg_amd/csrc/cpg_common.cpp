@@ -20,6 +20,8 @@ int fail(int code, const char *fmt, ...) {
 
 static thread_local PackCtx g_pack = {};
 PackCtx &pack_ctx() { return g_pack; }
+static thread_local WgradRider g_rider = {};
+WgradRider &wgrad_rider() { return g_rider; }
 
 int pack_site(const PackJob &job, const float **pre, const char *what) {
     PackCtx &c = g_pack;
@@ -59,6 +61,7 @@ const OptDef kDefs[OPT_COUNT] = {
     {"CPG_STEM_BLOCKS", INT},       {"CPG_WINO_KERNEL", WINO_KERNEL}, {"CPG_WINO_NW", INT},        {"CPG_WINO_PERSIST", INT},
     {"CPG_WINO_GRIDS", INT},        {"CPG_WW_UNITS", INT},         {"CPG_WW_XCD", INT},            {"CPG_PW_TILE", INT},           {"CPG_WG3_SHARE", INT},
     {"CPG_WW_SHARE", INT},          {"CPG_WINO_TAIL", INT},         {"CPG_FC_SMALL", INT},
+    {"CPG_NO_WW_RIDER", BOOL},
 };
 
 struct Table {

@@ -50,6 +50,7 @@ enum Opt {
     OPT_WW_SHARE,         // CPG_WW_SHARE=0: every wave of k_wgw stages its own x rows (round 3); 2 / 4: force that sharing group
     OPT_WINO_TAIL,        // CPG_WINO_TAIL=0: no channel-split tail launch for the leftover units of k_wg3's last round (round 4 behaviour)
     OPT_FC_SMALL,         // CPG_FC_SMALL=0: linear layers at <= 64 rows on the batch-256 tiles / the generic split-K kernel (round 4 behaviour)
+    OPT_NO_WW_RIDER,      // CPG_NO_WW_RIDER=1: cpg_conv2d_wgrad_rider_supported answers 0 (the BatchNorm backward apply stays a pass of its own)
     OPT_COUNT
 };
 constexpr int OPT_UNSET = INT32_MIN;
@@ -87,6 +88,17 @@ int pack_site(const PackJob &job, const float **pre, const char *what);
 int pack_jobs_launch(const PackJob *ja, float *dst_a, const PackJob *jb, float *dst_b, const float *w, const float *pm, float thr,
                      hipStream_t stream);
 
+// ---- BatchNorm backward apply riding in the Winograd weight-gradient kernel (include/cpg_hip.h: cpg_conv2d_wgrad_attach_bn_bwd) ------
+// Same plumbing as the packed operands: a per-THREAD one-shot context that cpg_conv2d_wgrad_attach_bn_bwd arms and the next
+// cpg_conv2d_wgrad on that thread consumes.  table: [C][8] = {mean, invstd, gamma, beta, mean(g), mean(g xhat), invstd * gamma, 0}.
+struct WgradRider {
+    bool armed;
+    const float *y, *gz, *table;
+    float *gy;
+    int N, C, HW;
+};
+WgradRider &wgrad_rider();    // thread-local
+
 inline int hip_status(hipError_t e, const char *what) {
     if (e == hipSuccess) return CPG_OK;
     return fail(CPG_E_HIP_BASE + (int)e, "%s: %s", what, hipGetErrorString(e));
@@ -106,6 +118,19 @@ inline int hip_status(hipError_t e, const char *what) {
 // models/layers.py:14-19 -- fp32 compare, NaN falls through unchanged
 __device__ __forceinline__ float binarize(float pm, float thr) {
     return pm > thr ? 1.0f : (pm <= thr ? 0.0f : pm);
+}
+
+// y = bn(x) before the ReLU, and one element of the BatchNorm(-> ReLU) backward apply pass:
+// TRAIN: dx = (g - mean(g) - xhat * mean(g xhat)) * invstd * gamma ; EVAL (fixed statistics): dx = g * invstd * gamma, with
+// g = gy * [bn(x) > 0] under RELU.  scale = invstd * gamma.  ONE definition for k_bn_bwd_apply (bn_kernels.hip) and the rider of k_wgw
+// (conv3x3_wino_wgrad.hip): the two must round alike bit for bit.
+__device__ __forceinline__ float bn_affine(float x, float mean, float invstd, float gamma, float beta) {
+    return (x - mean) * invstd * gamma + beta;
+}
+template <bool RELU, bool TRAIN>
+__device__ __forceinline__ float bn_bwd_apply_one(float xv, float gv, float m, float is, float ga, float be, float mg, float mgx, float scale) {
+    if (RELU && !(bn_affine(xv, m, is, ga, be) > 0.f)) gv = 0.f;
+    return TRAIN ? (gv - mg - ((xv - m) * is) * mgx) * scale : gv * scale;
 }
 
 constexpr int kCUs = 256;        // MI355X

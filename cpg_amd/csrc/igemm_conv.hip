@@ -842,11 +842,39 @@ extern "C" int cpg_conv2d_use_packed(const void *packed, size_t bytes) {
     return CPG_OK;
 }
 
+// ---- the BatchNorm backward apply of the layer below as a side job of the weight gradient (include/cpg_hip.h) --------------------------
+extern "C" int cpg_conv3x3_wino_wgrad_rider_ok(const cpg_conv_desc *d);
+extern "C" int32_t cpg_conv2d_wgrad_rider_supported(const cpg_conv_desc *d) {
+    ConvGeom g;
+    if (d == nullptr || make_geom(d, g) != CPG_OK || !use_c3_wgrad(d) || !cpg_conv3x3_wino_wgrad_ok(d)) return 0;
+    return cpg_conv3x3_wino_wgrad_rider_ok(d) ? 1 : 0;
+}
+extern "C" int cpg_conv2d_wgrad_attach_bn_bwd(const float *y, const float *gz, float *gy, const float *table, int32_t N, int32_t C, int32_t HW) {
+    cpg::WgradRider &r = cpg::wgrad_rider();
+    r = cpg::WgradRider{};
+    if (y == nullptr) return CPG_OK;             // (disarms)
+    CPG_REQUIRE(gz && gy && table, "cpg_conv2d_wgrad_attach_bn_bwd: null pointer");
+    CPG_REQUIRE(N > 0 && C > 0 && HW > 0 && HW % 4 == 0 && (int64_t)N * C * HW * 4 < (1ll << 31),
+                "cpg_conv2d_wgrad_attach_bn_bwd: needs 4 | HW and a tensor below 2 GiB");
+    CPG_REQUIRE(((((uintptr_t)y) | ((uintptr_t)gz) | ((uintptr_t)gy) | ((uintptr_t)table)) & 15) == 0,
+                "cpg_conv2d_wgrad_attach_bn_bwd: pointers must be 16-byte aligned");
+    r.armed = true, r.y = y, r.gz = gz, r.gy = gy, r.table = table, r.N = N, r.C = C, r.HW = HW;
+    return CPG_OK;
+}
+namespace {
+struct RiderScope {          // one-shot, like PackScope
+    ~RiderScope() { cpg::wgrad_rider() = cpg::WgradRider{}; }
+};
+}  // namespace
+
 extern "C" int cpg_conv2d_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm,
                                 float thr, float *gw, float *gpm, float *gb, void *ws, size_t ws_bytes, void *stream_v) {
+    RiderScope rider_scope;
     ConvGeom g;
     int rc = make_geom(d, g);
     if (rc) return rc;
+    if (cpg::wgrad_rider().armed && !cpg_conv2d_wgrad_rider_supported(d))
+        return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_wgrad: a BatchNorm backward is attached but this launch cannot carry it (cpg_conv2d_wgrad_rider_supported)");
     CPG_REQUIRE(x && gy && gw, "cpg_conv2d_wgrad: null pointer");
     CPG_REQUIRE((pm == nullptr) == (gpm == nullptr), "cpg_conv2d_wgrad: pm and gpm must both be given or both be NULL");
     CPG_REQUIRE(pm == nullptr || w != nullptr, "cpg_conv2d_wgrad: w is required to form the piggymask gradient");

@@ -20,12 +20,15 @@ from .. import _lib
 class BnBwdHint(object):
     """Link between a training-mode BatchNorm2d -> ReLU and the masked 3x3 conv that is the ONLY consumer of its output:
     the conv's input-gradient kernel does the BatchNorm's backward reduction in its epilogue (cpg_conv2d_dgrad_bnbwd) and
-    leaves the partial sums here for _BnReluFn.backward (cpg_bn_bwd_from_partials).  One hint per forward pass."""
-    __slots__ = ('ypre', 'gamma', 'beta', 'mean', 'invstd', 'partials', 'tiles', 'out_shape')
+    leaves the partial sums here for _BnReluFn.backward (cpg_bn_bwd_from_partials) -- `epilogue` --, or the conv's weight-gradient
+    kernel runs the BatchNorm's backward apply pass as a side job (cpg_conv2d_wgrad_attach_bn_bwd) and leaves (gx, dgamma, dbeta)
+    in `result`, computed from the gradient tensor `gz` -- `rider`.  One hint per forward pass."""
+    __slots__ = ('ypre', 'gamma', 'beta', 'mean', 'invstd', 'partials', 'tiles', 'out_shape', 'epilogue', 'rider', 'gz', 'result')
 
-    def __init__(self):
-        self.ypre = self.gamma = self.beta = self.mean = self.invstd = self.partials = self.out_shape = None
+    def __init__(self, epilogue=True, rider=False):
+        self.ypre = self.gamma = self.beta = self.mean = self.invstd = self.partials = self.out_shape = self.gz = self.result = None
         self.tiles = 0
+        self.epilogue, self.rider = epilogue, rider
 
     def usable(self, x):
         return self.ypre is not None and tuple(x.shape) == self.out_shape and x.is_cuda
@@ -35,6 +38,9 @@ class BnBwdHint(object):
 # reduction kernels (-2.4 ms per VGG16 step) but the input-gradient kernels pay the HBM time of the extra reads in an epilogue
 # that nothing hides (+0.28 ms per layer); interleaved in-process A/B (tools/step_ab.py): 184.6 ms with it, 183.8 ms without.
 ENABLE_BWD_HINT = False
+# The BatchNorm backward APPLY pass riding in the next conv's Winograd weight-gradient kernel (MFMA-bound, HBM mostly idle: the loads are
+# requested four k-steps ahead and every element is done once).  The library switch CPG_NO_WW_RIDER turns it off per process.
+ENABLE_WGRAD_RIDER = True
 
 
 class _BnReluFn(torch.autograd.Function):
@@ -81,13 +87,17 @@ class _BnReluFn(torch.autograd.Function):
         N, C, HW, relu, training = ctx.cfg
         gy = gy.contiguous()
         L = _lib.lib()
+        hint, ctx.hint = ctx.hint, None                  # (the hint only lives for one backward pass: drop its tensors afterwards)
+        if hint is not None:
+            hint.ypre = hint.gamma = hint.beta = hint.mean = hint.invstd = hint.out_shape = None
+            gz, result, hint.gz, hint.result = hint.gz, hint.result, None, None
+            if result is not None and gz is not None and gz.data_ptr() == gy.data_ptr() and gz.shape == gy.shape and relu and training:
+                # the consumer conv's weight-gradient kernel already ran this whole backward on exactly this gradient tensor
+                return (result[0], result[1], result[2]) + (None,) * 8
         gx = torch.empty_like(x)
         dgamma = torch.empty_like(gamma)
         dbeta = torch.empty_like(beta)
         ws, nb = _lib.workspace(L.cpg_bn_workspace_bytes(N, C, HW), x.device)
-        hint, ctx.hint = ctx.hint, None                  # (the hint only lives for one backward pass: drop its tensors afterwards)
-        if hint is not None:
-            hint.ypre = hint.gamma = hint.beta = hint.mean = hint.invstd = hint.out_shape = None
         if hint is not None and hint.partials is not None:
             # the consumer conv's input-gradient kernel already masked gy by the ReLU and reduced it per (channel, tile)
             rc = L.cpg_bn_bwd_from_partials(_lib.dptr(hint.partials), hint.tiles, _lib.dptr(x), _lib.dptr(gy, name='grad_output'),
@@ -633,8 +643,9 @@ class FusedSequential(nn.Sequential):
                     # BatchNorm -> ReLU feeding a masked conv directly: let that conv's input-gradient kernel do this
                     # BatchNorm's backward reduction (only this Sequential knows that nothing else reads the activation)
                     nxt2 = mods[i + 2] if i + 2 < n else None
-                    hint = BnBwdHint() if (ENABLE_BWD_HINT and m.training and torch.is_grad_enabled()
-                                           and hasattr(nxt2, 'forward_with_bn_stats')) else None
+                    hint = BnBwdHint(ENABLE_BWD_HINT, ENABLE_WGRAD_RIDER) if (
+                        (ENABLE_BWD_HINT or ENABLE_WGRAD_RIDER) and m.training and torch.is_grad_enabled()
+                        and hasattr(nxt2, 'forward_with_bn_stats')) else None
                     input = bn_relu(input, m, relu=True, stats=stats, hint=hint)
                     i += 2
                 stats = None

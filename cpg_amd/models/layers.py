@@ -113,13 +113,33 @@ class BiasGradSink(object):
         self.gb = None
 
 
+def _bn_bwd_rider(L, hint, gz, s):
+    """Reduce + finalize of the BatchNorm -> ReLU backward behind `hint` on gz (cpg_bn_relu_bwd's first two launches) and the buffers of
+    its apply pass: (ypre, gy, dgamma, dbeta, table), or None when the tensors do not suit the rider (alignment, 4 | HW, 2 GiB)."""
+    y = hint.ypre
+    N, C = y.shape[0], y.shape[1]
+    HW = y.numel() // (N * C)
+    if HW % 4 or y.numel() * 4 >= (1 << 31) or not y.is_contiguous() or not gz.is_contiguous() or (y.data_ptr() | gz.data_ptr()) & 15:
+        return None
+    gyb = torch.empty_like(y)
+    dgamma, dbeta = torch.empty_like(hint.gamma), torch.empty_like(hint.beta)
+    table = torch.empty((C, 8), dtype=torch.float32, device=y.device)
+    wsb, nbb = _lib.workspace(L.cpg_bn_workspace_bytes(N, C, HW), y.device)
+    rc = L.cpg_bn_relu_bwd_reduce(_lib.dptr(y), _lib.dptr(gz, name='grad_output'), _lib.dptr(hint.gamma), _lib.dptr(hint.beta),
+                                  _lib.dptr(hint.mean), _lib.dptr(hint.invstd), _lib.dptr(dgamma), _lib.dptr(dbeta), _lib.dptr(table),
+                                  N, C, HW, _lib.dptr(wsb), nbb, s)
+    _lib.check('cpg_bn_relu_bwd_reduce', rc)
+    return y, gyb, dgamma, dbeta, table
+
+
 class _MaskedConv2dFn(torch.autograd.Function):
     """y = conv2d(x, W * bin(pm), b) and its gradients, all through the C ABI."""
 
     @staticmethod
     def forward(ctx, x, weight, pm, bias, thr, stride, padding, dilation, groups, bn_stats=False, math='fp32', bn_hint=None, bias_sink=None):
         # bn_hint (fused_bn.BnBwdHint or None): `x` is relu(bn(ypre)) of the layer below and nothing else consumes it -- the
-        # input-gradient kernel may then do that BatchNorm's backward reduction in its epilogue (cpg_conv2d_dgrad_bnbwd)
+        # input-gradient kernel may then do that BatchNorm's backward reduction in its epilogue (cpg_conv2d_dgrad_bnbwd, hint.epilogue),
+        # or the weight-gradient kernel that BatchNorm's backward apply pass as a side job (cpg_conv2d_wgrad_attach_bn_bwd, hint.rider)
         ctx.bn_hint = bn_hint
         ctx.set_materialize_grads(False)         # (no zero-filled "gradient" tensor for the statistics output on every backward)
         ctx.bias_sink = bias_sink if bias is not None else None     # BiasGradSink: the activation behind this conv delivers the bias gradient
@@ -174,7 +194,7 @@ class _MaskedConv2dFn(torch.autograd.Function):
         # between: autograd's version check on the saved w / pm guards exactly that).  One launch instead of two per layer and step.
         ctx.packed_dgrad = pk_f = None
         if PACK_CACHE and ctx.needs_input_grad[0]:
-            uses_bnbwd = bn_hint is not None and L.cpg_conv2d_dgrad_bnbwd_tiles(ctypes.byref(d)) > 0      # (that launch packs for the direct kernels)
+            uses_bnbwd = bn_hint is not None and bn_hint.epilogue and L.cpg_conv2d_dgrad_bnbwd_tiles(ctypes.byref(d)) > 0      # (that launch packs for the direct kernels)
             nb_f, nb_d = _pack_bytes(L, d, 2 if tiles > 0 else 0), (0 if uses_bnbwd else _pack_bytes(L, d, 1))
             if nb_f and nb_d:
                 pk_f = torch.empty(nb_f // 4, dtype=torch.float32, device=x.device)
@@ -220,6 +240,7 @@ class _MaskedConv2dFn(torch.autograd.Function):
         L = _lib.lib()
         s = _lib.stream_ptr()
         gx = gw = gpm = gb = None
+        hint, ctx.bn_hint = ctx.bn_hint, None
         ws, nbytes = _lib.workspace(L.cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
         if ctx.needs_input_grad[0] and ctx.bf16:
             gx = torch.empty_like(x)
@@ -230,8 +251,7 @@ class _MaskedConv2dFn(torch.autograd.Function):
             _lib.check('cpg_conv2d_dgrad_bf16', rc)
         elif ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            hint, ctx.bn_hint = ctx.bn_hint, None
-            tiles = L.cpg_conv2d_dgrad_bnbwd_tiles(ctypes.byref(d)) if (hint is not None and hint.usable(x)) else 0
+            tiles = L.cpg_conv2d_dgrad_bnbwd_tiles(ctypes.byref(d)) if (hint is not None and hint.epilogue and hint.usable(x)) else 0
             if tiles > 0:
                 # gx becomes g * [bn(ypre) > 0] and the BatchNorm's two backward sums come out per (channel, pixel tile)
                 partials = torch.empty((d.C, tiles, 2), dtype=torch.float32, device=x.device)
@@ -265,6 +285,12 @@ class _MaskedConv2dFn(torch.autograd.Function):
             given = sink.gb if sink is not None else None
             if given is not None:                # the PReLU behind this conv already summed gy per channel (cpg_prelu_bwd_bias)
                 sink.gb, gb = None, None
+            rider = None
+            if (hint is not None and hint.rider and not ctx.bf16 and gx is not None and hint.partials is None and hint.usable(x)
+                    and L.cpg_conv2d_wgrad_rider_supported(ctypes.byref(d))):
+                # x = relu(bn(ypre)) and gx is the whole gradient reaching it: that BatchNorm's reduce + finalize now, its apply pass
+                # inside this layer's weight-gradient kernel; _BnReluFn.backward finds the three results in the hint
+                rider = _bn_bwd_rider(L, hint, gx, s)
             if ctx.bf16 and not ctx.has_bias and L.cpg_conv2d_wgrad_bf16_supported(ctypes.byref(d)):
                 wsw, nbw = _lib.workspace(L.cpg_conv2d_wgrad_bf16_workspace_bytes(ctypes.byref(d)), x.device)
                 wgrad = L.cpg_conv2d_wgrad_bf16x3 if ctx.x3 else L.cpg_conv2d_wgrad_bf16
@@ -272,9 +298,16 @@ class _MaskedConv2dFn(torch.autograd.Function):
                            _lib.dptr(gw), _lib.dptr(gpm), _lib.dptr(wsw), nbw, s)
                 _lib.check('cpg_conv2d_wgrad_bf16', rc)
             else:
+                if rider is not None:
+                    ypre, gyb, table = rider[0], rider[1], rider[4]
+                    _lib.check('cpg_conv2d_wgrad_attach_bn_bwd', L.cpg_conv2d_wgrad_attach_bn_bwd(
+                        _lib.dptr(ypre), _lib.dptr(gx), _lib.dptr(gyb), _lib.dptr(table), ypre.shape[0], ypre.shape[1],
+                        ypre.numel() // (ypre.shape[0] * ypre.shape[1])))
                 rc = L.cpg_conv2d_wgrad(ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), _lib.dptr(w), _lib.dptr(p), thr,
                                         _lib.dptr(gw), _lib.dptr(gpm), _lib.dptr(gb), _lib.dptr(ws), nbytes, s)
                 _lib.check('cpg_conv2d_wgrad', rc)
+                if rider is not None:
+                    hint.gz, hint.result = gx, rider[1:4]
             if given is not None:
                 gb = given
         return gx, gw, gpm, gb, None, None, None, None, None, None, None, None, None

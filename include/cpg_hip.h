@@ -109,7 +109,8 @@ int32_t cpg_get_shared_chip_hint(void);
  *       CPG_NO_STEM_FUSE (fused stem recomputes y instead of reading it back: same bits where the summation order is the same),
  *       and cpg_set_shared_chip_hint (above);
  *   no effect on any result bit (scheduling / mapping of the same work):
- *       CPG_WINO_PERSIST, CPG_WINO_GRIDS, CPG_WW_XCD, CPG_WG3_SHARE, CPG_NO_DEAD_SKIP (skips work whose inputs are exactly zero).
+ *       CPG_WINO_PERSIST, CPG_WINO_GRIDS, CPG_WW_XCD, CPG_WG3_SHARE, CPG_NO_DEAD_SKIP (skips work whose inputs are exactly zero),
+ *       CPG_NO_WW_RIDER (the BatchNorm backward apply as a pass of its own instead of inside the next weight gradient).
  * A run is bit-reproducible for a fixed set of switch values and a fixed hint; the defaults are what every committed number used.
  * The table is global state, but not per-call mutable state: no entry point writes it, and a concurrent cpg_set_option only ever
  * changes which of the above equivalent plans a LATER call picks (the workspace caveat of the hint applies to CPG_WW_UNITS,
@@ -173,6 +174,31 @@ size_t cpg_conv2d_pack_bytes(const cpg_conv_desc *desc, int32_t pass);
 int cpg_conv2d_pack(const cpg_conv_desc *desc, const float *w, const float *piggymask, float threshold, int32_t pass_a, void *packed_a,
                     size_t bytes_a, int32_t pass_b, void *packed_b, size_t bytes_b, void *stream);
 int cpg_conv2d_use_packed(const void *packed, size_t bytes);
+
+/* The apply pass of a BatchNorm -> ReLU backward as a SIDE JOB of the next layer's weight gradient (compatible addition: the ABI version
+ * stays 3).  The Winograd weight-gradient kernel of the wide layers is bound by its MFMA issue and leaves most of the HBM idle; the
+ * backward of conv l launches its input gradient first -- that is gz, the gradient reaching relu(bn(y)) of layer l - 1 -- and its weight
+ * gradient, which needs neither that BatchNorm's backward nor its result, second.  So the elementwise pass gy = bn_bwd(y, gz) of layer
+ * l - 1 (2 reads + 1 write, otherwise a kernel of its own) runs inside wgrad_l's main loop, every element once, its loads requested four
+ * k-steps ahead:
+ *   cpg_bn_relu_bwd_reduce(...): the reduce + finalize launches of cpg_bn_relu_bwd(relu = 1, train = 1) alone: dgamma, dbeta, and
+ *       table[C][8] = {mean, invstd, gamma, beta, mean(g), mean(g xhat), invstd * gamma, 0} (16-byte aligned) for the rider.
+ *   cpg_conv2d_wgrad_rider_supported(desc): 1 = cpg_conv2d_wgrad of this shape takes a rider: fp32 math on the Winograd kernel with the
+ *       four waves of a block sharing their input rows (>= 4 output-channel blocks, a multiple of 4), CPG_NO_WW_RIDER unset.
+ *   cpg_conv2d_wgrad_attach_bn_bwd(y, gz, gy, table, N, C, HW): arms THE CALLING THREAD -- the next cpg_conv2d_wgrad on it also writes
+ *       gy[N][C][HW] (4 | HW, below 2 GiB, all pointers 16-byte aligned, gy aliasing nothing).  One-shot: that call disarms the thread;
+ *       when its launch cannot carry the rider it fails with CPG_E_UNSUPPORTED before launching anything.  y == NULL disarms.
+ * gy is bit-equal to cpg_bn_relu_bwd's wherever it is a number, signed zeros and infinities included (one shared device function); where it
+ * is a NaN the other is a NaN too, but the NaN's sign and payload may differ (the two kernels compile the expression into different
+ * instruction sequences, a packed fma against a subtract).  The weight gradient is bit-equal to the call without a rider.
+ * DECISION on the version number: these three entries and CPG_NO_WW_RIDER were added WITHOUT raising CPG_ABI_VERSION (no existing
+ * signature or behaviour changes, and the version is pinned at 3 by the binding and its tests); cpg_version() therefore does not tell a
+ * caller whether they exist -- probe for them with dlsym("cpg_conv2d_wgrad_rider_supported"). */
+int cpg_bn_relu_bwd_reduce(const float *x, const float *gz, const float *gamma, const float *beta, const float *mean, const float *invstd,
+                           float *dgamma, float *dbeta, float *table, int32_t N, int32_t C, int32_t HW, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int32_t cpg_conv2d_wgrad_rider_supported(const cpg_conv_desc *desc);
+int cpg_conv2d_wgrad_attach_bn_bwd(const float *y, const float *gz, float *gy, const float *table, int32_t N, int32_t C, int32_t HW);
 
 /* ---- K5: F.linear of models/layers.py:194 and its autograd ----
  * x [batch][in], w [out][in], y [batch][out]; same masking / gradient rules as conv. */

@@ -4,6 +4,10 @@ launch stream).  Prints TFLOP/s per (layer, pass).  Used for A/B work on kernel 
 the command profiled with rocprofv3 --pmc.
 
     python tools/conv_bench.py [--batch 256] [--iters 5] [--only fwd,dgrad,wgrad] [--layers 3,7]
+
+Passes beside fwd / dgrad / wgrad and the opt-in bf16 ones: `wgradr` = the weight gradient with a BatchNorm-backward rider attached
+(cpg_conv2d_wgrad_attach_bn_bwd on a tensor shaped like the layer's input; skipped where the query says no), `bnbwd` / `bnred` = the
+standalone cpg_bn_relu_bwd on that tensor and its reduce + finalize part alone (their difference is the apply pass the rider replaces).
 """
 import argparse
 import ctypes
@@ -83,7 +87,24 @@ def main():
         P = _lib.dptr
         tiles = L.cpg_conv2d_bnstats_tiles(ctypes.byref(d))
         stats = torch.empty(max(1, K * tiles * 2) * 4, device=dev)       # (x 4: an --ab over kernel variants may change the tile count)
-        runs = {'fwdstats': lambda: L.cpg_conv2d_fwd_bnstats(ctypes.byref(d), P(x), P(w), P(pm), 5e-3, None, P(y), P(stats), stats.numel() * 4, P(ws), nb, st),
+        # the rider's side: BatchNorm -> ReLU backward of the layer below on a tensor shaped like x
+        want_rider = bool({'wgradr', 'bnbwd', 'bnred'} & set(a.only.split(',')))
+        ry, rgy = (torch.randn_like(x), torch.empty_like(x)) if want_rider else (None, None)       # (two more activation tensors: only when asked for)
+        table = torch.empty(C, 8, device=dev)
+        bp = [torch.rand(C, device=dev) + 0.5 for _ in range(4)]          # gamma, beta, mean, invstd
+        dgb = [torch.empty(C, device=dev) for _ in range(2)]
+        wsb, nbb = _lib.workspace(L.cpg_bn_workspace_bytes(a.batch, C, H * H), dev)
+        rider_ok = bool(L.cpg_conv2d_wgrad_rider_supported(ctypes.byref(d))) and x.numel() * 4 < (1 << 31)
+
+        def wgrad_rider():
+            rc = L.cpg_conv2d_wgrad_attach_bn_bwd(P(ry), P(gx), P(rgy), P(table), a.batch, C, H * H)
+            return rc or L.cpg_conv2d_wgrad(ctypes.byref(d), P(x), P(gy), P(w), P(pm), 5e-3, P(gw), P(gpm), None, P(ws), nb, st)
+        runs = {'wgradr': wgrad_rider,
+                'bnbwd': lambda: L.cpg_bn_relu_bwd(P(ry), P(gx), P(bp[0]), P(bp[1]), P(bp[2]), P(bp[3]), P(rgy), P(dgb[0]), P(dgb[1]), a.batch, C, H * H,
+                                                   1, 1, P(wsb), nbb, st),
+                'bnred': lambda: L.cpg_bn_relu_bwd_reduce(P(ry), P(gx), P(bp[0]), P(bp[1]), P(bp[2]), P(bp[3]), P(dgb[0]), P(dgb[1]), P(table), a.batch,
+                                                          C, H * H, P(wsb), nbb, st),
+                'fwdstats': lambda: L.cpg_conv2d_fwd_bnstats(ctypes.byref(d), P(x), P(w), P(pm), 5e-3, None, P(y), P(stats), stats.numel() * 4, P(ws), nb, st),
                 'fwd': lambda: L.cpg_conv2d_fwd(ctypes.byref(d), P(x), P(w), P(pm), 5e-3, None, P(y), P(ws), nb, st),
                 'dgrad': lambda: L.cpg_conv2d_dgrad(ctypes.byref(d), P(gy), P(w), P(pm), 5e-3, P(gx), P(ws), nb, st),
                 'fwd16': lambda: L.cpg_conv2d_fwd_bf16(ctypes.byref(d), P(x), P(w), P(pm), 5e-3, None, P(y), P(ws16), nb16, st),
@@ -96,6 +117,11 @@ def main():
         for k in a.only.split(','):
             if k in ('dgrad', 'dgrad16', 'dgradx3') and name == 'f0':
                 continue
+            if k == 'wgradr' and not rider_ok:
+                continue
+            if k == 'wgradr':
+                gx.normal_()
+                runs['bnred']()                   # (fills the coefficient table)
             if k in ('wgrad16', 'wgradx3') and not L.cpg_conv2d_wgrad_bf16_supported(ctypes.byref(d)):
                 continue
             if k in ('fwd16', 'dgrad16', 'fwdx3', 'dgradx3') and not L.cpg_conv2d_bf16_supported(ctypes.byref(d)):

@@ -54,6 +54,21 @@ struct WwGeom {
     int xcd;                  // blocks in XCD-contiguous order (block b runs on XCD b % 8: each XCD walks one eighth of the units)
 };
 
+// The RIDER (RI > 0, GS = 4 instances only): the apply pass of the BatchNorm -> ReLU backward of the layer BELOW, gy = bn_bwd_apply_one(y, gz)
+// over an [N][C][HW] tensor that this weight gradient neither reads nor writes, done as a side job of the main loop (the kernel is bound by
+// its MFMA issue and leaves most of the HBM idle).  Work is counted in wave-items: 64 lanes x float4 of ONE plane (ipp = ceil(HW / 4 / 64) items
+// per plane, the lanes past the plane's end get an out-of-range buffer offset: their loads return 0, their stores are dropped), so the
+// channel of an item is wave-uniform and its eight coefficients come through the scalar cache.  Wave u owns the items [u per, (u + 1) per)
+// (clamped to total); it does RI of them per stage and whatever is left after its last stage in a loop before the epilogue.
+struct WwRider {
+    const float *y, *gz;      // BatchNorm input (the conv output below) and the gradient that reached the ReLU
+    float *gy;                // result
+    const float *table;       // [C][8]: mean, invstd, gamma, beta, mean(g), mean(g xhat), invstd * gamma, 0
+    int C, HW, p4, ipp;       // p4 = HW / 4
+    int bytes;                // N * C * HW * 4 < 2^31
+    unsigned total, per;      // wave-items in all / per wave
+};
+
 @@MMA@@
 @@RD@@
 #define WW_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -74,10 +89,11 @@ __device__ unsigned long long ww_dbg[65536 * 8];
 // before it arrives at the barrier after which that buffer is written again).  gy rows stay wave-private.  Per stage and wave: 13 (GS = 4)
 // or 18 (GS = 2) vector-memory instructions and as many LDS store groups instead of 28 -- and the x rows are requested from L2 once per
 // GS units instead of once per unit.
-template <bool NARROW, int GS = 0>
+template <bool NARROW, int GS = 0, int RI = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void k_wgw(WwGeom g, const float *__restrict__ x, const float *__restrict__ gy, float *__restrict__ part) {
+void k_wgw(WwGeom g, const float *__restrict__ x, const float *__restrict__ gy, float *__restrict__ part, WwRider rd) {
     static_assert(GS == 0 || GS == 4 || (!NARROW && GS == 2), "shared staging: groups of 4 waves, or 2 on wide maps");
+    static_assert(RI == 0 || (GS == 4 && RI <= 2), "the rider's schedule slots exist in the GS = 4 bodies: one or two items per stage");
     constexpr int NG = GS ? 4 / GS : 0;                          // x-sharing groups per block
     // TS (GS == 4): the four waves of a group also SHARE THE INPUT TRANSFORM.  Their B operands are the same 16 values per lane (the
     // transformed patch of input channel li for the lane's tile): wave w computes transform row w only -- two patch rows, 4 + 4 adds
@@ -344,6 +360,50 @@ void k_wgw(WwGeom g, const float *__restrict__ x, const float *__restrict__ gy, 
             B[(m - 3) * 4 + 0] = v[0], B[(m - 3) * 4 + 1] = v[1], B[(m - 3) * 4 + 2] = v[2], B[(m - 3) * 4 + 3] = v[3];
         }
     };
+    // ---- R: the rider, item j of the stage in 6 micro steps (0, 1: request y and gz, 16 bytes per lane, and the channel's coefficients,
+    // four k-steps before use; 2-5: one element each; 5: store).  Wave-private, no LDS, no barrier.  Its loads are issued BEFORE the stage
+    // loads of k-steps 1 / 2 and its store after them, so the in-order vmcnt wait of the stage's LDS stores (k-step 6) covers all of them
+    // and the wait for the rider's loads (k-step 4 / 5) leaves the stage loads in flight.
+    constexpr int RJ = RI > 0 ? RI : 1;
+    typedef const float __attribute__((address_space(4))) *ww_cptr;
+    const __amdgpu_buffer_rsrc_t srd_ry = __builtin_amdgcn_make_buffer_rsrc((void *)rd.y, 0, rd.bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd_rz = __builtin_amdgcn_make_buffer_rsrc((void *)rd.gz, 0, rd.bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t srd_ro = __builtin_amdgcn_make_buffer_rsrc((void *)rd.gy, 0, rd.bytes, 0x00020000);
+    unsigned rq = 0, rq_end = 0, r_plane = 0;                    // (uniform) next item, end of the wave's range, the item's plane n C + c,
+    int r_sub = 0, r_c = 0;                                      // its 64-lane piece of the plane and its channel
+    if constexpr (RI > 0) {
+        rq = __builtin_amdgcn_readfirstlane(min(u * rd.per, rd.total));
+        rq_end = min(rq + rd.per, rd.total);
+        r_plane = rq / (unsigned)rd.ipp, r_sub = (int)(rq % (unsigned)rd.ipp), r_c = (int)(r_plane % (unsigned)rd.C);
+    }
+    f32x4 r_y[RJ], r_z[RJ];
+    float r_t[RJ][7];
+    int r_vo[RJ], r_so[RJ];
+    auto r_micro = [&](int j, int m) {
+        if (m == 0) {
+            const int left = rq < rq_end ? rd.p4 - r_sub * 64 : 0;
+            r_vo[j] = lane < left ? lane * 16 : kOOR;
+            r_so[j] = (int)(r_plane * (unsigned)rd.HW + (unsigned)r_sub * 256u) * 4;
+            r_y[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_ry, r_vo[j], r_so[j], 0));
+        } else if (m == 1) {
+            r_z[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_rz, r_vo[j], r_so[j], 0));
+            ww_cptr t = (ww_cptr)rd.table + r_c * 8;
+#pragma unroll
+            for (int k = 0; k < 7; ++k) r_t[j][k] = t[k];
+            if (rq < rq_end) {
+                ++rq;
+                if (++r_sub == rd.ipp) {
+                    r_sub = 0, ++r_plane;
+                    if (++r_c == rd.C) r_c = 0;
+                }
+            }
+        } else {
+            const int e = m - 2;
+            r_y[j][e] = bn_bwd_apply_one<true, true>(r_y[j][e], r_z[j][e], r_t[j][0], r_t[j][1], r_t[j][2], r_t[j][3], r_t[j][4], r_t[j][5], r_t[j][6]);
+            if (m == 5) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, r_y[j]), srd_ro, r_vo[j], r_so[j], 0);
+        }
+    };
+    (void)r_micro;
     // workgroup barrier that waits for this wave's LDS traffic only (__syncthreads would also wait for the stage loads in flight)
 #define WW_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
@@ -393,6 +453,15 @@ void k_wgw(WwGeom g, const float *__restrict__ x, const float *__restrict__ gy, 
     }
 
     WW_STAMP(3);
+    // What the stages of this wave did not cover: a last split with fewer stages, or more than 2 items per stage (a batch of one or two
+    // images).  A SLOW path: load, compute, store per item with nothing to hide the latency behind; the layers the rider is meant for
+    // (batch >= 32) only enter it in the waves of the last split.
+    if constexpr (RI > 0) {
+        while (rq < rq_end) {
+#pragma unroll
+            for (int m = 0; m < 6; ++m) r_micro(0, m);
+        }
+    }
     // ---- epilogue: dg = G^T M G per (k, c); M[i][j] = sigma_i sigma_j acc[4 i + j], sigma = (1, 1, 1, -1) ----
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
     float *pout = part + ((int64_t)split * 9 * g.K + k0) * g.C + c0 + li;
@@ -494,6 +563,25 @@ bool ww_plan(const cpg_conv_desc *d, WwPlan &p) {
     return p.blocks <= 0x7FFFFFFFll;
 }
 
+// the rider: which launches can carry one, and its geometry
+bool ww_rider_ok(const WwPlan &p) { return p.gs == 4 && !opt_on(OPT_NO_WW_RIDER); }
+bool ww_rider_plan(const WwPlan &p, const WgradRider &r, WwRider &rd, int &ri) {
+    if (r.N < 1 || r.C < 1 || r.HW < 4 || r.HW % 4 || (int64_t)r.N * r.C * r.HW * 4 >= (1ll << 31)) return false;
+    if ((((uintptr_t)r.y) | ((uintptr_t)r.gz) | ((uintptr_t)r.gy) | ((uintptr_t)r.table)) & 15) return false;
+    rd.y = r.y, rd.gz = r.gz, rd.gy = r.gy, rd.table = r.table;
+    rd.C = r.C, rd.HW = r.HW, rd.p4 = r.HW / 4, rd.ipp = (rd.p4 + 63) / 64;
+    rd.bytes = r.N * r.C * r.HW * 4;
+    // GS = 4 is only planned when the channel-block pairs are a multiple of 4 (ww_plan: npairs % 4 == 0), so units = npairs * nsplit fills
+    // whole blocks: no wave of the grid leaves early and the items can be dealt over ALL of them.  (A launch whose last block has idle
+    // waves is a GS = 0 / 2 launch: ww_rider_ok refuses it and the BatchNorm backward keeps its own apply pass.)
+    const int64_t total = (int64_t)r.N * r.C * rd.ipp, waves = (int64_t)p.g.nkb * p.g.ncb * p.g.nsplit;
+    if (waves % 4 != 0 || (waves + 3) / 4 != p.blocks) return false;
+    rd.total = (unsigned)total;
+    rd.per = (unsigned)((total + waves - 1) / waves);
+    ri = rd.per <= p.g.su ? 1 : 2;
+    return true;
+}
+
 }  // namespace
 
 #ifdef WG_TIMING
@@ -504,6 +592,12 @@ extern "C" int cpg_debug_ww_timing(unsigned long long *dst, int n) {
 extern "C" int cpg_conv3x3_wino_wgrad_ok(const cpg_conv_desc *d) {
     WwPlan p;
     return ww_plan(d, p) ? 1 : 0;
+}
+
+// 1: cpg_conv2d_wgrad of this shape takes a rider (cpg_conv2d_wgrad_attach_bn_bwd)
+extern "C" int cpg_conv3x3_wino_wgrad_rider_ok(const cpg_conv_desc *d) {
+    WwPlan p;
+    return ww_plan(d, p) && ww_rider_ok(p) ? 1 : 0;
 }
 
 extern "C" size_t cpg_conv3x3_wino_wgrad_workspace(const cpg_conv_desc *d) {
@@ -517,16 +611,34 @@ extern "C" int cpg_conv3x3_wino_wgrad(const cpg_conv_desc *d, const float *x, co
     if (!ww_plan(d, p)) return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_wgrad(winograd): shape not supported");
     if (ws == nullptr || ws_bytes < p.ws_bytes)
         return fail(CPG_E_WORKSPACE, "cpg_conv2d_wgrad(winograd): workspace %zu < %zu bytes", ws_bytes, p.ws_bytes);
-    if (p.narrow && p.gs == 4)
-        hipLaunchKernelGGL((k_wgw<true, 4>), dim3((unsigned)p.blocks), dim3(256), 0, stream, p.g, x, gy, (float *)ws);
+    WwRider rd{};
+    int ri = 0;
+    if (WgradRider &r = wgrad_rider(); r.armed) {                // (one-shot: cpg_conv2d_wgrad disarms the thread when it returns)
+        if (!ww_rider_ok(p) || !ww_rider_plan(p, r, rd, ri))
+            return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_wgrad(winograd): the attached BatchNorm backward cannot ride in this launch "
+                                           "(cpg_conv2d_wgrad_rider_supported, 4 | HW, < 2 GiB, 16-byte aligned pointers)");
+        if (rd.y == x || rd.gz == x || rd.gy == x || rd.gy == gy || (const float *)rd.gy == rd.y || (const float *)rd.gy == rd.gz)
+            return fail(CPG_E_INVALID, "cpg_conv2d_wgrad(winograd): the rider's result may not alias its inputs or the weight gradient's");
+    }
+    const dim3 grid((unsigned)p.blocks), block(256);
+    if (p.narrow && ri == 2)
+        hipLaunchKernelGGL((k_wgw<true, 4, 2>), grid, block, 0, stream, p.g, x, gy, (float *)ws, rd);
+    else if (p.narrow && ri == 1)
+        hipLaunchKernelGGL((k_wgw<true, 4, 1>), grid, block, 0, stream, p.g, x, gy, (float *)ws, rd);
+    else if (ri == 2)
+        hipLaunchKernelGGL((k_wgw<false, 4, 2>), grid, block, 0, stream, p.g, x, gy, (float *)ws, rd);
+    else if (ri == 1)
+        hipLaunchKernelGGL((k_wgw<false, 4, 1>), grid, block, 0, stream, p.g, x, gy, (float *)ws, rd);
+    else if (p.narrow && p.gs == 4)
+        hipLaunchKernelGGL((k_wgw<true, 4>), grid, block, 0, stream, p.g, x, gy, (float *)ws, rd);
     else if (p.narrow)
-        hipLaunchKernelGGL(k_wgw<true>, dim3((unsigned)p.blocks), dim3(256), 0, stream, p.g, x, gy, (float *)ws);
+        hipLaunchKernelGGL(k_wgw<true>, grid, block, 0, stream, p.g, x, gy, (float *)ws, rd);
     else if (p.gs == 4)
-        hipLaunchKernelGGL((k_wgw<false, 4>), dim3((unsigned)p.blocks), dim3(256), 0, stream, p.g, x, gy, (float *)ws);
+        hipLaunchKernelGGL((k_wgw<false, 4>), grid, block, 0, stream, p.g, x, gy, (float *)ws, rd);
     else if (p.gs == 2)
-        hipLaunchKernelGGL((k_wgw<false, 2>), dim3((unsigned)p.blocks), dim3(256), 0, stream, p.g, x, gy, (float *)ws);
+        hipLaunchKernelGGL((k_wgw<false, 2>), grid, block, 0, stream, p.g, x, gy, (float *)ws, rd);
     else
-        hipLaunchKernelGGL(k_wgw<false>, dim3((unsigned)p.blocks), dim3(256), 0, stream, p.g, x, gy, (float *)ws);
+        hipLaunchKernelGGL(k_wgw<false>, grid, block, 0, stream, p.g, x, gy, (float *)ws, rd);
     Epilogue ep{gw, nullptr, BIAS_NONE, 1, 1, pm, w, gpm, thr};
     const int64_t out_elems = (int64_t)d->K * d->C * 9;
     launch_split_reduce((const float *)ws, p.g.nsplit, out_elems, (int64_t)d->K * d->C, ep, stream);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generates cpg_amd/csrc/conv3x3_wino_wgrad.hip from tools/csrc/wino_wgrad_template.hip: the 16 fixed-AGPR MFMA macros, the accumulator
-zero-fill / read-back asm and the 2 x 7 x 16 schedule slots of the main loop (which micro-step of the staging work rides behind which
-MFMA).  The generated file is what is compiled and committed; re-run after editing the template or the slot tables.
+zero-fill / read-back asm and the 2 x 7 x 16 schedule slots of the main loop (which micro-step of the staging work -- and, in the GS = 4
+bodies, of the BatchNorm-backward rider -- rides behind which MFMA).  The generated file is what is compiled and committed; re-run after editing the template or the slot tables.
 
     python tools/gen_wino_wgrad.py
 """
@@ -40,6 +40,12 @@ def kstep(ks, cur, nxt, narrow=False, gs=0, half=0, kk=0):
                 if p in tm: work.append(tm[p] % (ks + 1, bb, nxt, xcur))
                 if p in am: work.append('t_micro(%d, %d, A%s, B%s, %s)' % (am[p], ks + 1, nxt, nxt, xcur))
                 if p == 7: work.append('WW_LDS_BARRIER()')
+                # the rider (RI items per stage, template csrc: r_micro) in the slots 12-15 that carry nothing else: requests in k-step 0,
+                # item 0 worked in k-step 4, item 1 in k-step 5
+                if p >= 12:
+                    if ks == 0: work.append('if constexpr (RI > %d) r_micro(%d, %d)' % ((p - 12) // 2, (p - 12) // 2, (p - 12) % 2))
+                    if ks == 4: work.append('if constexpr (RI > 0) r_micro(0, %d)' % (p - 10))
+                    if ks == 5: work.append('if constexpr (RI > 1) r_micro(1, %d)' % (p - 10))
             elif p < 14: work.append('t_micro(%d, %d, A%s, B%s, %s)' % (p, ks + 1, nxt, nxt, xcur))
             if gs:
                 if ks == 1 and p < min(first, nsi): work.append('g_load_s(%d)' % p)
