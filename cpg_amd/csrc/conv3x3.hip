@@ -26,7 +26,7 @@
 //   (igemm_core.h), which also applies the autograd epilogue gW = g*bin(pm), gPM = g*W.
 #include <algorithm>
 #include <cmath>
-#include "igemm_core.h"
+#include "cpg_dispatch.h"
 
 using namespace cpg;
 
@@ -1074,31 +1074,20 @@ inline size_t pack_floats(int c_read, int m) { return ((size_t)pad_to(c_read, 4)
 inline size_t live_words(int c_read, int m) { return (size_t)pad_to(m, 128) + 4 + pad_to(c_read, 4) / 4; }
 inline size_t pack_bytes(int c_read, int m) { return (pack_floats(c_read, m) + live_words(c_read, m)) * sizeof(float); }
 
-// stats != nullptr: forward with fused BatchNorm statistics.  tiles_out (optional) receives the number of pixel tiles;
-// dry: only compute it.
-}  // namespace
-extern "C" int cpg_conv3x3_wino_ok(int N, int c_read, int m, int H, int W);
-extern "C" int cpg_conv3x3_stem_ok(int N, int C, int K, int H, int W);
-extern "C" int cpg_conv3x3_stem_tiles(int N, int C, int K, int H, int W);
-extern "C" int cpg_conv3x3_stem_run(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr,
-                                    const float *bias, float *y, float *stats, hipStream_t stream);
-extern "C" size_t cpg_conv3x3_wino_pack_bytes(int c_read, int m);
-extern "C" size_t cpg_conv3x3_wino_tail_bytes(int N, int c_read, int m, int H, int W);
-extern "C" int cpg_conv3x3_wino_tiles(int N, int c_read, int m, int H, int W);
-extern "C" int cpg_conv3x3_wino_eval_ok(int N, int c_read, int m, int H, int W);
-extern "C" int cpg_conv3x3_wino_run_bn_eval(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr,
-                                            const float *bias, const float *gamma, const float *beta, const float *mean, const float *var,
-                                            float eps, int relu, int *live, size_t live_words, float *y, void *ws, size_t ws_bytes,
-                                            hipStream_t stream);
-extern "C" int cpg_conv3x3_wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w,
-                                    const float *pm, float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes,
-                                    hipStream_t stream);
-namespace {
+// What a forward / input-gradient launch does besides y = conv(x).  Filled field by field; everything is optional.
+struct C3Extra {
+    float *stats = nullptr;         // forward: [m][tiles][2] BatchNorm partial sums of y; with bb: the BatchNorm-backward partial sums
+    int *tiles_out = nullptr;       // receives the number of pixel tiles (the rows of `stats`)
+    bool dry = false;               // only compute tiles_out: nothing is launched, no pointer is touched
+    const C3BnEval *bn = nullptr;   // forward: eval-mode BatchNorm (+ ReLU) epilogue, dead-channel skip
+    const C3BnBwd *bb = nullptr;    // input gradient: BatchNorm-backward reduction of the layer below in the epilogue
+};
 
 template <class Cfg>
-int launch_fwd(C3Geom g, const float *x, const float *wp, const float *bias, float *y, hipStream_t stream, const char *what,
-               float *stats = nullptr, int *tiles_out = nullptr, bool dry = false, const C3BnEval *bnp = nullptr,
-               const C3BnBwd *bbp = nullptr) {
+int launch_fwd(C3Geom g, const float *x, const float *wp, const float *bias, float *y, hipStream_t stream, const char *what, const C3Extra &ex) {
+    float *const stats = ex.stats;
+    const C3BnEval *const bnp = ex.bn;
+    const C3BnBwd *const bbp = ex.bb;
     const C3BnEval bn = bnp ? *bnp : C3BnEval{nullptr, nullptr, nullptr, nullptr, 0.0f, 0, nullptr};
     const C3BnBwd bb = bbp ? *bbp : C3BnBwd{nullptr, nullptr, nullptr, nullptr, nullptr};
     g.tiles_x = (g.OW + Cfg::TW - 1) / Cfg::TW;           // (tiles cover the OUTPUT map; = the input map for the stride-1 tiles)
@@ -1107,8 +1096,8 @@ int launch_fwd(C3Geom g, const float *x, const float *wp, const float *bias, flo
     const int64_t blocks = Cfg::VROWS ? (int64_t)(((int64_t)g.N * Cfg::TH + Cfg::VROWS - 1) / Cfg::VROWS) * g.tiles_m
                                       : (int64_t)((g.N + Cfg::NIMG - 1) / Cfg::NIMG) * g.tiles_x * g.tiles_y * g.tiles_m;
     if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "conv3x3: grid too large");
-    if (tiles_out) *tiles_out = g.ksplit > 1 ? 0 : (int)(blocks / g.tiles_m);      // no fused statistics on split tiles
-    if (dry) return CPG_OK;
+    if (ex.tiles_out) *ex.tiles_out = g.ksplit > 1 ? 0 : (int)(blocks / g.tiles_m);      // no fused statistics on split tiles
+    if (ex.dry) return CPG_OK;
     if (g.ksplit > 1) {
         if (stats != nullptr || bnp != nullptr || bbp != nullptr) return fail(CPG_E_UNSUPPORTED, "conv3x3: no fused epilogue on channel-split tiles");
         hipError_t e = hipMemsetAsync(y, 0, (size_t)g.N * g.M * g.OH * g.OW * sizeof(float), stream);
@@ -1135,41 +1124,41 @@ int launch_fwd(C3Geom g, const float *x, const float *wp, const float *bias, flo
 
 // c_read / m: channels contracted over / produced.  w is the layer's [K][C][3][3] weight.
 int run_fwd(bool dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
-            float thr, const float *bias, float *y, void *ws, size_t ws_bytes, hipStream_t stream, float *stats = nullptr,
-            int *tiles_out = nullptr, bool dry = false, const C3BnEval *bn = nullptr, const C3BnBwd *bb = nullptr) {
+            float thr, const float *bias, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const C3Extra &extra = C3Extra()) {
     const char *what = dgrad ? "cpg_conv2d_dgrad(3x3)" : "cpg_conv2d_fwd(3x3)";
+    C3Extra ex = extra;             // (ex.bn is redirected to a copy with the workspace's liveness words below)
     // Winograd F(2x2, 3x3) (conv3x3_wino.hip) takes the training forward (with or without the BatchNorm statistics) and the plain
     // input gradient of every even-sized map with >= 16 channels on both sides: 2.25x fewer MFMAs, 1.36-1.47x the speed of the
     // direct kernels below.  The inference epilogues (eval BatchNorm, dead-channel skip) and BRED stay on the direct kernels.
-    if (bn == nullptr && bb == nullptr && cpg_conv3x3_wino_ok(N, c_read, m, H, W)) {
-        if (tiles_out) *tiles_out = cpg_conv3x3_wino_tiles(N, c_read, m, H, W);
-        if (dry) return CPG_OK;
-        return cpg_conv3x3_wino_run(dgrad ? 1 : 0, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, stats, ws, ws_bytes, stream);
+    if (ex.bn == nullptr && ex.bb == nullptr && cpg_conv3x3_wino_ok(N, c_read, m, H, W)) {
+        if (ex.tiles_out) *ex.tiles_out = cpg_conv3x3_wino_tiles(N, c_read, m, H, W);
+        if (ex.dry) return CPG_OK;
+        return cpg_conv3x3_wino_run(dgrad ? 1 : 0, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, ex.stats, ws, ws_bytes, stream);
     }
-    if (!dry && cpg::pack_query()) return CPG_OK;       // (cpg_conv2d_pack's query: only the Winograd route above records a job)
+    if (!ex.dry && cpg::pack_query()) return CPG_OK;       // (cpg_conv2d_pack's query: only the Winograd route above records a job)
     // ... and the inference forward with the eval-mode BatchNorm epilogue and the dead-channel skip (k_wg1<.., BNE>).  Workspace layout:
     // [the direct kernels' packed-weight region (unused) | liveness words, where cpg_conv3x3_fwd_bn_eval looks for them | U]
-    if (bn != nullptr && bb == nullptr && !dgrad && stats == nullptr && !dry && cpg_conv3x3_wino_eval_ok(N, c_read, m, H, W)) {
+    if (ex.bn != nullptr && ex.bb == nullptr && !dgrad && ex.stats == nullptr && !ex.dry && cpg_conv3x3_wino_eval_ok(N, c_read, m, H, W)) {
         const size_t off = (pack_bytes(c_read, m) + 15) / 16 * 16;
         if (ws == nullptr || ws_bytes < off) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, off);
-        int *live = bn->live != nullptr ? reinterpret_cast<int *>((float *)ws + pack_floats(c_read, m)) : nullptr;
-        return cpg_conv3x3_wino_run_bn_eval(N, c_read, m, H, W, x, w, pm, thr, bias, bn->gamma, bn->beta, bn->mean, bn->var, bn->eps, bn->relu,
+        int *live = ex.bn->live != nullptr ? reinterpret_cast<int *>((float *)ws + pack_floats(c_read, m)) : nullptr;
+        return cpg_conv3x3_wino_run_bn_eval(N, c_read, m, H, W, x, w, pm, thr, bias, ex.bn->gamma, ex.bn->beta, ex.bn->mean, ex.bn->var, ex.bn->eps, ex.bn->relu,
                                             live, live_words(c_read, m), y, (char *)ws + off, ws_bytes - off, stream);
     }
     // the <= 3-channel stem (conv3x3_stem.hip: one persistent wave per tile, weights in registers, HBM-bound)
-    if (!dgrad && bn == nullptr && bb == nullptr && cpg_conv3x3_stem_ok(N, c_read, m, H, W)) {
-        if (tiles_out) *tiles_out = cpg_conv3x3_stem_tiles(N, c_read, m, H, W);
-        if (dry) return CPG_OK;
-        return cpg_conv3x3_stem_run(N, c_read, m, H, W, x, w, pm, thr, bias, y, stats, stream);
+    if (!dgrad && ex.bn == nullptr && ex.bb == nullptr && cpg_conv3x3_stem_ok(N, c_read, m, H, W)) {
+        if (ex.tiles_out) *ex.tiles_out = cpg_conv3x3_stem_tiles(N, c_read, m, H, W);
+        if (ex.dry) return CPG_OK;
+        return cpg_conv3x3_stem_run(N, c_read, m, H, W, x, w, pm, thr, bias, y, ex.stats, stream);
     }
     float *wp = (float *)ws;
     const int rows_c = pad_to(c_read, 4), Mp = pad_to(m, 128);
-    if (!dry) {
+    if (!ex.dry) {
         const size_t need = pack_bytes(c_read, m);
         if (ws == nullptr || ws_bytes < need) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
         CPG_REQUIRE((((uintptr_t)ws) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
         int *live = nullptr;
-        if (bn != nullptr && bn->live != nullptr) {          // (bn->live is only a request flag here; the words live in the workspace)
+        if (ex.bn != nullptr && ex.bn->live != nullptr) {          // (bn->live is only a request flag here; the words live in the workspace)
             live = reinterpret_cast<int *>(wp + pack_floats(c_read, m));
             hipError_t e = hipMemsetAsync(live, 0, live_words(c_read, m) * sizeof(int), stream);
             if (e != hipSuccess) return hip_status(e, what);
@@ -1178,30 +1167,30 @@ int run_fwd(bool dgrad, int N, int c_read, int m, int H, int W, int K, int C, co
                            rows_c, Mp, dgrad ? 1 : 0, live);
     }
     C3BnEval bn_local;
-    if (bn != nullptr) {
-        bn_local = *bn;
-        bn_local.live = (bn->live != nullptr && !dry) ? reinterpret_cast<int *>(wp + pack_floats(c_read, m)) : nullptr;
-        bn = &bn_local;
+    if (ex.bn != nullptr) {
+        bn_local = *ex.bn;
+        bn_local.live = (ex.bn->live != nullptr && !ex.dry) ? reinterpret_cast<int *>(wp + pack_floats(c_read, m)) : nullptr;
+        ex.bn = &bn_local;
     }
     C3Geom g{N, c_read, H, W, m, Mp, 0, 0, 0, H, W, dgrad ? 1 : 0, 1};
     if (const int force = opt(OPT_C3_FORCE); force != OPT_UNSET) {        // A/B experiments only (tools/conv_bench.py --ab)
         switch (force) {
-            case 0: return launch_fwd<CfgM128>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
-            case 1: return launch_fwd<CfgM64>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
-            case 2: return launch_fwd<CfgS16>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
-            case 3: return launch_fwd<CfgD128>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
-            case 4: return launch_fwd<CfgD64>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
-            case 7: return launch_fwd<CfgV14>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
-            case 8: g.ksplit = 2; return launch_fwd<CfgV14>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
-            default: if (c_read % 4 == 0) return launch_fwd<CfgP28>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
+            case 0: return launch_fwd<CfgM128>(g, x, wp, bias, y, stream, what, ex);
+            case 1: return launch_fwd<CfgM64>(g, x, wp, bias, y, stream, what, ex);
+            case 2: return launch_fwd<CfgS16>(g, x, wp, bias, y, stream, what, ex);
+            case 3: return launch_fwd<CfgD128>(g, x, wp, bias, y, stream, what, ex);
+            case 4: return launch_fwd<CfgD64>(g, x, wp, bias, y, stream, what, ex);
+            case 7: return launch_fwd<CfgV14>(g, x, wp, bias, y, stream, what, ex);
+            case 8: g.ksplit = 2; return launch_fwd<CfgV14>(g, x, wp, bias, y, stream, what, ex);
+            default: if (c_read % 4 == 0) return launch_fwd<CfgP28>(g, x, wp, bias, y, stream, what, ex);
         }
     }
-    if (W == 7 && H == 7 && c_read % 4 == 0) return launch_fwd<CfgV7>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
+    if (W == 7 && H == 7 && c_read % 4 == 0) return launch_fwd<CfgV7>(g, x, wp, bias, y, stream, what, ex);
     // 14 x 14 maps: the 14 x 16 single-image tile wastes 1/8 of its MFMAs on two padding columns; the zero-waste virtual-row
     // tile alone measured the same, because its N*14/16 tiles put 3.5 block-equivalents on each CU, which rounds up to 4
     // (at batch 256 the layer is too small for 256 CUs).  Halving the blocks (two per tile, each half of the channel chunks,
     // atomically added into a zeroed y) makes it 7 half-blocks per CU.
-    if (W == 14 && H == 14 && m > 64 && c_read % 8 == 0 && bn == nullptr && !opt_on(OPT_NO_V14)) {
+    if (W == 14 && H == 14 && m > 64 && c_read % 8 == 0 && ex.bn == nullptr && !opt_on(OPT_NO_V14)) {
         // ... when that balances: per-CU MFMA time in block-equivalents of either tiling (the split pays a memset, atomics
         // and a second prologue; at 256 channels and batch 256 -- 3.5 half-blocks per CU -- it measured no gain)
         const int tm = (m + 127) / 128;
@@ -1209,20 +1198,42 @@ int run_fwd(bool dgrad, int N, int c_read, int m, int H, int W, int K, int C, co
         const double t_split = std::ceil(2.0 * (((int64_t)N * 14 + 15) / 16) * tm / kCUs) * 0.5 * 1.04;
         if (t_split < 0.9 * t_single) {
             g.ksplit = 2;
-            return launch_fwd<CfgV14>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
+            return launch_fwd<CfgV14>(g, x, wp, bias, y, stream, what, ex);
         }
     }
-    if (W <= 16 && H <= 16 && m > 64) return launch_fwd<CfgS16>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
+    if (W <= 16 && H <= 16 && m > 64) return launch_fwd<CfgS16>(g, x, wp, bias, y, stream, what, ex);
     if (W == 28 && H % 4 == 0 && m > 64 && c_read % 4 == 0)
-        return launch_fwd<CfgP28>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
+        return launch_fwd<CfgP28>(g, x, wp, bias, y, stream, what, ex);
     // 56, 112, 168 ...: a 32-wide tile would waste 12.5 % of the MFMAs.  The 64-channel 8 x 56 tile (2 x 2 waves) measured
     // 1-2 % faster than the 128-channel 4 x 56 tile (4 x 1 waves) on every 56- and 112-wide VGG layer, also for m > 64
     // (interleaved in-process A/B, tools/conv_bench.py --ab CPG_C3_FORCE=3,4).
     // (224-wide maps divide by 32 too; the 8 x 56 tile measured 0.8 % faster there as well -- except for the HBM-bound 3-channel
     // stem, which prefers the 8 x 32 tile by 9 %)
-    if (W % 56 == 0 && (W % 32 != 0 || c_read >= 16)) return launch_fwd<CfgD64>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
-    if (m <= 64) return launch_fwd<CfgM64>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
-    return launch_fwd<CfgM128>(g, x, wp, bias, y, stream, what, stats, tiles_out, dry, bn, bb);
+    if (W % 56 == 0 && (W % 32 != 0 || c_read >= 16)) return launch_fwd<CfgD64>(g, x, wp, bias, y, stream, what, ex);
+    if (m <= 64) return launch_fwd<CfgM64>(g, x, wp, bias, y, stream, what, ex);
+    return launch_fwd<CfgM128>(g, x, wp, bias, y, stream, what, ex);
+}
+
+int run_fwd_s2(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y, void *ws,
+               size_t ws_bytes, hipStream_t stream, const C3Extra &ex);        // (the stride-2 class, below)
+
+// Pixel tiles of the launch a call would make, from a dry run of its dispatch; 0: there is no such launch.
+enum C3Probe { PROBE_FWD, PROBE_DGRAD_BNBWD, PROBE_FWD_S2 };
+int dry_run_tiles(const cpg_conv_desc *d, C3Probe which) {
+    int tiles = 0;
+    const C3BnBwd probe{nullptr, nullptr, nullptr, nullptr, nullptr};
+    C3Extra ex;
+    ex.tiles_out = &tiles;
+    ex.dry = true;
+    if (which == PROBE_DGRAD_BNBWD) ex.bb = &probe;
+    int rc;
+    if (which == PROBE_FWD_S2)
+        rc = run_fwd_s2(d, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, 0, nullptr, ex);
+    else if (which == PROBE_FWD)
+        rc = run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, 0, nullptr, ex);
+    else           // reads gy (K channels), produces gx (C channels)
+        rc = run_fwd(true, d->N, d->K, d->C, d->H, d->W, d->K, d->C, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, 0, nullptr, ex);
+    return rc == CPG_OK ? tiles : 0;
 }
 
 }  // namespace
@@ -1250,17 +1261,13 @@ int cpg_conv3x3_fwd(const cpg_conv_desc *d, const float *x, const float *w, cons
 }
 
 // forward that also writes the per-(channel, pixel tile) BatchNorm partial sums; tiles = cpg_conv3x3_bnstats_tiles(d)
-int cpg_conv3x3_bnstats_tiles(const cpg_conv_desc *d) {
-    int tiles = 0;
-    if (run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, 0, nullptr,
-                nullptr, &tiles, true) != CPG_OK)
-        return 0;
-    return tiles;
-}
+int cpg_conv3x3_bnstats_tiles(const cpg_conv_desc *d) { return dry_run_tiles(d, PROBE_FWD); }
 int cpg_conv3x3_fwd_bnstats(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                             float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream) {
     CPG_REQUIRE(x && w && y && stats, "cpg_conv2d_fwd_bnstats: null pointer");
-    return run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, x, w, pm, thr, bias, y, ws, ws_bytes, stream, stats);
+    C3Extra ex;
+    ex.stats = stats;
+    return run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, x, w, pm, thr, bias, y, ws, ws_bytes, stream, ex);
 }
 
 // forward with the inference-mode BatchNorm (+ ReLU) that follows the conv folded into the epilogue (Manager.validate's path)
@@ -1271,8 +1278,9 @@ int cpg_conv3x3_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float 
     static int dummy;
     const bool skip = !opt_on(OPT_NO_DEAD_SKIP);
     const C3BnEval bn{gamma, beta, mean, var, eps, relu, skip ? &dummy : nullptr};
-    int rc = run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, x, w, pm, thr, bias, y, ws, ws_bytes, stream, nullptr, nullptr, false,
-                     &bn);
+    C3Extra ex;
+    ex.bn = &bn;
+    int rc = run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, x, w, pm, thr, bias, y, ws, ws_bytes, stream, ex);
     if (rc == CPG_OK && skip_stats != nullptr) {
         // {4 * (input chunks up to the last live one), output blocks skipped}: device-to-device copy of the two words behind live[Mp]
         if (skip) {
@@ -1296,21 +1304,16 @@ int cpg_conv3x3_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, c
 
 // input gradient whose epilogue also does the BatchNorm-backward reduction of the layer below (see C3BnBwd).  tiles = 0: this
 // shape has no such path (channel-split 14 x 14 tiles).
-int cpg_conv3x3_dgrad_bnbwd_tiles(const cpg_conv_desc *d) {
-    int tiles = 0;
-    const C3BnBwd probe{nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (run_fwd(true, d->N, d->K, d->C, d->H, d->W, d->K, d->C, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                &tiles, true, nullptr, &probe) != CPG_OK)
-        return 0;
-    return tiles;
-}
+int cpg_conv3x3_dgrad_bnbwd_tiles(const cpg_conv_desc *d) { return dry_run_tiles(d, PROBE_DGRAD_BNBWD); }
 int cpg_conv3x3_dgrad_bnbwd(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, const float *ypre,
                             const float *gamma, const float *beta, const float *mean, const float *invstd, float *gx, float *partials,
                             void *ws, size_t ws_bytes, hipStream_t stream) {
     CPG_REQUIRE(gy && w && gx && ypre && gamma && beta && mean && invstd && partials, "cpg_conv2d_dgrad_bnbwd: null pointer");
     const C3BnBwd bb{ypre, gamma, beta, mean, invstd};
-    return run_fwd(true, d->N, d->K, d->C, d->H, d->W, d->K, d->C, gy, w, pm, thr, nullptr, gx, ws, ws_bytes, stream, partials, nullptr, false,
-                   nullptr, &bb);
+    C3Extra ex;
+    ex.stats = partials;
+    ex.bb = &bb;
+    return run_fwd(true, d->N, d->K, d->C, d->H, d->W, d->K, d->C, gy, w, pm, thr, nullptr, gx, ws, ws_bytes, stream, ex);
 }
 
 // ---- wgrad host side -------------------------------------------------------------------------
@@ -1359,23 +1362,30 @@ inline int w3_pick(const cpg_conv_desc *d) {
 }
 }  // namespace
 
-extern "C" int cpg_conv3x3_wino_wgrad_ok(const cpg_conv_desc *d);
-extern "C" size_t cpg_conv3x3_wino_wgrad_workspace(const cpg_conv_desc *d);
-extern "C" int cpg_conv3x3_wino_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr,
-                                      float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
+namespace {
+struct WSPlan {
+    int tiles_x, tiles_y, blocks_co, nsplit, units_per_split;
+    size_t ws_bytes;
+};
+WSPlan ws_plan(const cpg_conv_desc *d) {
+    WSPlan p;
+    p.tiles_x = (d->W + WSCfg::TW - 1) / WSCfg::TW;
+    p.tiles_y = (d->H + WSCfg::TH - 1) / WSCfg::TH;
+    p.blocks_co = (d->K + 63) / 64;
+    const int64_t units = (int64_t)d->N * p.tiles_x * p.tiles_y;
+    int64_t want = (8 * kCUs + p.blocks_co - 1) / p.blocks_co;     // HBM-streaming kernel: ~8 blocks per CU
+    if (want > units) want = units;
+    if (want < 1) want = 1;
+    p.units_per_split = (int)((units + want - 1) / want);
+    p.nsplit = (int)((units + p.units_per_split - 1) / p.units_per_split);
+    p.ws_bytes = (size_t)p.nsplit * d->K * d->C * 9 * sizeof(float);
+    return p;
+}
+}  // namespace
 
 size_t cpg_conv3x3_wgrad_workspace(const cpg_conv_desc *d) {
     if (cpg_conv3x3_wino_wgrad_ok(d)) return cpg_conv3x3_wino_wgrad_workspace(d);
-    if (d->C <= 3) {            // stem kernel: same formula as ws_plan() below
-        const int tiles = ((d->W + 31) / 32) * ((d->H + 3) / 4);
-        const int64_t units = (int64_t)d->N * tiles;
-        const int blocks_co = (d->K + 63) / 64;
-        int64_t want = (8 * kCUs + blocks_co - 1) / blocks_co;
-        if (want > units) want = units;
-        if (want < 1) want = 1;
-        const int64_t per = (units + want - 1) / want;
-        return (size_t)((units + per - 1) / per) * d->K * d->C * 9 * sizeof(float);
-    }
+    if (d->C <= WSCfg::CMAX) return ws_plan(d).ws_bytes;
     switch (w3_pick(d)) {
         case 1: return w3_plan<W3Mid>(d).ws_bytes;
         case 2: return w3_plan<W3Nar>(d).ws_bytes;
@@ -1398,27 +1408,6 @@ static int w3_launch(const cpg_conv_desc *d, const float *x, const float *gy, co
     CPG_CHECK_LAUNCH("cpg_conv2d_wgrad(3x3)");
     return CPG_OK;
 }
-
-namespace {
-struct WSPlan {
-    int tiles_x, tiles_y, blocks_co, nsplit, units_per_split;
-    size_t ws_bytes;
-};
-WSPlan ws_plan(const cpg_conv_desc *d) {
-    WSPlan p;
-    p.tiles_x = (d->W + WSCfg::TW - 1) / WSCfg::TW;
-    p.tiles_y = (d->H + WSCfg::TH - 1) / WSCfg::TH;
-    p.blocks_co = (d->K + 63) / 64;
-    const int64_t units = (int64_t)d->N * p.tiles_x * p.tiles_y;
-    int64_t want = (8 * kCUs + p.blocks_co - 1) / p.blocks_co;     // HBM-streaming kernel: ~8 blocks per CU
-    if (want > units) want = units;
-    if (want < 1) want = 1;
-    p.units_per_split = (int)((units + want - 1) / want);
-    p.nsplit = (int)((units + p.units_per_split - 1) / p.units_per_split);
-    p.ws_bytes = (size_t)p.nsplit * d->K * d->C * 9 * sizeof(float);
-    return p;
-}
-}  // namespace
 
 int cpg_conv3x3_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr,
                       float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream) {
@@ -1453,17 +1442,17 @@ using S2G128 = C3Cfg<128, 4, 32, 2, 2, 4, 2, 1, 0, 1>;  // anything else
 using S2G64 = C3Cfg<64, 8, 32, 1, 4, 4, 2, 1, 0, 1>;    // ... with <= 64 output channels
 
 template <class Cfg>
-int launch_fwd_s2(C3Geom g, const float *x, const float *wp, const float *bias, float *y, hipStream_t stream, float *stats,
-                  int *tiles_out, bool dry, const C3BnEval *bnp) {
-    const C3BnEval bn = bnp ? *bnp : C3BnEval{nullptr, nullptr, nullptr, nullptr, 0.0f, 0, nullptr};
+int launch_fwd_s2(C3Geom g, const float *x, const float *wp, const float *bias, float *y, hipStream_t stream, const C3Extra &ex) {
+    float *const stats = ex.stats;
+    const C3BnEval bn = ex.bn ? *ex.bn : C3BnEval{nullptr, nullptr, nullptr, nullptr, 0.0f, 0, nullptr};
     const C3BnBwd bb{nullptr, nullptr, nullptr, nullptr, nullptr};
     g.tiles_x = (g.OW + Cfg::TW - 1) / Cfg::TW;
     g.tiles_y = (g.OH + Cfg::TH - 1) / Cfg::TH;
     g.tiles_m = (g.M + Cfg::BM - 1) / Cfg::BM;
     const int64_t blocks = (int64_t)((g.N + Cfg::NIMG - 1) / Cfg::NIMG) * g.tiles_x * g.tiles_y * g.tiles_m;
     if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "conv3x3 s2: grid too large");
-    if (tiles_out) *tiles_out = (int)(blocks / g.tiles_m);
-    if (dry) return CPG_OK;
+    if (ex.tiles_out) *ex.tiles_out = (int)(blocks / g.tiles_m);
+    if (ex.dry) return CPG_OK;
     if (stats != nullptr)
         hipLaunchKernelGGL((k_c3_fwd<Cfg, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, stats, bn, bb);
     else
@@ -1475,8 +1464,9 @@ int launch_fwd_s2(C3Geom g, const float *x, const float *wp, const float *bias, 
 inline int s2_out(int v) { return (v - 1) / 2 + 1; }
 
 int run_fwd_s2(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y, void *ws,
-               size_t ws_bytes, hipStream_t stream, float *stats, int *tiles_out, bool dry) {
+               size_t ws_bytes, hipStream_t stream, const C3Extra &ex) {
     const char *what = "cpg_conv2d_fwd(3x3 s2)";
+    const bool dry = ex.dry;
     const int OH = s2_out(d->H), OW = s2_out(d->W);
     float *wp = (float *)ws;
     const int rows_c = pad_to(d->C, 4), Mp = pad_to(d->K, 128);
@@ -1488,11 +1478,11 @@ int run_fwd_s2(const cpg_conv_desc *d, const float *x, const float *w, const flo
                            rows_c, Mp, 0, (int *)nullptr);
     }
     C3Geom g{d->N, d->C, d->H, d->W, d->K, Mp, 0, 0, 0, OH, OW, 0, 1};
-    if (OW == 28 && OH % 4 == 0 && d->K > 64) return launch_fwd_s2<S2P28>(g, x, wp, bias, y, stream, stats, tiles_out, dry, nullptr);
-    if (OW <= 8 && OH <= 8 && d->K > 64) return launch_fwd_s2<S2M8>(g, x, wp, bias, y, stream, stats, tiles_out, dry, nullptr);
-    if (OW <= 16 && OH <= 16 && d->K > 64) return launch_fwd_s2<S2S16>(g, x, wp, bias, y, stream, stats, tiles_out, dry, nullptr);
-    if (d->K <= 64) return launch_fwd_s2<S2G64>(g, x, wp, bias, y, stream, stats, tiles_out, dry, nullptr);
-    return launch_fwd_s2<S2G128>(g, x, wp, bias, y, stream, stats, tiles_out, dry, nullptr);
+    if (OW == 28 && OH % 4 == 0 && d->K > 64) return launch_fwd_s2<S2P28>(g, x, wp, bias, y, stream, ex);
+    if (OW <= 8 && OH <= 8 && d->K > 64) return launch_fwd_s2<S2M8>(g, x, wp, bias, y, stream, ex);
+    if (OW <= 16 && OH <= 16 && d->K > 64) return launch_fwd_s2<S2S16>(g, x, wp, bias, y, stream, ex);
+    if (d->K <= 64) return launch_fwd_s2<S2G64>(g, x, wp, bias, y, stream, ex);
+    return launch_fwd_s2<S2G128>(g, x, wp, bias, y, stream, ex);
 }
 
 //                  BM  WM WN TH TW NIMG
@@ -1527,15 +1517,13 @@ extern "C" int cpg_conv3x3s2_supported(const cpg_conv_desc *d) {
            (int64_t)d->C * d->H * d->W < (1ll << 27) && (int64_t)d->K * d->H * d->W < (1ll << 27) && (int64_t)d->H * d->W <= (1ll << 22);
 }
 size_t cpg_conv3x3s2_pack_workspace(const cpg_conv_desc *d) { return std::max(pack_bytes(d->C, d->K), pack_bytes(d->K, d->C)) + 16; }
-int cpg_conv3x3s2_bnstats_tiles(const cpg_conv_desc *d) {
-    int tiles = 0;
-    if (run_fwd_s2(d, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, 0, nullptr, nullptr, &tiles, true) != CPG_OK) return 0;
-    return tiles;
-}
+int cpg_conv3x3s2_bnstats_tiles(const cpg_conv_desc *d) { return dry_run_tiles(d, PROBE_FWD_S2); }
 int cpg_conv3x3s2_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y,
                       float *stats, void *ws, size_t ws_bytes, hipStream_t stream) {
     CPG_REQUIRE(x && w && y, "cpg_conv2d_fwd: null pointer");
-    return run_fwd_s2(d, x, w, pm, thr, bias, y, ws, ws_bytes, stream, stats, nullptr, false);
+    C3Extra ex;
+    ex.stats = stats;
+    return run_fwd_s2(d, x, w, pm, thr, bias, y, ws, ws_bytes, stream, ex);
 }
 int cpg_conv3x3s2_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                         size_t ws_bytes, hipStream_t stream) {

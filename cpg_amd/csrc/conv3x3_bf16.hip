@@ -23,7 +23,7 @@
 //   Work per staged byte is 16x lower than in the fp32 kernel, so this kernel is bound by L2 / HBM delivery of the patch
 //   and the packed weights on most VGG layers, not by the matrix pipe (docs/LAB_NOTEBOOK.md section 4.6 has the measurements).
 #include <algorithm>
-#include "igemm_core.h"
+#include "cpg_dispatch.h"
 
 using namespace cpg;
 
@@ -595,8 +595,6 @@ int wlaunch(const cpg_conv_desc *d, const float *x, const float *gy, const Epilo
 }
 
 }  // namespace
-
-extern "C" int cpg_conv3x3_supported(const cpg_conv_desc *d);
 
 // (fewer than 16 channels on either side -- the 3 -> 64 stem -- would fill most of a 16-channel k-step with zeros and is
 // HBM-bound anyway: it stays on the fp32 kernels)

@@ -30,7 +30,7 @@
 // the last bit wherever the summation order is the same.
 #include <algorithm>
 #include <type_traits>
-#include "igemm_core.h"
+#include "cpg_dispatch.h"
 
 using namespace cpg;
 

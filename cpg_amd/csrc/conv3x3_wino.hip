@@ -36,7 +36,7 @@
 //   dgrad       the same kernel on gy with the filter transposed and spatially flipped (k_wg_pack's dgrad flavour).
 #include <algorithm>
 #include <type_traits>
-#include "igemm_core.h"
+#include "cpg_dispatch.h"
 
 using namespace cpg;
 
@@ -2180,6 +2180,53 @@ extern "C" int cpg_conv3x3_wino_tiles(int N, int c_read, int m, int H, int W) {
     return (int)((tiles + per - 1) / per);
 }
 
+// What a launch of the one- and two-wave kernels computes.  Each kernel family has ONE function that maps a mode to the template
+// instance; an instance that does not exist cannot be named, and a mode a family lacks is a status, not a launch.
+enum WgMode {
+    WG_FWD,           // y = conv(x) (+ bias)
+    WG_FWD_STATS,     // ... + the BatchNorm partial sums of y
+    WG_FWD_BNE,       // ... + eval-mode BatchNorm (+ ReLU), dead-channel skip: the inference epilogue
+    WG_DGRAD,         // gx = dgrad(gy)
+    WG_DGRAD_ADD      // ... + addend (rides in the bias slot)
+};
+struct WgLaunch {     // the arguments every instance takes
+    const WgGeom &g;
+    const float *x, *up, *bias;      // bias: the addend under WG_DGRAD_ADD
+    float *y, *stats;                // stats: passed under WG_FWD_STATS only
+    const WgBnEval &bne;             // read under WG_FWD_BNE only
+    hipStream_t stream;
+};
+#define WG_GO(kernel, blocks, threads, a, stats_arg) \
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, (a).stream, (a).g, (a).x, (a).up, (a).bias, (a).y, stats_arg, (a).bne)
+
+// k_wg3<DGRAD, STATS, BNE, ODD, SH, SPLIT, ADD>: 18 instances.  ODD (odd maps) and SH (two units per four-wave block) exclude each
+// other; SPLIT (a tail piece: raw partial output) exists for the plain forward and input gradient of even maps; SH has no BNE.
+template <bool ODD, bool SH, bool SPLIT>
+static int wg3_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
+    static_assert(!(ODD && (SH || SPLIT)), "k_wg3: the odd-map instances neither share the transform nor split the channel loop");
+    constexpr int threads = SH ? 256 : 128;
+    if constexpr (!SH && !SPLIT) {
+        if (mode == WG_FWD_BNE) { WG_GO((k_wg3<false, false, true, ODD>), blocks, threads, a, nullptr); return CPG_OK; }
+    }
+    if constexpr (!SPLIT) {
+        if (mode == WG_DGRAD_ADD) { WG_GO((k_wg3<true, false, false, ODD, SH, false, true>), blocks, threads, a, nullptr); return CPG_OK; }
+    }
+    if (mode == WG_DGRAD) { WG_GO((k_wg3<true, false, false, ODD, SH, SPLIT>), blocks, threads, a, nullptr); return CPG_OK; }
+    if constexpr (!SPLIT) {
+        if (mode == WG_FWD_STATS) { WG_GO((k_wg3<false, true, false, ODD, SH>), blocks, threads, a, a.stats); return CPG_OK; }
+    }
+    if (mode == WG_FWD) { WG_GO((k_wg3<false, false, false, ODD, SH, SPLIT>), blocks, threads, a, nullptr); return CPG_OK; }
+    return fail(CPG_E_UNSUPPORTED, "conv3x3 (winograd): k_wg3 has no instance for mode %d (odd %d, shared %d, split %d)", (int)mode, ODD, SH, SPLIT);
+}
+// k_wg2<DGRAD, STATS, BNE> and k_wg1<DGRAD, STATS, BNE>: 4 instances each, no addend
+static int wg2_launch(WgMode mode, unsigned blocks, const WgLaunch &a);
+static int wg1_launch(WgMode mode, unsigned blocks, const WgLaunch &a);
+// the cooperative block kernel k_wg_fwd (CPG_WINO_KERNEL=block only): packs for itself, no inference epilogue
+static int wino_run_block(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
+                          float thr, const float *bias, float *y, float *stats, void *ws, hipStream_t stream, const char *what);
+// (These three are defined below wino_run, in the order wino_run reaches them: the compiler emits kernels in the order of their first
+// reference, and host-side edits keep this file's device code byte-identical -- tools/build_digest.py.)
+
 // y[N][m][H][W] = conv3x3(x[N][c_read][H][W], W .* bin(pm)) (+ bias); dgrad: x = gy, the filter transposed and flipped.
 // w is the layer's [K][C][3][3] weight.  stats (forward only, may be null): [m][tiles][2] partial sums for the BatchNorm.
 static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
@@ -2255,22 +2302,16 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
                                K, C, m, c_read, g.nch, dgrad ? 1 : 0, bne ? bne->live : nullptr, bne ? bne->Mp : 0);
         const int64_t runs = (g.tiles_total + W1_T - 1) / W1_T;
         const bool persist = wino_persist();
+        const WgMode mode = bne != nullptr ? WG_FWD_BNE : dgrad ? (addend != nullptr ? WG_DGRAD_ADD : WG_DGRAD) : stats != nullptr ? WG_FWD_STATS : WG_FWD;
+        const WgLaunch whole{g, x, up, mode == WG_DGRAD_ADD ? addend : bias, y, stats, bne != nullptr ? *bne : none, stream};
+        int rc;
         if (variant == WV_PAIR64) {
             int64_t blocks = runs * ((g.nkb + 1) / 2);
             if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "%s: grid too large", what);
             g.nblocks = (unsigned)blocks;
             if (persist) blocks = std::min<int64_t>(blocks, (int64_t)wino_grids() * 2 * kCUs);
             if (odd) {
-                if (bne != nullptr)
-                    hipLaunchKernelGGL((k_wg3<false, false, true, true>), dim3((unsigned)blocks), dim3(128), 0, stream, g, x, up, bias, y, nullptr, *bne);
-                else if (dgrad && addend != nullptr)
-                    hipLaunchKernelGGL((k_wg3<true, false, false, true, false, false, true>), dim3((unsigned)blocks), dim3(128), 0, stream, g, x, up, addend, y, nullptr, none);
-                else if (dgrad)
-                    hipLaunchKernelGGL((k_wg3<true, false, false, true>), dim3((unsigned)blocks), dim3(128), 0, stream, g, x, up, bias, y, nullptr, none);
-                else if (stats != nullptr)
-                    hipLaunchKernelGGL((k_wg3<false, true, false, true>), dim3((unsigned)blocks), dim3(128), 0, stream, g, x, up, bias, y, stats, none);
-                else
-                    hipLaunchKernelGGL((k_wg3<false, false, false, true>), dim3((unsigned)blocks), dim3(128), 0, stream, g, x, up, bias, y, nullptr, none);
+                if ((rc = wg3_launch<true, false, false>(mode, (unsigned)blocks, whole)) != CPG_OK) return rc;
                 CPG_CHECK_LAUNCH(what);
                 return CPG_OK;
             }
@@ -2297,46 +2338,24 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
                 else
                     hipLaunchKernelGGL(k_wg_tail_reduce<false>, rg, dim3(256), 0, stream, gt, part0, bias, y, tail.first_lb, tail.end_lb, (float *)nullptr, addend);
             };
+            const WgLaunch pieces{gt, x, up, nullptr, part0, nullptr, none, stream};      // (the tail: raw partial outputs, forward or input gradient)
+            const unsigned tb = (unsigned)(tail.left * tail.S);
             // two units per block sharing the input transform (k_wg3<..., SH>): training launches whose 64-channel blocks pair up
             if (sh) {
                 int64_t pairs = (int64_t)g.nblocks / 2;
                 if (persist) pairs = std::min<int64_t>(pairs, (int64_t)wino_grids() * kCUs);       // (one four-wave block per CU is resident)
-                if (dgrad && addend != nullptr)
-                    hipLaunchKernelGGL((k_wg3<true, false, false, false, true, false, true>), dim3((unsigned)pairs), dim3(256), 0, stream, g, x, up, addend, y, nullptr, none);
-                else if (dgrad)
-                    hipLaunchKernelGGL((k_wg3<true, false, false, false, true>), dim3((unsigned)pairs), dim3(256), 0, stream, g, x, up, bias, y, nullptr, none);
-                else if (stats != nullptr)
-                    hipLaunchKernelGGL((k_wg3<false, true, false, false, true>), dim3((unsigned)pairs), dim3(256), 0, stream, g, x, up, bias, y, stats, none);
-                else
-                    hipLaunchKernelGGL((k_wg3<false, false, false, false, true>), dim3((unsigned)pairs), dim3(256), 0, stream, g, x, up, bias, y, nullptr, none);
+                if ((rc = wg3_launch<false, true, false>(mode, (unsigned)pairs, whole)) != CPG_OK) return rc;
                 if (tail.on) {
-                    const unsigned tb = (unsigned)(tail.left * tail.S);
-                    if (dgrad)
-                        hipLaunchKernelGGL((k_wg3<true, false, false, false, true, true>), dim3(tb), dim3(256), 0, stream, gt, x, up, nullptr, part0, nullptr, none);
-                    else
-                        hipLaunchKernelGGL((k_wg3<false, false, false, false, true, true>), dim3(tb), dim3(256), 0, stream, gt, x, up, nullptr, part0, nullptr, none);
+                    if ((rc = wg3_launch<false, true, true>(dgrad ? WG_DGRAD : WG_FWD, tb, pieces)) != CPG_OK) return rc;
                     finish_tail();
                 }
                 CPG_CHECK_LAUNCH(what);
                 return CPG_OK;
             }
             if (tail.on) blocks = std::min<int64_t>(blocks, (int64_t)g.nblocks);
-            if (bne != nullptr)
-                hipLaunchKernelGGL((k_wg3<false, false, true>), dim3((unsigned)blocks), dim3(128), 0, stream, g, x, up, bias, y, nullptr, *bne);
-            else if (dgrad && addend != nullptr)
-                hipLaunchKernelGGL((k_wg3<true, false, false, false, false, false, true>), dim3((unsigned)blocks), dim3(128), 0, stream, g, x, up, addend, y, nullptr, none);
-            else if (dgrad)
-                hipLaunchKernelGGL((k_wg3<true, false>), dim3((unsigned)blocks), dim3(128), 0, stream, g, x, up, bias, y, nullptr, none);
-            else if (stats != nullptr)
-                hipLaunchKernelGGL((k_wg3<false, true>), dim3((unsigned)blocks), dim3(128), 0, stream, g, x, up, bias, y, stats, none);
-            else
-                hipLaunchKernelGGL((k_wg3<false, false>), dim3((unsigned)blocks), dim3(128), 0, stream, g, x, up, bias, y, nullptr, none);
+            if ((rc = wg3_launch<false, false, false>(mode, (unsigned)blocks, whole)) != CPG_OK) return rc;
             if (tail.on) {
-                const unsigned tb = (unsigned)(tail.left * tail.S);
-                if (dgrad)
-                    hipLaunchKernelGGL((k_wg3<true, false, false, false, false, true>), dim3(tb), dim3(128), 0, stream, gt, x, up, nullptr, part0, nullptr, none);
-                else
-                    hipLaunchKernelGGL((k_wg3<false, false, false, false, false, true>), dim3(tb), dim3(128), 0, stream, gt, x, up, nullptr, part0, nullptr, none);
+                if ((rc = wg3_launch<false, false, true>(dgrad ? WG_DGRAD : WG_FWD, tb, pieces)) != CPG_OK) return rc;
                 finish_tail();
             }
             CPG_CHECK_LAUNCH(what);
@@ -2345,14 +2364,7 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
         if (variant == WV_PAIR) {
             const int64_t blocks = runs * g.nkb;
             if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "%s: grid too large", what);
-            if (bne != nullptr)
-                hipLaunchKernelGGL((k_wg2<false, false, true>), dim3((unsigned)blocks), dim3(128), 0, stream, g, x, up, bias, y, nullptr, *bne);
-            else if (dgrad)
-                hipLaunchKernelGGL((k_wg2<true, false>), dim3((unsigned)blocks), dim3(128), 0, stream, g, x, up, bias, y, nullptr, none);
-            else if (stats != nullptr)
-                hipLaunchKernelGGL((k_wg2<false, true>), dim3((unsigned)blocks), dim3(128), 0, stream, g, x, up, bias, y, stats, none);
-            else
-                hipLaunchKernelGGL((k_wg2<false, false>), dim3((unsigned)blocks), dim3(128), 0, stream, g, x, up, bias, y, nullptr, none);
+            if ((rc = wg2_launch(mode, (unsigned)blocks, whole)) != CPG_OK) return rc;
             CPG_CHECK_LAUNCH(what);
             return CPG_OK;
         }
@@ -2360,18 +2372,36 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
         if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "%s: grid too large", what);
         g.nblocks = (unsigned)blocks;
         if (persist) blocks = std::min<int64_t>(blocks, (int64_t)wino_grids() * kCUs);
-        if (bne != nullptr)
-            hipLaunchKernelGGL((k_wg1<false, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, up, bias, y, nullptr, *bne);
-        else if (dgrad)
-            hipLaunchKernelGGL((k_wg1<true, false>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, up, bias, y, nullptr, none);
-        else if (stats != nullptr)
-            hipLaunchKernelGGL((k_wg1<false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, up, bias, y, stats, none);
-        else
-            hipLaunchKernelGGL((k_wg1<false, false>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, up, bias, y, nullptr, none);
+        if ((rc = wg1_launch(mode, (unsigned)blocks, whole)) != CPG_OK) return rc;
         CPG_CHECK_LAUNCH(what);
         return CPG_OK;
     }
     if (bne != nullptr) return fail(CPG_E_UNSUPPORTED, "%s: the block kernels have no inference epilogue", what);
+    return wino_run_block(dgrad, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, stats, ws, stream, what);
+}
+
+static int wg2_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
+    switch (mode) {
+        case WG_FWD_BNE: WG_GO((k_wg2<false, false, true>), blocks, 128, a, nullptr); return CPG_OK;
+        case WG_DGRAD: WG_GO((k_wg2<true, false>), blocks, 128, a, nullptr); return CPG_OK;
+        case WG_FWD_STATS: WG_GO((k_wg2<false, true>), blocks, 128, a, a.stats); return CPG_OK;
+        case WG_FWD: WG_GO((k_wg2<false, false>), blocks, 128, a, nullptr); return CPG_OK;
+        default: return fail(CPG_E_UNSUPPORTED, "conv3x3 (winograd): k_wg2 takes no addend");
+    }
+}
+static int wg1_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
+    switch (mode) {
+        case WG_FWD_BNE: WG_GO((k_wg1<false, false, true>), blocks, 256, a, nullptr); return CPG_OK;
+        case WG_DGRAD: WG_GO((k_wg1<true, false>), blocks, 256, a, nullptr); return CPG_OK;
+        case WG_FWD_STATS: WG_GO((k_wg1<false, true>), blocks, 256, a, a.stats); return CPG_OK;
+        case WG_FWD: WG_GO((k_wg1<false, false>), blocks, 256, a, nullptr); return CPG_OK;
+        default: return fail(CPG_E_UNSUPPORTED, "conv3x3 (winograd): k_wg1 takes no addend");
+    }
+}
+#undef WG_GO
+
+static int wino_run_block(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
+                          float thr, const float *bias, float *y, float *stats, void *ws, hipStream_t stream, const char *what) {
     if (cpg::pack_query()) return CPG_OK;        // (the block kernels pack for themselves: no job recorded)
     const int nw = wino_nw(c_read, m), BK = 8 * nw;
     WgGeom g;

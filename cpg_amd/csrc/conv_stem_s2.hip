@@ -21,7 +21,7 @@
 // k_split_reduce (with the autograd epilogue gW = g bin(pm), gPM = g W).
 #include <algorithm>
 #include <type_traits>
-#include "igemm_core.h"
+#include "cpg_dispatch.h"
 
 using namespace cpg;
 

@@ -1,0 +1,148 @@
+// Every function of libcpg_hip.so that one translation unit defines and another calls, declared ONCE (the C ABI itself is
+// include/cpg_hip.h).  The defining file includes this header too, so a definition that drifts from its declaration is a compile
+// error (extern "C") or a link error (mangled) instead of a call with its arguments in the wrong slots.  Default arguments live here only.
+// The extern "C" helpers are reachable in a CPG_EXPORT_ALL=1 build (tools/wino_bench.py, tools/wino_wgrad_bench.py); the normal
+// build exports none of them.  Only the conv / linear translation units include this header: it pulls in igemm_core.h's kernels.
+#pragma once
+#include "igemm_core.h"
+
+// ---- conv3x3.hip: 3x3 / stride 1 / pad 1 -----------------------------------------------------------------------------------------------
+// 1: the specialised 3x3 kernels take this shape (CPG_DISABLE_CONV3X3: never)
+extern "C" int cpg_conv3x3_supported(const cpg_conv_desc *d);
+// workspace of the forward / input gradient: packed weights of either direction + the Winograd filter + its tail pieces
+size_t cpg_conv3x3_pack_workspace(const cpg_conv_desc *d);
+int cpg_conv3x3_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                    float *y, void *ws, size_t ws_bytes, hipStream_t stream);
+// forward that also writes stats[K][tiles][2], the per-(channel, pixel tile) BatchNorm partial sums; tiles = 0: not available
+int cpg_conv3x3_bnstats_tiles(const cpg_conv_desc *d);
+int cpg_conv3x3_fwd_bnstats(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                            float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream);
+// forward with the inference-mode BatchNorm (+ ReLU) folded into the epilogue; skip_stats (may be null): 2 device words
+int cpg_conv3x3_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                            const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu, float *y,
+                            int32_t *skip_stats, void *ws, size_t ws_bytes, hipStream_t stream);
+int cpg_conv3x3_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
+                      size_t ws_bytes, hipStream_t stream);
+// input gradient whose epilogue also does the BatchNorm-backward reduction of the layer below; tiles = 0: this shape has no such path
+int cpg_conv3x3_dgrad_bnbwd_tiles(const cpg_conv_desc *d);
+int cpg_conv3x3_dgrad_bnbwd(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, const float *ypre,
+                            const float *gamma, const float *beta, const float *mean, const float *invstd, float *gx, float *partials,
+                            void *ws, size_t ws_bytes, hipStream_t stream);
+// weight gradient: Winograd, the <= 3-channel stem kernel or k_c3_wgrad's 64-wide input-channel tile (4..15 channels: the generic kernel)
+size_t cpg_conv3x3_wgrad_workspace(const cpg_conv_desc *d);
+int cpg_conv3x3_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr,
+                      float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
+
+// ---- conv3x3.hip: 3x3 / stride 2 / pad 1, >= 16 channels on both sides (k_c3_fwd's strided tiles, k_c3s2_dgrad, k_c3_wgrad's strided units) ----
+// 1: ... take this shape (CPG_DISABLE_CONV3X3, CPG_NO_S2: never)
+extern "C" int cpg_conv3x3s2_supported(const cpg_conv_desc *d);
+size_t cpg_conv3x3s2_pack_workspace(const cpg_conv_desc *d);
+int cpg_conv3x3s2_bnstats_tiles(const cpg_conv_desc *d);
+// stats (may be null): [K][tiles][2] BatchNorm partial sums
+int cpg_conv3x3s2_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y,
+                      float *stats, void *ws, size_t ws_bytes, hipStream_t stream);
+int cpg_conv3x3s2_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
+                        size_t ws_bytes, hipStream_t stream);
+size_t cpg_conv3x3s2_wgrad_workspace(const cpg_conv_desc *d);
+int cpg_conv3x3s2_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr, float *gw,
+                        float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
+
+// ---- conv3x3_wino.hip: Winograd F(2x2, 3x3) forward / input gradient.  c_read / m: channels contracted over / produced ----------------------
+// eligibility of one launch (CPG_NO_WINO: never; odd maps: the two-wave kernel's ODD instances only)
+extern "C" int cpg_conv3x3_wino_ok(int N, int c_read, int m, int H, int W);
+// bytes of the transformed filter at the head of the workspace
+extern "C" size_t cpg_conv3x3_wino_pack_bytes(int c_read, int m);
+// workspace behind the packed filter for the partial outputs of a tail launch (0: this launch has none)
+extern "C" size_t cpg_conv3x3_wino_tail_bytes(int N, int c_read, int m, int H, int W);
+// BatchNorm-statistics tiles per channel of a forward launch (stats[m][tiles][2])
+extern "C" int cpg_conv3x3_wino_tiles(int N, int c_read, int m, int H, int W);
+// y[N][m][H][W] = conv3x3(x[N][c_read][H][W], W .* bin(pm)) (+ bias); dgrad: x = gy, the filter transposed and flipped.
+// w is the layer's [K][C][3][3] weight.  stats (forward only, may be null): [m][tiles][2]
+extern "C" int cpg_conv3x3_wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w,
+                                    const float *pm, float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes,
+                                    hipStream_t stream);
+// 1: the inference epilogue is available on the Winograd kernels (not on the cooperative block kernel)
+extern "C" int cpg_conv3x3_wino_eval_ok(int N, int c_read, int m, int H, int W);
+// forward with eval-mode BatchNorm (+ ReLU) in the epilogue; live (may be null): live_words ints, zeroed here, layout of k_c3_pack
+extern "C" int cpg_conv3x3_wino_run_bn_eval(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr,
+                                            const float *bias, const float *gamma, const float *beta, const float *mean, const float *var,
+                                            float eps, int relu, int *live, size_t live_words, float *y, void *ws, size_t ws_bytes,
+                                            hipStream_t stream);
+// input gradient + addend (gx = dgrad(gy) + addend): the two-wave kernel's launches (>= 64 channels on both sides, or an odd map)
+extern "C" int cpg_conv3x3_wino_dgrad_add_ok(int N, int c_read, int m, int H, int W);
+extern "C" int cpg_conv3x3_wino_dgrad_add(int N, int c_read, int m, int H, int W, int K, int C, const float *gy, const float *w, const float *pm,
+                                          float thr, const float *addend, float *gx, void *ws, size_t ws_bytes, hipStream_t stream);
+
+// ---- conv3x3_wino_wgrad.hip: Winograd F(2x2, 3x3) weight gradient (maps 14 or a multiple of 28 wide, channel counts multiples of 32) -------
+extern "C" int cpg_conv3x3_wino_wgrad_ok(const cpg_conv_desc *d);
+// 1: cpg_conv2d_wgrad of this shape takes a rider (cpg_conv2d_wgrad_attach_bn_bwd)
+extern "C" int cpg_conv3x3_wino_wgrad_rider_ok(const cpg_conv_desc *d);
+extern "C" size_t cpg_conv3x3_wino_wgrad_workspace(const cpg_conv_desc *d);
+extern "C" int cpg_conv3x3_wino_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr,
+                                      float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
+
+// ---- conv3x3_stem.hip: the <= 3-channel 3x3 s1 p1 stem (one persistent wave per tile, weights in registers, HBM-bound) ---------------------
+// 1: cpg_conv2d_fwd / cpg_conv2d_fwd_bnstats run this layer on the stem kernel (CPG_NO_STEM: never)
+extern "C" int cpg_conv3x3_stem_ok(int N, int C, int K, int H, int W);
+// BatchNorm-statistics tiles per channel (stats[K][tiles][2])
+extern "C" int cpg_conv3x3_stem_tiles(int N, int C, int K, int H, int W);
+extern "C" int cpg_conv3x3_stem_run(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr,
+                                    const float *bias, float *y, float *stats, hipStream_t stream);
+
+// ---- conv_stem_s2.hip: the strided image stems (7x7 s2 p3 and 3x3 s2 p1 from <= 3 channels to 64) -----------------------------------------
+// 1: cpg_conv2d_fwd / cpg_conv2d_fwd_bnstats / cpg_conv2d_wgrad run this layer on the strided stem kernels (CPG_NO_STEM: never)
+extern "C" int cpg_conv_stem2_ok(const cpg_conv_desc *d);
+int cpg_conv_stem2_tiles(const cpg_conv_desc *d);
+// stats (may be null): [K][tiles][2] BatchNorm partial sums
+int cpg_conv_stem2_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y,
+                       float *stats, hipStream_t stream);
+size_t cpg_conv_stem2_wgrad_workspace(const cpg_conv_desc *d);
+int cpg_conv_stem2_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr, float *gw,
+                         float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
+
+// ---- pointwise.hip: 1x1 convolutions ----------------------------------------------------------------------------------------------------
+// 1: the pointwise kernels take this shape's forward and input gradient (CPG_DISABLE_CONV1X1: never)
+extern "C" int cpg_conv1x1_supported(const cpg_conv_desc *d);
+size_t cpg_conv1x1_pack_workspace(const cpg_conv_desc *d);
+// stats (may be null): [K][tiles][2] BatchNorm partial sums, tiles = cpg_conv1x1_bnstats_tiles(d)
+int cpg_conv1x1_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                    float *y, void *ws, size_t ws_bytes, hipStream_t stream, float *stats = nullptr);
+int cpg_conv1x1_bnstats_tiles(const cpg_conv_desc *d);
+// addend (may be null; stride 1 only): gx = dgrad(gy) + addend
+int cpg_conv1x1_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
+                      size_t ws_bytes, hipStream_t stream, const float *addend = nullptr);
+// dense pointwise layers whose activations can be staged as aligned float4 and addressed with 31-bit byte offsets
+extern "C" int cpg_conv1x1_wgrad_supported(const cpg_conv_desc *d);
+size_t cpg_conv1x1_wgrad_workspace(const cpg_conv_desc *d);
+int cpg_conv1x1_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr,
+                      float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
+
+// ---- pointwise.hip: the same kernels as plain GEMMs (the linear layers) -------------------------------------------------------------------
+// D[M][C] = A[M][K] . B[C][K]^T, both operands row-major and 16-byte aligned
+bool cpg_pw_gemm_nt_ok(const float *A, const float *B, int M, int C, int64_t K);
+size_t cpg_pw_gemm_nt_workspace(int M, int C, int64_t K);
+int cpg_pw_gemm_nt(const float *A, const float *B, int M, int C, int64_t K, const cpg::Epilogue &ep, void *ws, size_t ws_bytes,
+                   hipStream_t stream, const char *what);
+// the same product with B masked in staging: D[M][C] = A[M][K] . (B * bin(pmB))[C][K]^T
+int cpg_pw_gemm_nt_maskb(const float *A, const float *B, const float *pmB, float thr, int M, int C, int64_t K, const cpg::Epilogue &ep, void *ws,
+                         size_t ws_bytes, hipStream_t stream, const char *what);
+// masked: the launch that follows is cpg_pw_gemm_nn_masked / _maskx (their pixel tile differs)
+bool cpg_pw_gemm_nn_ok(const float *X, int M, int Mp, int Kd, int64_t G, bool masked = false);
+// y[M][G] (+ bias[m]) from K-major Wp (row stride Mp >= M, a multiple of 128; rows beyond Kd are never read)
+int cpg_pw_gemm_nn(const float *wp, int Mp, const float *X, int M, int Kd, int64_t G, const float *bias, float *y, hipStream_t stream,
+                   const char *what);
+// the same GEMM with the autograd epilogue of bin(pm) * W: gw[M][G] = D * bin(pm), gpm[M][G] = D * w (pm, w, gpm laid out like gw)
+int cpg_pw_gemm_nn_masked(const float *wp, int Mp, const float *X, int M, int Kd, int64_t G, const float *pm, const float *w, float thr,
+                          float *gw, float *gpm, hipStream_t stream, const char *what);
+// ... and with the operand X * bin(pmX) formed in staging
+int cpg_pw_gemm_nn_maskx(const float *wp, int Mp, const float *X, const float *pmX, float thr, int M, int Kd, int64_t G, float *y,
+                         hipStream_t stream, const char *what);
+// K-major transpose of a row-major [R][Cc] matrix into wp[Cc (padded to 16)][R (padded to 128)]
+void cpg_pw_pack_transpose(const float *a, int R, int Cc, float *wp, hipStream_t stream);
+size_t cpg_pw_pack_transpose_bytes(int R, int Cc);
+
+// ---- fc_small.hip: the weight-streaming input gradient of linear layers at <= 64 rows ------------------------------------------------------
+bool cpg_fc_small_dgrad_ok(const float *w, const float *pm, const float *gx, int batch, int in_f, int out_f);
+size_t cpg_fc_small_dgrad_workspace(int batch, int in_f, int out_f);
+int cpg_fc_small_dgrad(const float *gy, const float *w, const float *pm, float thr, float *gx, int batch, int in_f, int out_f, void *ws,
+                       size_t ws_bytes, hipStream_t stream, const char *what);

@@ -17,7 +17,7 @@
 //     tiles alone do not fill the chip, combined by k_split_reduce in a fixed order (deterministic for a given shape).
 // MFMA issue would sustain 16 B / clk / CU (9.8 TB/s) at 32 rows, 4.9 TB/s at 64 rows: above 64 rows the GEMM kernels take over.
 #include <algorithm>
-#include "igemm_core.h"
+#include "cpg_dispatch.h"
 
 using namespace cpg;
 

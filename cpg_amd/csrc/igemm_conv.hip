@@ -10,8 +10,7 @@
 //   fwd  : D[co][p]        = sum_{ci,r,s} Weff[co][ci][r][s] * x[n_p][ci][ih][iw]
 //   dgrad: D[ci][q]        = sum_{co,r,s} Weff[co][ci][r][s] * gy[n_q][co][oh][ow]
 //   wgrad: D[co][(ci,r,s)] = sum_{p}      gy[n_p][co][p]      * x[n_p][ci][ih][iw]     (split-K over p)
-#include <algorithm>
-#include "igemm_core.h"
+#include "cpg_dispatch.h"
 
 using namespace cpg;
 
@@ -508,75 +507,59 @@ void conv_wgrad_tiles(const ConvGeom &g, int &tiles_m, int &tiles_n) {
 
 }  // namespace
 
-// The specialised 3x3 kernels (conv3x3.hip) take over when they support the shape.
-extern "C" int cpg_conv3x3_supported(const cpg_conv_desc *d);
-int cpg_conv3x3_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                    float *y, void *ws, size_t ws_bytes, hipStream_t stream);
-int cpg_conv3x3_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
-                      size_t ws_bytes, hipStream_t stream);
-size_t cpg_conv3x3_pack_workspace(const cpg_conv_desc *d);
-size_t cpg_conv3x3_wgrad_workspace(const cpg_conv_desc *d);
-int cpg_conv3x3_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr,
-                      float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
+// ---------------------------------------------------------------------------------- dispatch
+// The shape classes with kernels of their own; everything else runs the generic implicit-GEMM kernels of this file.
+// The classes are mutually exclusive, so the order in which a route tests them decides nothing:
+//   - 3x3 s1 p1 (conv3x3.hip, conv3x3_wino*.hip), 1x1 (pointwise.hip) and the two stride-2 classes differ in kernel size or stride;
+//   - of the stride-2 classes, 3x3 s2 p1 (conv3x3.hip) needs >= 16 channels on both sides, the image stems (conv_stem_s2.hip:
+//     7x7 s2 p3, 3x3 s2 p1) need <= 3 input channels.
+// (wgrad_route tests the stems before 3x3 s2, fwd_route after it, as the entry points always did.)
+enum ConvRoute { ROUTE_C3, ROUTE_C1, ROUTE_C3S2, ROUTE_STEM2, ROUTE_GENERIC };
+
 // the 3x3 weight-gradient kernel owns a 64-wide input-channel tile; <= 3 channels (the VGG stem) have their own
 // HBM-streaming kernel, 4..15 channels go to the generic kernel whose (ci, tap) column packing wastes less MFMA
-int cpg_conv3x3_bnstats_tiles(const cpg_conv_desc *d);
-int cpg_conv3x3_fwd_bnstats(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                            float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream);
-int cpg_conv3x3_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                            const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu, float *y,
-                            int32_t *skip_stats, void *ws, size_t ws_bytes, hipStream_t stream);
-int cpg_conv3x3_dgrad_bnbwd_tiles(const cpg_conv_desc *d);
-int cpg_conv3x3_dgrad_bnbwd(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, const float *ypre,
-                            const float *gamma, const float *beta, const float *mean, const float *invstd, float *gx, float *partials,
-                            void *ws, size_t ws_bytes, hipStream_t stream);
-// ... and the pointwise kernels (pointwise.hip) for 1x1 convolutions (forward and input gradient)
-extern "C" int cpg_conv1x1_supported(const cpg_conv_desc *d);
-size_t cpg_conv1x1_pack_workspace(const cpg_conv_desc *d);
-int cpg_conv1x1_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                    float *y, void *ws, size_t ws_bytes, hipStream_t stream, float *stats = nullptr);
-int cpg_conv1x1_bnstats_tiles(const cpg_conv_desc *d);
-int cpg_conv1x1_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
-                      size_t ws_bytes, hipStream_t stream, const float *addend = nullptr);
-extern "C" int cpg_conv1x1_wgrad_supported(const cpg_conv_desc *d);
-size_t cpg_conv1x1_wgrad_workspace(const cpg_conv_desc *d);
-int cpg_conv1x1_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr,
-                      float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
-// ... the 3x3 / stride 2 / pad 1 class (conv3x3.hip: k_c3_fwd's strided tiles, k_c3s2_dgrad, k_c3_wgrad's strided units)
-extern "C" int cpg_conv3x3s2_supported(const cpg_conv_desc *d);
-size_t cpg_conv3x3s2_pack_workspace(const cpg_conv_desc *d);
-int cpg_conv3x3s2_bnstats_tiles(const cpg_conv_desc *d);
-int cpg_conv3x3s2_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y,
-                      float *stats, void *ws, size_t ws_bytes, hipStream_t stream);
-int cpg_conv3x3s2_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
-                        size_t ws_bytes, hipStream_t stream);
-size_t cpg_conv3x3s2_wgrad_workspace(const cpg_conv_desc *d);
-int cpg_conv3x3s2_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr, float *gw,
-                        float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
-// ... and the strided image stems (conv_stem_s2.hip: 7x7 s2 p3 and 3x3 s2 p1 from <= 3 channels to 64)
-extern "C" int cpg_conv_stem2_ok(const cpg_conv_desc *d);
-int cpg_conv_stem2_tiles(const cpg_conv_desc *d);
-int cpg_conv_stem2_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y,
-                       float *stats, hipStream_t stream);
-size_t cpg_conv_stem2_wgrad_workspace(const cpg_conv_desc *d);
-int cpg_conv_stem2_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr, float *gw,
-                         float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
 static inline bool use_c3_wgrad(const cpg_conv_desc *d) { return cpg_conv3x3_supported(d) && (d->C >= 16 || d->C <= 3); }
+
+// forward and input gradient (the stems have no input gradient of their own: cpg_conv2d_dgrad sends ROUTE_STEM2 to the generic kernel)
+static ConvRoute fwd_route(const cpg_conv_desc *d) {
+    if (d == nullptr) return ROUTE_GENERIC;              // (the generic entry point reports it)
+    if (cpg_conv3x3_supported(d)) return ROUTE_C3;
+    if (cpg_conv1x1_supported(d)) return ROUTE_C1;
+    if (cpg_conv3x3s2_supported(d)) return ROUTE_C3S2;
+    if (cpg_conv_stem2_ok(d)) return ROUTE_STEM2;
+    return ROUTE_GENERIC;
+}
+// weight gradient (d != nullptr)
+static ConvRoute wgrad_route(const cpg_conv_desc *d) {
+    if (use_c3_wgrad(d)) return ROUTE_C3;
+    if (cpg_conv_stem2_ok(d)) return ROUTE_STEM2;
+    if (cpg_conv3x3s2_supported(d)) return ROUTE_C3S2;
+    if (cpg_conv1x1_wgrad_supported(d)) return ROUTE_C1;
+    return ROUTE_GENERIC;
+}
 
 extern "C" size_t cpg_conv2d_workspace_bytes(const cpg_conv_desc *d) {
     ConvGeom g;
     if (make_geom(d, g) != CPG_OK) return 0;
-    size_t pack = cpg_conv3x3_supported(d) ? cpg_conv3x3_pack_workspace(d) : cpg_conv1x1_supported(d) ? cpg_conv1x1_pack_workspace(d) : 0;
-    pack = std::max(pack, bias_ws_bytes(g.N, g.K));          // the bias gradient's partial sums reuse the workspace
-    if (use_c3_wgrad(d)) return std::max(pack, cpg_conv3x3_wgrad_workspace(d));
-    if (cpg_conv3x3s2_supported(d)) return std::max(std::max(pack, cpg_conv3x3s2_pack_workspace(d)), cpg_conv3x3s2_wgrad_workspace(d));
-    if (cpg_conv_stem2_ok(d)) return std::max(pack, cpg_conv_stem2_wgrad_workspace(d));
-    if (cpg_conv1x1_wgrad_supported(d)) return std::max(pack, cpg_conv1x1_wgrad_workspace(d));
+    size_t need = bias_ws_bytes(g.N, g.K);                   // the bias gradient's partial sums reuse the workspace
+    switch (fwd_route(d)) {                                  // the packed operands of the forward and the input gradient
+        case ROUTE_C3: need = std::max(need, cpg_conv3x3_pack_workspace(d)); break;
+        case ROUTE_C1: need = std::max(need, cpg_conv1x1_pack_workspace(d)); break;
+        case ROUTE_C3S2: need = std::max(need, cpg_conv3x3s2_pack_workspace(d)); break;
+        default: break;
+    }
+    switch (wgrad_route(d)) {
+        case ROUTE_C3: return std::max(need, cpg_conv3x3_wgrad_workspace(d));
+        case ROUTE_STEM2: return std::max(need, cpg_conv_stem2_wgrad_workspace(d));
+        case ROUTE_C3S2: return std::max(need, cpg_conv3x3s2_wgrad_workspace(d));
+        case ROUTE_C1: return std::max(need, cpg_conv1x1_wgrad_workspace(d));
+        default: break;
+    }
     int tm, tn, nsplit, per;
     conv_wgrad_tiles<CfgA>(g, tm, tn);
     const int64_t P = (int64_t)g.N * g.OH * g.OW;
     wgrad_plan((int64_t)tm * tn, (int)((P + CfgA::BK - 1) / CfgA::BK), nsplit, per);
-    return std::max(pack, nsplit > 1 ? (size_t)nsplit * g.K * g.C * g.R * g.S * sizeof(float) : (size_t)0);
+    return std::max(need, nsplit > 1 ? (size_t)nsplit * g.K * g.C * g.R * g.S * sizeof(float) : (size_t)0);
 }
 
 extern "C" int cpg_conv2d_fwd_generic(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr,
@@ -672,40 +655,46 @@ struct PackScope {
 extern "C" int cpg_conv2d_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr,
                               const float *bias, float *y, void *ws, size_t ws_bytes, void *stream) {
     PackScope scope;
-    if (d && cpg_conv3x3_supported(d)) return cpg_conv3x3_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream);
-    if (d && cpg_conv1x1_supported(d)) return cpg_conv1x1_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream);
-    if (cpg::pack_query()) return CPG_OK;
-    if (d && cpg_conv3x3s2_supported(d)) return cpg_conv3x3s2_fwd(d, x, w, pm, thr, bias, y, nullptr, ws, ws_bytes, (hipStream_t)stream);
-    if (d && cpg_conv_stem2_ok(d)) return cpg_conv_stem2_fwd(d, x, w, pm, thr, bias, y, nullptr, (hipStream_t)stream);
+    const ConvRoute route = fwd_route(d);
+    if (route == ROUTE_C3) return cpg_conv3x3_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream);
+    if (route == ROUTE_C1) return cpg_conv1x1_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream);
+    if (cpg::pack_query()) return CPG_OK;        // (only the two routes above have pack sites)
+    if (route == ROUTE_C3S2) return cpg_conv3x3s2_fwd(d, x, w, pm, thr, bias, y, nullptr, ws, ws_bytes, (hipStream_t)stream);
+    if (route == ROUTE_STEM2) return cpg_conv_stem2_fwd(d, x, w, pm, thr, bias, y, nullptr, (hipStream_t)stream);
     return cpg_conv2d_fwd_generic(d, x, w, pm, thr, bias, y, stream);
 }
 
-// Forward that also emits the BatchNorm partial sums of its output (3x3 s1 p1 shapes; 0 tiles = not available).
-extern "C" int32_t cpg_conv2d_bnstats_tiles(const cpg_conv_desc *d) {
-    if (d && cpg_conv3x3s2_supported(d)) return cpg_conv3x3s2_bnstats_tiles(d);
-    if (d && cpg_conv_stem2_ok(d)) return cpg_conv_stem2_tiles(d);
-    if (d && !cpg_conv3x3_supported(d) && cpg_conv1x1_supported(d)) return cpg_conv1x1_bnstats_tiles(d);
-    return (d && cpg_conv3x3_supported(d)) ? cpg_conv3x3_bnstats_tiles(d) : 0;
+// Forward that also emits the BatchNorm partial sums of its output (0 tiles = not available: the generic kernel, channel-split tiles).
+static int32_t bnstats_tiles(const cpg_conv_desc *d, ConvRoute route) {
+    switch (route) {
+        case ROUTE_C3: return cpg_conv3x3_bnstats_tiles(d);
+        case ROUTE_C1: return cpg_conv1x1_bnstats_tiles(d);
+        case ROUTE_C3S2: return cpg_conv3x3s2_bnstats_tiles(d);
+        case ROUTE_STEM2: return cpg_conv_stem2_tiles(d);
+        default: return 0;
+    }
 }
+extern "C" int32_t cpg_conv2d_bnstats_tiles(const cpg_conv_desc *d) { return bnstats_tiles(d, fwd_route(d)); }
 extern "C" int cpg_conv2d_fwd_bnstats(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr,
                                       const float *bias, float *y, float *stats, size_t stats_bytes, void *ws, size_t ws_bytes,
                                       void *stream) {
     PackScope scope;
-    const int tiles = cpg_conv2d_bnstats_tiles(d);
+    const ConvRoute route = fwd_route(d);
+    const int tiles = bnstats_tiles(d, route);
     if (tiles <= 0) return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_bnstats: no fused-statistics kernel for this shape");
     const size_t need = (size_t)d->K * tiles * 2 * sizeof(float);
     if (stats == nullptr || stats_bytes < need)
         return fail(CPG_E_WORKSPACE, "cpg_conv2d_fwd_bnstats: statistics buffer %zu < %zu bytes", stats_bytes, need);
-    if (cpg::pack_query() && (cpg_conv3x3s2_supported(d) || cpg_conv_stem2_ok(d))) return CPG_OK;
-    if (cpg_conv3x3s2_supported(d)) return cpg_conv3x3s2_fwd(d, x, w, pm, thr, bias, y, stats, ws, ws_bytes, (hipStream_t)stream);
-    if (cpg_conv_stem2_ok(d)) return cpg_conv_stem2_fwd(d, x, w, pm, thr, bias, y, stats, (hipStream_t)stream);
-    if (!cpg_conv3x3_supported(d)) return cpg_conv1x1_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream, stats);
-    return cpg_conv3x3_fwd_bnstats(d, x, w, pm, thr, bias, y, stats, ws, ws_bytes, (hipStream_t)stream);
+    switch (route) {
+        case ROUTE_C3: return cpg_conv3x3_fwd_bnstats(d, x, w, pm, thr, bias, y, stats, ws, ws_bytes, (hipStream_t)stream);
+        case ROUTE_C1: return cpg_conv1x1_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream, stats);
+        default: break;
+    }
+    if (cpg::pack_query()) return CPG_OK;        // (only the two routes above have pack sites)
+    if (route == ROUTE_C3S2) return cpg_conv3x3s2_fwd(d, x, w, pm, thr, bias, y, stats, ws, ws_bytes, (hipStream_t)stream);
+    return cpg_conv_stem2_fwd(d, x, w, pm, thr, bias, y, stats, (hipStream_t)stream);
 }
 
-extern "C" int cpg_conv3x3_wino_ok(int N, int c_read, int m, int H, int W);
-extern "C" int cpg_conv3x3_wino_wgrad_ok(const cpg_conv_desc *d);
-extern "C" int cpg_conv3x3_wino_eval_ok(int N, int c_read, int m, int H, int W);
 extern "C" int32_t cpg_conv2d_winograd(const cpg_conv_desc *d, int32_t dgrad) {
     ConvGeom g;
     if (d == nullptr || make_geom(d, g) != CPG_OK || !cpg_conv3x3_supported(d)) return 0;
@@ -753,17 +742,15 @@ extern "C" int cpg_conv2d_dgrad_bnbwd(const cpg_conv_desc *d, const float *gy, c
 extern "C" int cpg_conv2d_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr,
                                 float *gx, void *ws, size_t ws_bytes, void *stream) {
     PackScope scope;
-    if (d && cpg_conv3x3_supported(d)) return cpg_conv3x3_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream);
-    if (d && cpg_conv1x1_supported(d)) return cpg_conv1x1_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream);
-    if (cpg::pack_query()) return CPG_OK;
-    if (d && cpg_conv3x3s2_supported(d)) return cpg_conv3x3s2_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream);
+    const ConvRoute route = fwd_route(d);
+    if (route == ROUTE_C3) return cpg_conv3x3_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream);
+    if (route == ROUTE_C1) return cpg_conv1x1_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream);
+    if (cpg::pack_query()) return CPG_OK;        // (only the two routes above have pack sites)
+    if (route == ROUTE_C3S2) return cpg_conv3x3s2_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream);
     return cpg_conv2d_dgrad_generic(d, gy, w, pm, thr, gx, stream);
 }
 
 // input gradient + addend (the gradient of the input's other consumer): dense pointwise layers only
-extern "C" int cpg_conv3x3_wino_dgrad_add_ok(int N, int c_read, int m, int H, int W);
-extern "C" int cpg_conv3x3_wino_dgrad_add(int N, int c_read, int m, int H, int W, int K, int C, const float *gy, const float *w, const float *pm,
-                                          float thr, const float *addend, float *gx, void *ws, size_t ws_bytes, hipStream_t stream);
 extern "C" int32_t cpg_conv2d_dgrad_add_supported(const cpg_conv_desc *d) {
     if (d == nullptr) return 0;
     // (round 5) the 3x3 s1 p1 layers whose input gradient runs the two-wave Winograd kernel: SphereNet's residual units
@@ -843,7 +830,6 @@ extern "C" int cpg_conv2d_use_packed(const void *packed, size_t bytes) {
 }
 
 // ---- the BatchNorm backward apply of the layer below as a side job of the weight gradient (include/cpg_hip.h) --------------------------
-extern "C" int cpg_conv3x3_wino_wgrad_rider_ok(const cpg_conv_desc *d);
 extern "C" int32_t cpg_conv2d_wgrad_rider_supported(const cpg_conv_desc *d) {
     ConvGeom g;
     if (d == nullptr || make_geom(d, g) != CPG_OK || !use_c3_wgrad(d) || !cpg_conv3x3_wino_wgrad_ok(d)) return 0;
@@ -867,48 +853,9 @@ struct RiderScope {          // one-shot, like PackScope
 };
 }  // namespace
 
-extern "C" int cpg_conv2d_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm,
-                                float thr, float *gw, float *gpm, float *gb, void *ws, size_t ws_bytes, void *stream_v) {
-    RiderScope rider_scope;
-    ConvGeom g;
-    int rc = make_geom(d, g);
-    if (rc) return rc;
-    if (cpg::wgrad_rider().armed && !cpg_conv2d_wgrad_rider_supported(d))
-        return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_wgrad: a BatchNorm backward is attached but this launch cannot carry it (cpg_conv2d_wgrad_rider_supported)");
-    CPG_REQUIRE(x && gy && gw, "cpg_conv2d_wgrad: null pointer");
-    CPG_REQUIRE((pm == nullptr) == (gpm == nullptr), "cpg_conv2d_wgrad: pm and gpm must both be given or both be NULL");
-    CPG_REQUIRE(pm == nullptr || w != nullptr, "cpg_conv2d_wgrad: w is required to form the piggymask gradient");
-    if (gb != nullptr && (ws == nullptr || ws_bytes < bias_ws_bytes(g.N, g.K)))
-        return fail(CPG_E_WORKSPACE, "cpg_conv2d_wgrad: workspace %zu < %zu bytes (bias gradient)", ws_bytes, bias_ws_bytes(g.N, g.K));
-    hipStream_t stream = (hipStream_t)stream_v;
-    if (use_c3_wgrad(d)) {
-        rc = cpg_conv3x3_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream);
-        if (rc) return rc;
-        if (gb) launch_conv_bias_grad(gy, gb, g.N, g.K, g.OH * g.OW, ws, stream);
-        CPG_CHECK_LAUNCH("cpg_conv2d_wgrad(bias)");
-        return CPG_OK;
-    }
-    if (cpg_conv_stem2_ok(d)) {
-        rc = cpg_conv_stem2_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream);
-        if (rc) return rc;
-        if (gb) launch_conv_bias_grad(gy, gb, g.N, g.K, g.OH * g.OW, ws, stream);
-        CPG_CHECK_LAUNCH("cpg_conv2d_wgrad(bias)");
-        return CPG_OK;
-    }
-    if (cpg_conv3x3s2_supported(d)) {
-        rc = cpg_conv3x3s2_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream);
-        if (rc) return rc;
-        if (gb) launch_conv_bias_grad(gy, gb, g.N, g.K, g.OH * g.OW, ws, stream);
-        CPG_CHECK_LAUNCH("cpg_conv2d_wgrad(bias)");
-        return CPG_OK;
-    }
-    if (cpg_conv1x1_wgrad_supported(d)) {
-        rc = cpg_conv1x1_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream);
-        if (rc) return rc;
-        if (gb) launch_conv_bias_grad(gy, gb, g.N, g.K, g.OH * g.OW, ws, stream);
-        CPG_CHECK_LAUNCH("cpg_conv2d_wgrad(bias)");
-        return CPG_OK;
-    }
+// the generic weight gradient (the caller checks the launches)
+static int wgrad_generic(const ConvGeom &g, const float *x, const float *gy, const float *w, const float *pm, float thr, float *gw, float *gpm,
+                         void *ws, size_t ws_bytes, hipStream_t stream) {
     int tm, tn, nsplit, per;
     conv_wgrad_tiles<CfgA>(g, tm, tn);
     const int64_t P = (int64_t)g.N * g.OH * g.OW;
@@ -924,8 +871,34 @@ extern "C" int cpg_conv2d_wgrad(const cpg_conv_desc *d, const float *x, const fl
                        part, tm, per);
     if (nsplit > 1)
         launch_split_reduce(part, nsplit, out_elems, 0, ep, stream);
-    if (gb) launch_conv_bias_grad(gy, gb, g.N, g.K, g.OH * g.OW, ws, stream);
-    CPG_CHECK_LAUNCH("cpg_conv2d_wgrad");
+    return CPG_OK;
+}
+
+extern "C" int cpg_conv2d_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm,
+                                float thr, float *gw, float *gpm, float *gb, void *ws, size_t ws_bytes, void *stream_v) {
+    RiderScope rider_scope;
+    ConvGeom g;
+    int rc = make_geom(d, g);
+    if (rc) return rc;
+    if (cpg::wgrad_rider().armed && !cpg_conv2d_wgrad_rider_supported(d))
+        return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_wgrad: a BatchNorm backward is attached but this launch cannot carry it (cpg_conv2d_wgrad_rider_supported)");
+    CPG_REQUIRE(x && gy && gw, "cpg_conv2d_wgrad: null pointer");
+    CPG_REQUIRE((pm == nullptr) == (gpm == nullptr), "cpg_conv2d_wgrad: pm and gpm must both be given or both be NULL");
+    CPG_REQUIRE(pm == nullptr || w != nullptr, "cpg_conv2d_wgrad: w is required to form the piggymask gradient");
+    if (gb != nullptr && (ws == nullptr || ws_bytes < bias_ws_bytes(g.N, g.K)))
+        return fail(CPG_E_WORKSPACE, "cpg_conv2d_wgrad: workspace %zu < %zu bytes (bias gradient)", ws_bytes, bias_ws_bytes(g.N, g.K));
+    hipStream_t stream = (hipStream_t)stream_v;
+    const char *what = "cpg_conv2d_wgrad(bias)";         // (the specialised routes have checked their own launches)
+    switch (wgrad_route(d)) {
+        case ROUTE_C3: rc = cpg_conv3x3_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream); break;
+        case ROUTE_STEM2: rc = cpg_conv_stem2_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream); break;
+        case ROUTE_C3S2: rc = cpg_conv3x3s2_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream); break;
+        case ROUTE_C1: rc = cpg_conv1x1_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream); break;
+        default: rc = wgrad_generic(g, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream); what = "cpg_conv2d_wgrad"; break;
+    }
+    if (rc) return rc;
+    if (gb) launch_conv_bias_grad(gy, gb, g.N, g.K, g.OH * g.OW, ws, stream);       // (the workspace is free again: same stream)
+    CPG_CHECK_LAUNCH(what);
     return CPG_OK;
 }
 
@@ -942,27 +915,6 @@ void gemm_plan(int64_t tiles, int nkt, int &nsplit, int &per) {
     nsplit = (nkt + per - 1) / per;
 }
 }  // namespace
-// plain-GEMM entry points of pointwise.hip (used when the layer has no piggymask)
-bool cpg_pw_gemm_nt_ok(const float *A, const float *B, int M, int C, int64_t K);
-size_t cpg_pw_gemm_nt_workspace(int M, int C, int64_t K);
-int cpg_pw_gemm_nt(const float *A, const float *B, int M, int C, int64_t K, const Epilogue &ep, void *ws, size_t ws_bytes,
-                   hipStream_t stream, const char *what);
-int cpg_pw_gemm_nt_maskb(const float *A, const float *B, const float *pmB, float thr, int M, int C, int64_t K, const Epilogue &ep, void *ws,
-                         size_t ws_bytes, hipStream_t stream, const char *what);
-bool cpg_pw_gemm_nn_ok(const float *X, int M, int Mp, int Kd, int64_t G, bool masked = false);
-int cpg_pw_gemm_nn(const float *wp, int Mp, const float *X, int M, int Kd, int64_t G, const float *bias, float *y, hipStream_t stream,
-                   const char *what);
-int cpg_pw_gemm_nn_masked(const float *wp, int Mp, const float *X, int M, int Kd, int64_t G, const float *pm, const float *w, float thr,
-                          float *gw, float *gpm, hipStream_t stream, const char *what);
-int cpg_pw_gemm_nn_maskx(const float *wp, int Mp, const float *X, const float *pmX, float thr, int M, int Kd, int64_t G, float *y,
-                         hipStream_t stream, const char *what);
-void cpg_pw_pack_transpose(const float *a, int R, int Cc, float *wp, hipStream_t stream);
-size_t cpg_pw_pack_transpose_bytes(int R, int Cc);
-// fc_small.hip: the weight-streaming input gradient at <= 64 rows
-bool cpg_fc_small_dgrad_ok(const float *w, const float *pm, const float *gx, int batch, int in_f, int out_f);
-size_t cpg_fc_small_dgrad_workspace(int batch, int in_f, int out_f);
-int cpg_fc_small_dgrad(const float *gy, const float *w, const float *pm, float thr, float *gx, int batch, int in_f, int out_f, void *ws,
-                       size_t ws_bytes, hipStream_t stream, const char *what);
 namespace {
 size_t linear_ws(int batch, int in_f, int out_f) {
     size_t best = std::max(cpg_pw_gemm_nt_workspace(batch, out_f, in_f), cpg_pw_pack_transpose_bytes(batch, out_f));

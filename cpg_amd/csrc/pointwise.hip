@@ -23,7 +23,7 @@
 //          strided / odd-sized ones stay on the generic split-K kernel of igemm_conv.hip.
 #include <algorithm>
 #include <type_traits>
-#include "igemm_core.h"
+#include "cpg_dispatch.h"
 
 using namespace cpg;
 

@@ -44,6 +44,37 @@ def test_library_exports_nothing_but_the_header():
     assert exported == set(L.EXPORTS), exported ^ set(L.EXPORTS)
 
 
+def test_cross_file_helpers_are_declared_once():
+    """cpg_amd/csrc/cpg_dispatch.h is the only place a cross-file helper is declared: no source file carries a body-less prototype of
+    a cpg_* function (a use-site copy that drifts from the definition passes arguments in the wrong slots without a diagnostic)."""
+    import glob
+    csrc = os.path.join(ROOT, 'cpg_amd', 'csrc')
+    files = sorted(glob.glob(os.path.join(csrc, '*.hip')) + glob.glob(os.path.join(csrc, '*.cpp')))
+    files.append(os.path.join(ROOT, 'tools', 'csrc', 'wino_wgrad_template.hip'))
+    assert len(files) > 16
+    # a declaration at file scope: optional linkage / storage words, a return type, the name, a parameter list without a body
+    proto = re.compile(r'^(?:extern "C" |static |inline )*(?:int|size_t|bool|void|int32_t|int64_t|unsigned|float|double)\s+\**cpg_\w+\([^{;]*\);',
+                       re.M)
+    found = {os.path.relpath(f, ROOT): [m.group(0).split('(')[0] for m in proto.finditer(open(f).read())] for f in files}
+    found = {f: names for f, names in found.items() if names}
+    assert not found, found
+    header = open(os.path.join(csrc, 'cpg_dispatch.h')).read()
+    declared = [m.group(0).split('(')[0].split()[-1] for m in proto.finditer(header)]
+    assert len(declared) == len(set(declared)) >= 60, sorted(n for n in declared if declared.count(n) > 1)
+    for name in ('cpg_conv3x3_wino_run', 'cpg_conv3x3_wino_run_bn_eval', 'cpg_conv3x3_wino_wgrad', 'cpg_conv1x1_fwd', 'cpg_pw_gemm_nn_ok'):
+        assert name in declared
+
+
+def test_generated_wgrad_kernel_is_current():
+    """cpg_amd/csrc/conv3x3_wino_wgrad.hip is exactly what tools/gen_wino_wgrad.py makes of tools/csrc/wino_wgrad_template.hip."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('gen_wino_wgrad', os.path.join(ROOT, 'tools', 'gen_wino_wgrad.py'))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    committed = open(os.path.join(ROOT, 'cpg_amd', 'csrc', 'conv3x3_wino_wgrad.hip')).read()
+    assert gen.generate() == committed, 'run python tools/gen_wino_wgrad.py'
+
+
 def test_struct_layouts_match_header():
     import ctypes
     assert ctypes.sizeof(L.ConvDesc) == 14 * 4

@@ -24,7 +24,7 @@
 // through the autograd epilogue (gW = g * bin(pm), gPM = g * W) exactly as for the direct kernels.
 // The sign of the transform rows / columns with a -1 (A's last row) is applied to M in the epilogue instead of to the operands.
 #include <algorithm>
-#include "igemm_core.h"
+#include "cpg_dispatch.h"
 
 using namespace cpg;
 

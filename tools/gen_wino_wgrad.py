@@ -103,10 +103,20 @@ def make_body(narrow, gs=0):
     body += '            advance_stage();\n        }\n'
   return body
 
-body, body_n, body_s4, body_s2, body_ns4 = make_body(False), make_body(True), make_body(False, 4), make_body(False, 2), make_body(True, 4)
+TEMPLATE = os.path.join(ROOT, 'tools', 'csrc', 'wino_wgrad_template.hip')
+OUTPUT = os.path.join(ROOT, 'cpg_amd', 'csrc', 'conv3x3_wino_wgrad.hip')
 
-src = open(os.path.join(ROOT, 'tools', 'csrc', 'wino_wgrad_template.hip')).read()
-src = src.replace('@@MMA@@', mma).replace('@@ZERO@@', zero).replace('@@RD@@', rd).replace('@@OUT@@', out_calls).replace('@@BODY@@', body).replace('@@BODY_N@@', body_n).replace('@@BODY_S4@@', body_s4).replace('@@BODY_S2@@', body_s2).replace('@@BODY_NS4@@', body_ns4)
-src = '// GENERATED by tools/gen_wino_wgrad.py from tools/csrc/wino_wgrad_template.hip -- edit those, not this file.\n' + src
-open(os.path.join(ROOT, 'cpg_amd', 'csrc', 'conv3x3_wino_wgrad.hip'), 'w').write(src)
-print('ok', len(src))
+def generate():
+    """The text of cpg_amd/csrc/conv3x3_wino_wgrad.hip (tests/test_abi_and_host.py compares it with the committed file)."""
+    body, body_n, body_s4, body_s2, body_ns4 = make_body(False), make_body(True), make_body(False, 4), make_body(False, 2), make_body(True, 4)
+    src = open(TEMPLATE).read()
+    src = src.replace('@@MMA@@', mma).replace('@@ZERO@@', zero).replace('@@RD@@', rd).replace('@@OUT@@', out_calls).replace('@@BODY@@', body).replace('@@BODY_N@@', body_n).replace('@@BODY_S4@@', body_s4).replace('@@BODY_S2@@', body_s2).replace('@@BODY_NS4@@', body_ns4)
+    return '// GENERATED by tools/gen_wino_wgrad.py from tools/csrc/wino_wgrad_template.hip -- edit those, not this file.\n' + src
+
+def main():
+    src = generate()
+    open(OUTPUT, 'w').write(src)
+    print('ok', len(src))
+
+if __name__ == '__main__':
+    main()
