@@ -21,8 +21,6 @@ CPG_E_INVALID = -1
 MODE_FINETUNE = 0
 MODE_PRUNE = 1
 
-_c_f32p = ctypes.c_void_p
-_vp = ctypes.c_void_p
 
 
 class ConvDesc(ctypes.Structure):
@@ -60,122 +58,101 @@ PRUNE_RESULT_BYTES = ctypes.sizeof(PruneResult)
 assert PRUNE_RESULT_BYTES == 32
 assert ctypes.sizeof(ResampleItem) == ctypes.sizeof(TensorItem) == 48
 
-# name -> (restype, argtypes); mirrors include/cpg_hip.h one to one
+# name -> (restype, argtypes); mirrors include/cpg_hip.h one to one (tests/test_abi_and_host.py compares every slot with the header)
+_vp, _int, _i32, _i64, _sz, _f32, _f64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float,
+                                         ctypes.c_double)
+_desc = ctypes.POINTER(ConvDesc)
 _SIGNATURES = {
-    'cpg_version': (ctypes.c_int, []),
-    'cpg_set_shared_chip_hint': (ctypes.c_int, [ctypes.c_int32]),
-    'cpg_get_shared_chip_hint': (ctypes.c_int32, []),
-    'cpg_set_option': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32]),
-    'cpg_get_option': (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32)]),
+    'cpg_version': (_int, []),
+    'cpg_set_shared_chip_hint': (_int, [_i32]),
+    'cpg_get_shared_chip_hint': (_i32, []),
+    'cpg_set_option': (_int, [ctypes.c_char_p, _i32]),
+    'cpg_get_option': (_int, [ctypes.c_char_p, ctypes.POINTER(_i32)]),
     'cpg_last_error': (ctypes.c_char_p, []),
-    'cpg_binarize_mask_weight': (ctypes.c_int, [_vp, _vp, ctypes.c_float, _vp, ctypes.c_int64, _vp]),
-    'cpg_conv2d_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
-    'cpg_conv2d_fwd': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'cpg_conv2d_dgrad': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]),
-    'cpg_conv2d_dgrad_add_supported': (ctypes.c_int32, [ctypes.POINTER(ConvDesc)]),
-    'cpg_conv2d_dgrad_add': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'cpg_conv2d_wgrad': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'cpg_conv2d_pack_bytes': (ctypes.c_size_t, [ctypes.POINTER(ConvDesc), ctypes.c_int32]),
-    'cpg_conv2d_pack': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, ctypes.c_float, ctypes.c_int32, _vp, ctypes.c_size_t, ctypes.c_int32, _vp,
-                                       ctypes.c_size_t, _vp]),
-    'cpg_conv2d_use_packed': (ctypes.c_int, [_vp, ctypes.c_size_t]),
-    'cpg_bn_relu_bwd_reduce': (ctypes.c_int, [_vp] * 9 + [ctypes.c_int32] * 3 + [_vp, ctypes.c_size_t, _vp]),
-    'cpg_conv2d_wgrad_rider_supported': (ctypes.c_int32, [ctypes.POINTER(ConvDesc)]),
-    'cpg_conv2d_wgrad_attach_bn_bwd': (ctypes.c_int, [_vp] * 4 + [ctypes.c_int32] * 3),
-    'cpg_linear_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    'cpg_linear_fwd': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_size_t, _vp]),
-    'cpg_linear_dgrad': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_size_t, _vp]),
-    'cpg_linear_wgrad': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_size_t, _vp]),
-    'cpg_route_grads': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_float, _vp, ctypes.c_int32, ctypes.c_int64, _vp]),
-    'cpg_rank_prune_workspace_bytes': (ctypes.c_size_t, []),
-    'cpg_rank_prune': (ctypes.c_int, [_vp, _vp, ctypes.c_int32, ctypes.c_double, ctypes.c_int64, _vp, _vp, ctypes.c_size_t, _vp]),
-    'cpg_mask_hist': (ctypes.c_int, [_vp, _vp, ctypes.c_int32, ctypes.c_int64, _vp, _vp]),
-    'cpg_apply_mask': (ctypes.c_int, [_vp, _vp, ctypes.c_int32, ctypes.c_int64, _vp]),
-    'cpg_zero_pruned': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp]),
-    'cpg_claim_free': (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int64, _vp]),
-    'cpg_owned_num_blocks': (ctypes.c_int64, [ctypes.c_int64]),
-    'cpg_owned_block_counts': (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _vp, _vp]),
-    'cpg_pack_owned': (ctypes.c_int, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _vp, _vp, _vp]),
-    'cpg_unpack_owned': (ctypes.c_int, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _vp, _vp, _vp]),
-    'cpg_sgd_route_step': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _vp]),
-    'cpg_multi_tensor_max': (ctypes.c_int32, []),
-    'cpg_sgd_route_step_multi': (ctypes.c_int, [ctypes.POINTER(SgdItem), ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                                ctypes.c_int32, ctypes.c_int32, _vp]),
-    'cpg_adam_route_step_multi': (ctypes.c_int, [ctypes.POINTER(AdamItem), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
-                                                 ctypes.c_double, ctypes.c_double, ctypes.c_int32, _vp]),
-    'cpg_adam_route_step': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
-                                           ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_int64, _vp]),
-    'cpg_bn_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    'cpg_bn_relu_fwd_train': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp, _vp,
-                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_size_t, _vp]),
-    'cpg_bn_relu_fwd_eval': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                            ctypes.c_int32, _vp]),
-    'cpg_bn_relu_pool_fwd': (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32,
-                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_size_t, _vp]),
-    'cpg_bn_relu_pool_bwd': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                            ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_size_t, _vp]),
-    'cpg_bn_relu_bwd': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                       ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_size_t, _vp]),
-    'cpg_conv2d_winograd': (ctypes.c_int32, [ctypes.POINTER(ConvDesc), ctypes.c_int32]),
-    'cpg_conv2d_bnstats_tiles': (ctypes.c_int32, [ctypes.POINTER(ConvDesc)]),
-    'cpg_conv2d_fwd_bnstats': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp,
-                                              ctypes.c_size_t, _vp]),
-    'cpg_conv2d_fwd_bn_eval_supported': (ctypes.c_int32, [ctypes.POINTER(ConvDesc)]),
-    'cpg_conv2d_fwd_bn_eval': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, ctypes.c_float,
-                                              ctypes.c_int32, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'cpg_conv2d_bf16_supported': (ctypes.c_int32, [ctypes.POINTER(ConvDesc)]),
-    'cpg_conv2d_bf16_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
-    'cpg_conv2d_fwd_bf16': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'cpg_conv2d_wgrad_bf16_supported': (ctypes.c_int32, [ctypes.POINTER(ConvDesc)]),
-    'cpg_conv2d_wgrad_bf16_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
-    'cpg_conv2d_wgrad_bf16': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'cpg_conv2d_fwd_bf16x3': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'cpg_conv2d_dgrad_bf16x3': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]),
-    'cpg_conv2d_wgrad_bf16x3': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'cpg_conv2d_dgrad_bf16': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]),
-    'cpg_conv2d_dgrad_bnbwd_tiles': (ctypes.c_int32, [ctypes.POINTER(ConvDesc)]),
-    'cpg_conv2d_dgrad_bnbwd': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                              ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
-    'cpg_bn_bwd_from_partials': (ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_int32, _vp, ctypes.c_size_t, _vp]),
-    'cpg_bn_bwd_finalize_partials': (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp]),
-    'cpg_stem_bn_supported': (ctypes.c_int32, [ctypes.POINTER(ConvDesc)]),
-    'cpg_stem_bn_tiles': (ctypes.c_int32, [ctypes.POINTER(ConvDesc)]),
-    'cpg_stem_bn_stats': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, ctypes.c_size_t, _vp]),
-    'cpg_stem_bn_relu_fwd': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'cpg_stem_bn_relu_bwd_reduce': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                   ctypes.c_size_t, _vp]),
-    'cpg_stem_bn_relu_bwd_apply': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                  _vp, _vp]),
-    'cpg_stem_bn_wgrad_workspace': (ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
-    'cpg_stem_bn_relu_bwd_wgrad': (ctypes.c_int, [ctypes.POINTER(ConvDesc), _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                  _vp, _vp, _vp, ctypes.c_size_t, _vp]),
-    'cpg_bn_stats_finalize_count': (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                                   ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'cpg_bn_stats_finalize': (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                             ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
-    'cpg_bn_add_relu_mask_bytes': (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    'cpg_bn_add_relu_fwd': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32,
-                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_size_t, _vp, _vp]),
-    'cpg_bn_relu_pool3_supported': (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32]),
-    'cpg_bn_relu_pool3_fwd': (ctypes.c_int, [_vp] * 6 + [ctypes.c_int32] * 4 + [_vp]),
-    'cpg_bn_relu_pool3_bwd': (ctypes.c_int, [_vp] * 9 + [ctypes.c_int32] * 5 + [_vp, ctypes.c_size_t, _vp]),
-    'cpg_bn_add_relu_bwd': (ctypes.c_int, [_vp] * 11 + [ctypes.c_int32] * 4 + [_vp, ctypes.c_size_t, _vp, _vp]),
-    'cpg_prelu_fwd': (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp]),
-    'cpg_prelu_bwd_bias': (ctypes.c_int, [_vp] * 6 + [ctypes.c_int32] * 4 + [_vp, ctypes.c_size_t, _vp]),
-    'cpg_prelu_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    'cpg_prelu_bwd': (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp,
-                                     ctypes.c_size_t, _vp]),
-    'cpg_image_resample_workspace_bytes': (ctypes.c_size_t, [ctypes.POINTER(ResampleItem), ctypes.c_int32]),
-    'cpg_image_resample': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(ResampleItem), ctypes.c_int32, _vp, ctypes.c_int64, _vp,
-                                          ctypes.c_size_t, _vp]),
-    'cpg_image_to_tensor': (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(TensorItem), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                           ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _vp, ctypes.c_int64, _vp]),
-    'cpg_pair_distance': (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _vp, _vp,
-                                         _vp]),
-    'cpg_pair_sweep': (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.c_int32, _vp, _vp,
-                                      _vp]),
+    'cpg_binarize_mask_weight': (_int, [_vp, _vp, _f32, _vp, _i64, _vp]),
+    'cpg_conv2d_workspace_bytes': (_sz, [_desc]),
+    'cpg_conv2d_fwd': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _sz, _vp]),
+    'cpg_conv2d_dgrad': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _sz, _vp]),
+    'cpg_conv2d_dgrad_add_supported': (_i32, [_desc]),
+    'cpg_conv2d_dgrad_add': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _sz, _vp]),
+    'cpg_conv2d_wgrad': (_int, [_desc, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'cpg_conv2d_pack_bytes': (_sz, [_desc, _i32]),
+    'cpg_conv2d_pack': (_int, [_desc, _vp, _vp, _f32, _i32, _vp, _sz, _i32, _vp, _sz, _vp]),
+    'cpg_conv2d_use_packed': (_int, [_vp, _sz]),
+    'cpg_bn_relu_bwd_reduce': (_int, [_vp] * 9 + [_i32] * 3 + [_vp, _sz, _vp]),
+    'cpg_conv2d_wgrad_rider_supported': (_i32, [_desc]),
+    'cpg_conv2d_wgrad_attach_bn_bwd': (_int, [_vp] * 4 + [_i32] * 3),
+    'cpg_linear_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    'cpg_linear_fwd': (_int, [_vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    'cpg_linear_dgrad': (_int, [_vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    'cpg_linear_wgrad': (_int, [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    'cpg_route_grads': (_int, [_vp, _vp, _vp, _i32, _f32, _vp, _i32, _i64, _vp]),
+    'cpg_rank_prune_workspace_bytes': (_sz, []),
+    'cpg_rank_prune': (_int, [_vp, _vp, _i32, _f64, _i64, _vp, _vp, _sz, _vp]),
+    'cpg_mask_hist': (_int, [_vp, _vp, _i32, _i64, _vp, _vp]),
+    'cpg_apply_mask': (_int, [_vp, _vp, _i32, _i64, _vp]),
+    'cpg_zero_pruned': (_int, [_vp, _vp, _i64, _vp]),
+    'cpg_claim_free': (_int, [_vp, _i32, _i64, _vp]),
+    'cpg_owned_num_blocks': (_i64, [_i64]),
+    'cpg_owned_block_counts': (_int, [_vp, _i32, _i32, _i64, _vp, _vp]),
+    'cpg_pack_owned': (_int, [_vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp]),
+    'cpg_unpack_owned': (_int, [_vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp]),
+    'cpg_sgd_route_step': (_int, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _i32, _i32, _i64, _vp]),
+    'cpg_multi_tensor_max': (_i32, []),
+    'cpg_sgd_route_step_multi': (_int, [ctypes.POINTER(SgdItem), _i32, _i32, _f32, _f32, _f32, _i32, _i32, _vp]),
+    'cpg_adam_route_step_multi': (_int, [ctypes.POINTER(AdamItem), _i32, _i32, _i32, _f64, _f64, _f64, _f64, _i32, _vp]),
+    'cpg_adam_route_step': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _f64, _f64, _i32, _i64, _vp]),
+    'cpg_bn_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    'cpg_bn_relu_fwd_train': (_int, [_vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    'cpg_bn_relu_fwd_eval': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    'cpg_bn_relu_pool_fwd': (_int, [_vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    'cpg_bn_relu_pool_bwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    'cpg_bn_relu_bwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    'cpg_conv2d_winograd': (_i32, [_desc, _i32]),
+    'cpg_conv2d_bnstats_tiles': (_i32, [_desc]),
+    'cpg_conv2d_fwd_bnstats': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    'cpg_conv2d_fwd_bn_eval_supported': (_i32, [_desc]),
+    'cpg_conv2d_fwd_bn_eval': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    'cpg_conv2d_bf16_supported': (_i32, [_desc]),
+    'cpg_conv2d_bf16_workspace_bytes': (_sz, [_desc]),
+    'cpg_conv2d_fwd_bf16': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _sz, _vp]),
+    'cpg_conv2d_wgrad_bf16_supported': (_i32, [_desc]),
+    'cpg_conv2d_wgrad_bf16_workspace_bytes': (_sz, [_desc]),
+    'cpg_conv2d_wgrad_bf16': (_int, [_desc, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _sz, _vp]),
+    'cpg_conv2d_fwd_bf16x3': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _sz, _vp]),
+    'cpg_conv2d_dgrad_bf16x3': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _sz, _vp]),
+    'cpg_conv2d_wgrad_bf16x3': (_int, [_desc, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _sz, _vp]),
+    'cpg_conv2d_dgrad_bf16': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _sz, _vp]),
+    'cpg_conv2d_dgrad_bnbwd_tiles': (_i32, [_desc]),
+    'cpg_conv2d_dgrad_bnbwd': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    'cpg_bn_bwd_from_partials': (_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    'cpg_bn_bwd_finalize_partials': (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'cpg_stem_bn_supported': (_i32, [_desc]),
+    'cpg_stem_bn_tiles': (_i32, [_desc]),
+    'cpg_stem_bn_stats': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _sz, _vp]),
+    'cpg_stem_bn_relu_fwd': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'cpg_stem_bn_relu_bwd_reduce': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'cpg_stem_bn_relu_bwd_apply': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'cpg_stem_bn_wgrad_workspace': (_sz, [_desc]),
+    'cpg_stem_bn_relu_bwd_wgrad': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'cpg_bn_stats_finalize_count': (_int, [_vp, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'cpg_bn_stats_finalize': (_int, [_vp, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    'cpg_bn_add_relu_mask_bytes': (_sz, [_i32, _i32, _i32]),
+    'cpg_bn_add_relu_fwd': (_int, [_vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
+    'cpg_bn_relu_pool3_supported': (_i32, [_i32, _i32]),
+    'cpg_bn_relu_pool3_fwd': (_int, [_vp] * 6 + [_i32] * 4 + [_vp]),
+    'cpg_bn_relu_pool3_bwd': (_int, [_vp] * 9 + [_i32] * 5 + [_vp, _sz, _vp]),
+    'cpg_bn_add_relu_bwd': (_int, [_vp] * 11 + [_i32] * 4 + [_vp, _sz, _vp, _vp]),
+    'cpg_prelu_fwd': (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    'cpg_prelu_bwd_bias': (_int, [_vp] * 6 + [_i32] * 4 + [_vp, _sz, _vp]),
+    'cpg_prelu_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    'cpg_prelu_bwd': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    'cpg_image_resample_workspace_bytes': (_sz, [ctypes.POINTER(ResampleItem), _i32]),
+    'cpg_image_resample': (_int, [_vp, _i64, ctypes.POINTER(ResampleItem), _i32, _vp, _i64, _vp, _sz, _vp]),
+    'cpg_image_to_tensor': (_int, [_vp, _i64, ctypes.POINTER(TensorItem), _i32, _i32, _i32, ctypes.POINTER(_f32), ctypes.POINTER(_f32), _vp,
+                                           _i64, _vp]),
+    'cpg_pair_distance': (_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    'cpg_pair_sweep': (_int, [_vp, _vp, _i64, ctypes.POINTER(_f64), _i32, _i32, _vp, _vp, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -213,6 +190,14 @@ def check(fn_name, code):
         raise CpgHipError(fn_name, code, text.decode(errors='replace') if text else '')
 
 
+def call(name, *args):
+    """One status-returning entry point: looked up on lib() at call time (a profiler may have put a proxy there), raised on failure under
+    its own name."""
+    rc = getattr(_lib if _lib is not None else lib(), name)(*args)
+    if rc != CPG_OK:
+        check(name, rc)
+
+
 OPT_UNSET = -(1 << 31)
 _WINO_KERNEL = {'block': 0, 'wave': 1, 'pair': 2, '64': 3}
 
@@ -220,7 +205,7 @@ _WINO_KERNEL = {'block': 0, 'wave': 1, 'pair': 2, '64': 3}
 def get_option(name):
     """Current value of a library switch (include/cpg_hip.h: cpg_get_option); None when it was never given."""
     v = ctypes.c_int32(0)
-    check('cpg_get_option', lib().cpg_get_option(name.encode(), ctypes.byref(v)))
+    call('cpg_get_option', name.encode(), ctypes.byref(v))
     return None if v.value == OPT_UNSET else v.value
 
 
@@ -229,10 +214,21 @@ def set_option(name, value):
     the only way to change it afterwards.  CPG_WINO_KERNEL also takes its environment spelling ('block' | 'wave' | 'pair' | '64')."""
     if isinstance(value, str):
         value = _WINO_KERNEL[value] if name == 'CPG_WINO_KERNEL' else int(value)
-    check('cpg_set_option', lib().cpg_set_option(name.encode(), OPT_UNSET if value is None else int(value)))
-    mod = sys.modules.get('cpg_amd.models.layers')
-    if mod is not None:
-        mod._PACK_BYTES.clear()             # which kernel family (hence which packed operand) a shape gets depends on the switches
+    call('cpg_set_option', name.encode(), OPT_UNSET if value is None else int(value))
+    _PACK_BYTES.clear()                     # which kernel family (hence which packed operand) a shape gets depends on the switches
+
+
+_PACK_BYTES = {}
+
+
+def pack_bytes(d, which):
+    """cpg_conv2d_pack_bytes per (shape, pass), memoised: the answer depends on the shape and the library options only (set_option
+    clears the table)."""
+    key = (d.N, d.C, d.H, d.W, d.K, d.R, d.S, d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w, d.groups, which)
+    v = _PACK_BYTES.get(key)
+    if v is None:
+        v = _PACK_BYTES[key] = int(lib().cpg_conv2d_pack_bytes(ctypes.byref(d), which))
+    return v
 
 
 class option(object):

@@ -54,21 +54,17 @@ def resample(src, src_bytes, rows, dst, dst_bytes):
     items = _items(_lib.ResampleItem, rows)
     nbytes = lib.cpg_image_resample_workspace_bytes(items, len(rows))
     ws, wsb = _lib.workspace(nbytes, dst.device) if nbytes else (None, 0)
-    rc = lib.cpg_image_resample(_lib.dptr(src, torch.uint8, 'image store'), int(src_bytes), items, len(rows),
-                                _lib.dptr(dst, torch.uint8, 'resample destination'), int(dst_bytes), _lib.dptr(ws), wsb,
-                                _lib.stream_ptr())
-    _lib.check('cpg_image_resample', rc)
+    _lib.call('cpg_image_resample', _lib.dptr(src, torch.uint8, 'image store'), int(src_bytes), items, len(rows),
+              _lib.dptr(dst, torch.uint8, 'resample destination'), int(dst_bytes), _lib.dptr(ws), wsb, _lib.stream_ptr())
 
 
 def to_tensor(src, src_bytes, rows, out_h, out_w, mean, std, dst):
     """Enqueue cpg_image_to_tensor: rows (src_off, src_h, src_w, y0, x0, flip, cut_y0, cut_y1, cut_x0, cut_x1) -> dst[i]."""
-    lib = _lib.lib()
     items = _items(_lib.TensorItem, [tuple(r) + (0,) for r in rows])
     m = (ctypes.c_float * 3)(*[float(v) for v in mean])
     s = (ctypes.c_float * 3)(*[float(v) for v in std])
-    rc = lib.cpg_image_to_tensor(_lib.dptr(src, torch.uint8, 'image store'), int(src_bytes), items, len(rows), int(out_h), int(out_w),
-                                 m, s, _lib.dptr(dst, torch.float32, 'batch'), dst.numel() * 4, _lib.stream_ptr())
-    _lib.check('cpg_image_to_tensor', rc)
+    _lib.call('cpg_image_to_tensor', _lib.dptr(src, torch.uint8, 'image store'), int(src_bytes), items, len(rows), int(out_h), int(out_w), m, s,
+              _lib.dptr(dst, torch.float32, 'batch'), dst.numel() * 4, _lib.stream_ptr())
 
 
 # ---------------------------------------------------------------------------------------------------------------- the store

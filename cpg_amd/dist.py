@@ -189,9 +189,8 @@ class DataParallel(nn.Module):
         owner = pr._owner(name, p.data)
         nblk = int(L.cpg_owned_num_blocks(p.numel()))
         counts = torch.empty(nblk, dtype=torch.int32, device=p.device)
-        rc = L.cpg_owned_block_counts(_lib.dptr(owner, torch.uint8, 'mask'), cur, select, p.numel(), ctypes.c_void_p(counts.data_ptr()),
-                                      _lib.stream_ptr())
-        _lib.check('cpg_owned_block_counts', rc)
+        _lib.call('cpg_owned_block_counts', _lib.dptr(owner, torch.uint8, 'mask'), cur, select, p.numel(), ctypes.c_void_p(counts.data_ptr()),
+                  _lib.stream_ptr())
         ends = torch.cumsum(counts, 0, dtype=torch.int64)
         total = int(ends[-1].item())                              # one read-back per mask mutation, then cached
         plan = None if total > self.compact_below * p.numel() else (owner, cur, select, (ends - counts).contiguous(), total)
@@ -221,10 +220,8 @@ class DataParallel(nn.Module):
             if not g.is_contiguous():
                 p.grad = g = g.contiguous()
             buf = torch.empty(total, dtype=torch.float32, device=g.device)
-            L = _lib.lib()
-            rc = L.cpg_pack_owned(_lib.dptr(g, name='grad'), _lib.dptr(owner, torch.uint8, 'mask'), cur, select, g.numel(),
-                                  ctypes.c_void_p(offsets.data_ptr()), _lib.dptr(buf), _lib.stream_ptr())
-            _lib.check('cpg_pack_owned', rc)
+            _lib.call('cpg_pack_owned', _lib.dptr(g, name='grad'), _lib.dptr(owner, torch.uint8, 'mask'), cur, select, g.numel(),
+                      ctypes.c_void_p(offsets.data_ptr()), _lib.dptr(buf), _lib.stream_ptr())
             self._step_payload['sent_elems'] += total
             self.bucket_log.append(('packed', total * 4))
             work = dist.all_reduce(buf, op=op, group=self.process_group, async_op=True)
@@ -273,9 +270,8 @@ class DataParallel(nn.Module):
                 from . import _lib
                 import ctypes
                 grad, owner, cur, select, offsets = packed
-                rc = _lib.lib().cpg_unpack_owned(_lib.dptr(g), _lib.dptr(owner, torch.uint8, 'mask'), cur, select, grad.numel(),
-                                                 ctypes.c_void_p(offsets.data_ptr()), _lib.dptr(grad, name='grad'), _lib.stream_ptr())
-                _lib.check('cpg_unpack_owned', rc)
+                _lib.call('cpg_unpack_owned', _lib.dptr(g), _lib.dptr(owner, torch.uint8, 'mask'), cur, select, grad.numel(),
+                          ctypes.c_void_p(offsets.data_ptr()), _lib.dptr(grad, name='grad'), _lib.stream_ptr())
         self._handles = []
         for p, ch in self._chunked:
             adopted = p.grad.data_ptr() == ch.base_ptr           # autograd took the gradient tensor itself: the rows ARE p.grad's

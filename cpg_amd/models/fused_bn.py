@@ -9,31 +9,15 @@ backward (csrc/bn_kernels.hip).  Semantics are torch.nn.BatchNorm2d's: batch sta
 running statistics in eval mode.  SURVEY.md section 8(f) item 2.
 """
 import ctypes
-import threading
 
 import torch
 import torch.nn as nn
 
 from .. import _lib
+from .layers import BiasGradSink, BnBwdHint, _conv_desc
 
-
-class BnBwdHint(object):
-    """Link between a training-mode BatchNorm2d -> ReLU and the masked 3x3 conv that is the ONLY consumer of its output:
-    the conv's input-gradient kernel does the BatchNorm's backward reduction in its epilogue (cpg_conv2d_dgrad_bnbwd) and
-    leaves the partial sums here for _BnReluFn.backward (cpg_bn_bwd_from_partials) -- `epilogue` --, or the conv's weight-gradient
-    kernel runs the BatchNorm's backward apply pass as a side job (cpg_conv2d_wgrad_attach_bn_bwd) and leaves (gx, dgamma, dbeta)
-    in `result`, computed from the gradient tensor `gz` -- `rider`.  One hint per forward pass."""
-    __slots__ = ('ypre', 'gamma', 'beta', 'mean', 'invstd', 'partials', 'tiles', 'out_shape', 'epilogue', 'rider', 'gz', 'result')
-
-    def __init__(self, epilogue=True, rider=False):
-        self.ypre = self.gamma = self.beta = self.mean = self.invstd = self.partials = self.out_shape = self.gz = self.result = None
-        self.tiles = 0
-        self.epilogue, self.rider = epilogue, rider
-
-    def usable(self, x):
-        return self.ypre is not None and tuple(x.shape) == self.out_shape and x.is_cuda
-
-
+# ---- module-level switches (the per-Sequential ones -- fuse, fuse_pool, fuse_stats, fuse_eval -- are FusedSequential's attributes) ----
+ENABLED = True          # module-wide switch (tests compare the fused against the stock evaluation)
 # The BatchNorm backward reduction riding in the next conv's input-gradient epilogue.  OFF by default: it removes the 2-read
 # reduction kernels (-2.4 ms per VGG16 step) but the input-gradient kernels pay the HBM time of the extra reads in an epilogue
 # that nothing hides (+0.28 ms per layer); interleaved in-process A/B (tools/step_ab.py): 184.6 ms with it, 183.8 ms without.
@@ -41,43 +25,76 @@ ENABLE_BWD_HINT = False
 # The BatchNorm backward APPLY pass riding in the next conv's Winograd weight-gradient kernel (MFMA-bound, HBM mostly idle: the loads are
 # requested four k-steps ahead and every element is done once).  The library switch CPG_NO_WW_RIDER turns it off per process.
 ENABLE_WGRAD_RIDER = True
+RELU_BYTE_MASK = True   # relu(bn(x) + res): the forward leaves the ReLU mask as one byte per four outputs for the backward
+FUSE_STEM = True        # conv(<= 3 -> 64 channels, 3x3 s1 p1) -> BatchNorm2d -> ReLU: the conv output is never written (cpg_stem_bn_*)
+FUSE_STEM_WGRAD = True  # ... and its weight gradient inside the BatchNorm backward's apply pass (cpg_stem_bn_relu_bwd_wgrad)
+FUSE_SKIP_ADD = True    # residual blocks: the identity branch's gradient is added in conv1's input-gradient epilogue
+
+
+def _batch_stats(stats, nbt, N, C, HW, eps, momentum, running_mean, running_var, training, device):
+    """(mean, invstd, counter still to bump) a fused BatchNorm forward normalises with:
+      eval                        the running statistics;
+      training, `stats` given     finalised from the producing conv's [C][tiles][2] partial sums, the running statistics updated
+                                  (cpg_bn_stats_finalize) -- and `nbt`, the layer's num_batches_tracked, bumped in the same launch when
+                                  it is a one-element int64 HIP tensor (cpg_bn_stats_finalize_count: stock torch spends one `add<long>`
+                                  launch per layer on it, 53 per ResNet-50 step);
+      training, no `stats`        two empty vectors for the layer's own kernel to fill.
+    The Function bumps a counter that comes back (not None) with _count() after its kernels."""
+    if not training:
+        return running_mean, torch.rsqrt(running_var + eps), nbt
+    mean = torch.empty(C, dtype=torch.float32, device=device)
+    invstd = torch.empty(C, dtype=torch.float32, device=device)
+    if stats is not None:
+        args = (_lib.dptr(stats, name='bn partial sums'), stats.shape[1], N, C, HW, float(eps), float(momentum),
+                _lib.dptr(running_mean, name='running_mean'), _lib.dptr(running_var, name='running_var'), _lib.dptr(mean), _lib.dptr(invstd))
+        if nbt is not None and running_mean is not None and nbt.is_cuda and nbt.dtype == torch.int64 and nbt.numel() == 1:
+            _lib.call('cpg_bn_stats_finalize_count', *args, _lib.dptr(nbt, torch.int64, 'num_batches_tracked'), _lib.stream_ptr())
+            nbt = None
+        else:
+            _lib.call('cpg_bn_stats_finalize', *args, _lib.stream_ptr())
+    return mean, invstd, nbt
+
+
+def _count(nbt):
+    """nn.BatchNorm2d's `num_batches_tracked += 1` of a training-mode forward, where no kernel of the layer took it along."""
+    if nbt is not None:
+        nbt.add_(1)
+
+
+def _bn_args(bn):
+    """(what every fused BatchNorm Function takes after its input: parameters, running statistics, eps, momentum, training;
+    training; the counter a training-mode forward bumps, or None)."""
+    training = bn.training or not bn.track_running_stats
+    rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
+    nbt = bn.num_batches_tracked if (training and bn.track_running_stats) else None
+    return (bn.weight, bn.bias, rm, rv, bn.eps, bn.momentum, training), training, nbt
 
 
 class _BnReluFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, training, relu, stats=None, hint=None):
+    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, training, relu, stats=None, hint=None, nbt=None):
         x = x.contiguous()
         N, C = x.shape[0], x.shape[1]
         HW = x.numel() // (N * C)
         L = _lib.lib()
         y = torch.empty_like(x)
         s = _lib.stream_ptr()
-        if training and stats is not None:
-            # the producing conv already accumulated the partial sums: finalize, then the apply pass alone
-            mean, invstd = _finalize_stats(stats, N, C, HW, eps, momentum, running_mean, running_var, x.device)
-            rc = L.cpg_bn_relu_fwd_eval(_lib.dptr(x, name='input'), _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(mean),
-                                        _lib.dptr(invstd), _lib.dptr(y), N, C, HW, int(relu), s)
-            _lib.check('cpg_bn_relu_fwd_eval', rc)
-        elif training:
-            mean = torch.empty(C, dtype=torch.float32, device=x.device)
-            invstd = torch.empty(C, dtype=torch.float32, device=x.device)
+        mean, invstd, nbt = _batch_stats(stats, nbt, N, C, HW, eps, momentum, running_mean, running_var, training, x.device)
+        if training and stats is None:
             ws, nb = _lib.workspace(L.cpg_bn_workspace_bytes(N, C, HW), x.device)
-            rc = L.cpg_bn_relu_fwd_train(_lib.dptr(x, name='input'), _lib.dptr(gamma, name='bn.weight'), _lib.dptr(beta, name='bn.bias'),
-                                         float(eps), float(momentum), _lib.dptr(running_mean, name='running_mean'),
-                                         _lib.dptr(running_var, name='running_var'), _lib.dptr(mean), _lib.dptr(invstd),
-                                         _lib.dptr(y), N, C, HW, int(relu), _lib.dptr(ws), nb, s)
-            _lib.check('cpg_bn_relu_fwd_train', rc)
+            _lib.call('cpg_bn_relu_fwd_train', _lib.dptr(x, name='input'), _lib.dptr(gamma, name='bn.weight'), _lib.dptr(beta, name='bn.bias'),
+                      float(eps), float(momentum), _lib.dptr(running_mean, name='running_mean'), _lib.dptr(running_var, name='running_var'),
+                      _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(y), N, C, HW, int(relu), _lib.dptr(ws), nb, s)
         else:
-            mean = running_mean
-            invstd = torch.rsqrt(running_var + eps)
-            rc = L.cpg_bn_relu_fwd_eval(_lib.dptr(x, name='input'), _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(mean),
-                                        _lib.dptr(invstd), _lib.dptr(y), N, C, HW, int(relu), s)
-            _lib.check('cpg_bn_relu_fwd_eval', rc)
+            # eval, or the producing conv already accumulated the partial sums: the apply pass alone
+            _lib.call('cpg_bn_relu_fwd_eval', _lib.dptr(x, name='input'), _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(mean),
+                      _lib.dptr(invstd), _lib.dptr(y), N, C, HW, int(relu), s)
+        _count(nbt)
         ctx.save_for_backward(x, gamma, beta, mean, invstd)
         ctx.cfg = (N, C, HW, bool(relu), bool(training))
         ctx.hint = None
         if hint is not None and relu and training:
-            hint.ypre, hint.gamma, hint.beta, hint.mean, hint.invstd, hint.out_shape = x, gamma, beta, mean, invstd, tuple(y.shape)
+            hint.fill(x, gamma, beta, mean, invstd, y.shape)
             ctx.hint = hint
         return y
 
@@ -87,69 +104,28 @@ class _BnReluFn(torch.autograd.Function):
         N, C, HW, relu, training = ctx.cfg
         gy = gy.contiguous()
         L = _lib.lib()
-        hint, ctx.hint = ctx.hint, None                  # (the hint only lives for one backward pass: drop its tensors afterwards)
+        hint, ctx.hint = ctx.hint, None
+        partials = None
         if hint is not None:
-            hint.ypre = hint.gamma = hint.beta = hint.mean = hint.invstd = hint.out_shape = None
-            gz, result, hint.gz, hint.result = hint.gz, hint.result, None, None
-            if result is not None and gz is not None and gz.data_ptr() == gy.data_ptr() and gz.shape == gy.shape and relu and training:
+            result = hint.take(gy)
+            if result is not None:
                 # the consumer conv's weight-gradient kernel already ran this whole backward on exactly this gradient tensor
-                return (result[0], result[1], result[2]) + (None,) * 8
+                return tuple(result) + (None,) * 9
+            partials, hint.partials = hint.partials, None
         gx = torch.empty_like(x)
         dgamma = torch.empty_like(gamma)
         dbeta = torch.empty_like(beta)
         ws, nb = _lib.workspace(L.cpg_bn_workspace_bytes(N, C, HW), x.device)
-        if hint is not None and hint.partials is not None:
+        if partials is not None:
             # the consumer conv's input-gradient kernel already masked gy by the ReLU and reduced it per (channel, tile)
-            rc = L.cpg_bn_bwd_from_partials(_lib.dptr(hint.partials), hint.tiles, _lib.dptr(x), _lib.dptr(gy, name='grad_output'),
-                                            _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(gx),
-                                            _lib.dptr(dgamma), _lib.dptr(dbeta), N, C, HW, _lib.dptr(ws), nb, _lib.stream_ptr())
-            _lib.check('cpg_bn_bwd_from_partials', rc)
-            hint.partials = None
-            return gx, dgamma, dbeta, None, None, None, None, None, None, None, None
-        rc = L.cpg_bn_relu_bwd(_lib.dptr(x), _lib.dptr(gy, name='grad_output'), _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(mean),
-                               _lib.dptr(invstd), _lib.dptr(gx), _lib.dptr(dgamma), _lib.dptr(dbeta), N, C, HW, int(relu),
-                               int(training), _lib.dptr(ws), nb, _lib.stream_ptr())
-        _lib.check('cpg_bn_relu_bwd', rc)
-        return gx, dgamma, dbeta, None, None, None, None, None, None, None, None
-
-
-_tls = threading.local()
-
-
-def _count_batch(bn):
-    """nn.BatchNorm2d's `num_batches_tracked += 1` of a training-mode forward, handed to the kernel that finalises this layer's batch
-    statistics (cpg_bn_stats_finalize_count bumps the counter in the same launch: stock torch spends one `add<long>` launch per layer on
-    it, 53 per ResNet-50 step).  _settle_count() right behind the fused call does the plain add when no such kernel took it."""
-    _tls.nbt = bn.num_batches_tracked
-
-
-def _settle_count():
-    nbt = getattr(_tls, 'nbt', None)
-    if nbt is not None:
-        _tls.nbt = None
-        nbt.add_(1)
-
-
-def _finalize_stats(stats, N, C, HW, eps, momentum, running_mean, running_var, device):
-    """mean / invstd (+ running statistics update, + the pending num_batches_tracked bump) from a conv's [C][tiles][2] partial sums
-    (cpg_bn_stats_finalize / cpg_bn_stats_finalize_count)."""
-    L = _lib.lib()
-    mean = torch.empty(C, dtype=torch.float32, device=device)
-    invstd = torch.empty(C, dtype=torch.float32, device=device)
-    nbt = getattr(_tls, 'nbt', None)
-    if nbt is not None and running_mean is not None and nbt.is_cuda and nbt.dtype == torch.int64 and nbt.numel() == 1:
-        _tls.nbt = None
-        rc = L.cpg_bn_stats_finalize_count(_lib.dptr(stats, name='bn partial sums'), stats.shape[1], N, C, HW, float(eps), float(momentum),
-                                           _lib.dptr(running_mean, name='running_mean'), _lib.dptr(running_var, name='running_var'),
-                                           _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(nbt, torch.int64, 'num_batches_tracked'),
-                                           _lib.stream_ptr())
-        _lib.check('cpg_bn_stats_finalize_count', rc)
-        return mean, invstd
-    rc = L.cpg_bn_stats_finalize(_lib.dptr(stats, name='bn partial sums'), stats.shape[1], N, C, HW, float(eps), float(momentum),
-                                 _lib.dptr(running_mean, name='running_mean'), _lib.dptr(running_var, name='running_var'),
-                                 _lib.dptr(mean), _lib.dptr(invstd), _lib.stream_ptr())
-    _lib.check('cpg_bn_stats_finalize', rc)
-    return mean, invstd
+            _lib.call('cpg_bn_bwd_from_partials', _lib.dptr(partials), hint.tiles, _lib.dptr(x), _lib.dptr(gy, name='grad_output'),
+                      _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(gx), _lib.dptr(dgamma),
+                      _lib.dptr(dbeta), N, C, HW, _lib.dptr(ws), nb, _lib.stream_ptr())
+        else:
+            _lib.call('cpg_bn_relu_bwd', _lib.dptr(x), _lib.dptr(gy, name='grad_output'), _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(mean),
+                      _lib.dptr(invstd), _lib.dptr(gx), _lib.dptr(dgamma), _lib.dptr(dbeta), N, C, HW, int(relu), int(training),
+                      _lib.dptr(ws), nb, _lib.stream_ptr())
+        return (gx, dgamma, dbeta) + (None,) * 9
 
 
 class _BnAddReluFn(torch.autograd.Function):
@@ -157,39 +133,27 @@ class _BnAddReluFn(torch.autograd.Function):
     BN backward kernels, and the masked gradient itself for the residual."""
 
     @staticmethod
-    def forward(ctx, x, res, gamma, beta, running_mean, running_var, eps, momentum, training, stats=None):
+    def forward(ctx, x, res, gamma, beta, running_mean, running_var, eps, momentum, training, stats=None, nbt=None):
         x, res = x.contiguous(), res.contiguous()
         N, C = x.shape[0], x.shape[1]
         HW = x.numel() // (N * C)
         L = _lib.lib()
         y = torch.empty_like(x)
-        apply_only = not training
-        if training and stats is not None:
-            # the producing conv's epilogue already accumulated the partial sums (cpg_conv2d_fwd_bnstats): finalize + apply pass
-            mean, invstd = _finalize_stats(stats, N, C, HW, eps, momentum, running_mean, running_var, x.device)
-            ws, nb = None, 0
-            apply_only = True
-        elif training:
-            mean = torch.empty(C, dtype=torch.float32, device=x.device)
-            invstd = torch.empty(C, dtype=torch.float32, device=x.device)
-            ws, nb = _lib.workspace(L.cpg_bn_workspace_bytes(N, C, HW), x.device)
-        else:
-            mean, invstd = running_mean, torch.rsqrt(running_var + eps)
-            ws, nb = None, 0
+        # (partial sums from the producing conv's epilogue, cpg_conv2d_fwd_bnstats: finalize + apply pass, as in eval mode)
+        apply_only = not training or stats is not None
+        mean, invstd, nbt = _batch_stats(stats, nbt, N, C, HW, eps, momentum, running_mean, running_var, training, x.device)
+        ws, nb = (None, 0) if apply_only else _lib.workspace(L.cpg_bn_workspace_bytes(N, C, HW), x.device)
         # the backward's ReLU mask as one byte per four outputs, written by the forward pass (the backward then does not re-read y)
         mask = None
         nmask = L.cpg_bn_add_relu_mask_bytes(N, C, HW) if (RELU_BYTE_MASK and any(ctx.needs_input_grad)) else 0
         if nmask and x.data_ptr() % 16 == 0 and res.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0:
             mask = torch.empty(nmask, dtype=torch.uint8, device=x.device)
-        rc = L.cpg_bn_add_relu_fwd(_lib.dptr(x, name='input'), _lib.dptr(res, name='residual'), _lib.dptr(gamma), _lib.dptr(beta),
-                                   float(eps), float(momentum), _lib.dptr(None if apply_only else running_mean),
-                                   _lib.dptr(None if apply_only else running_var), _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(y),
-                                   N, C, HW, int(not apply_only), _lib.dptr(ws), nb, _lib.stream_ptr(), _lib.dptr(mask, torch.uint8))
-        _lib.check('cpg_bn_add_relu_fwd', rc)
-        if mask is not None:
-            ctx.save_for_backward(x, mask, gamma, beta, mean, invstd)
-        else:
-            ctx.save_for_backward(x, y, gamma, beta, mean, invstd)
+        _lib.call('cpg_bn_add_relu_fwd', _lib.dptr(x, name='input'), _lib.dptr(res, name='residual'), _lib.dptr(gamma), _lib.dptr(beta),
+                  float(eps), float(momentum), _lib.dptr(None if apply_only else running_mean),
+                  _lib.dptr(None if apply_only else running_var), _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(y),
+                  N, C, HW, int(not apply_only), _lib.dptr(ws), nb, _lib.stream_ptr(), _lib.dptr(mask, torch.uint8))
+        _count(nbt)
+        ctx.save_for_backward(x, y if mask is None else mask, gamma, beta, mean, invstd)
         ctx.has_mask = mask is not None
         ctx.cfg = (N, C, HW, bool(training))
         return y
@@ -207,69 +171,61 @@ class _BnAddReluFn(torch.autograd.Function):
         gz = torch.empty_like(x)                       # gy * [y > 0]: the residual branch's gradient, written by the reduction pass
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
         ws, nb = _lib.workspace(L.cpg_bn_workspace_bytes(N, C, HW), x.device)
-        rc = L.cpg_bn_add_relu_bwd(_lib.dptr(x), _lib.dptr(y), _lib.dptr(gy, name='grad_output'), _lib.dptr(gamma), _lib.dptr(beta),
-                                   _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(gx), _lib.dptr(gz), _lib.dptr(dgamma), _lib.dptr(dbeta),
-                                   N, C, HW, int(training), _lib.dptr(ws), nb, _lib.stream_ptr(), _lib.dptr(mask, torch.uint8))
-        _lib.check('cpg_bn_add_relu_bwd', rc)
-        return gx, gz, dgamma, dbeta, None, None, None, None, None, None
+        _lib.call('cpg_bn_add_relu_bwd', _lib.dptr(x), _lib.dptr(y), _lib.dptr(gy, name='grad_output'), _lib.dptr(gamma), _lib.dptr(beta),
+                  _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(gx), _lib.dptr(gz), _lib.dptr(dgamma), _lib.dptr(dbeta),
+                  N, C, HW, int(training), _lib.dptr(ws), nb, _lib.stream_ptr(), _lib.dptr(mask, torch.uint8))
+        return (gx, gz, dgamma, dbeta) + (None,) * 7
+
+
+def _pool_backward(name, ctx, gp):
+    """The backward shared by both BatchNorm2d -> ReLU -> MaxPool2d Functions (cpg_bn_relu_pool_bwd / cpg_bn_relu_pool3_bwd)."""
+    x, gamma, beta, mean, invstd = ctx.saved_tensors
+    N, C, H, W = x.shape
+    gp = gp.contiguous()
+    gx = torch.empty_like(x)
+    dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
+    ws, nb = _lib.workspace(_lib.lib().cpg_bn_workspace_bytes(N, C, H * W), x.device)
+    _lib.call(name, _lib.dptr(x), _lib.dptr(gp, name='grad_output'), _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(mean),
+              _lib.dptr(invstd), _lib.dptr(gx), _lib.dptr(dgamma), _lib.dptr(dbeta), N, C, H, W, int(ctx.training), _lib.dptr(ws), nb,
+              _lib.stream_ptr())
+    return (gx, dgamma, dbeta) + (None,) * 7
 
 
 class _BnReluPoolFn(torch.autograd.Function):
     """BatchNorm2d -> ReLU -> MaxPool2d(2, 2); only the pooled tensor is written."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, training, stats=None):
+    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, training, stats=None, nbt=None):
         x = x.contiguous()
         N, C, H, W = x.shape
         L = _lib.lib()
         y = torch.empty((N, C, H // 2, W // 2), dtype=torch.float32, device=x.device)
         compute_stats = training and stats is None
-        if training and stats is not None:
-            mean, invstd = _finalize_stats(stats, N, C, H * W, eps, momentum, running_mean, running_var, x.device)
-        elif training:
-            mean = torch.empty(C, dtype=torch.float32, device=x.device)
-            invstd = torch.empty(C, dtype=torch.float32, device=x.device)
-        else:
-            mean, invstd = running_mean, torch.rsqrt(running_var + eps)
+        mean, invstd, nbt = _batch_stats(stats, nbt, N, C, H * W, eps, momentum, running_mean, running_var, training, x.device)
         ws, nb = _lib.workspace(L.cpg_bn_workspace_bytes(N, C, H * W), x.device)
-        rc = L.cpg_bn_relu_pool_fwd(_lib.dptr(x, name='input'), _lib.dptr(gamma, name='bn.weight'), _lib.dptr(beta, name='bn.bias'),
-                                    float(eps), float(momentum), _lib.dptr(running_mean if compute_stats else None),
-                                    _lib.dptr(running_var if compute_stats else None), _lib.dptr(mean), _lib.dptr(invstd),
-                                    _lib.dptr(y), N, C, H, W, int(compute_stats), _lib.dptr(ws), nb, _lib.stream_ptr())
-        _lib.check('cpg_bn_relu_pool_fwd', rc)
+        _lib.call('cpg_bn_relu_pool_fwd', _lib.dptr(x, name='input'), _lib.dptr(gamma, name='bn.weight'), _lib.dptr(beta, name='bn.bias'),
+                  float(eps), float(momentum), _lib.dptr(running_mean if compute_stats else None),
+                  _lib.dptr(running_var if compute_stats else None), _lib.dptr(mean), _lib.dptr(invstd),
+                  _lib.dptr(y), N, C, H, W, int(compute_stats), _lib.dptr(ws), nb, _lib.stream_ptr())
+        _count(nbt)
         ctx.save_for_backward(x, gamma, beta, mean, invstd)
         ctx.training = bool(training)
         return y
 
     @staticmethod
     def backward(ctx, gp):
-        x, gamma, beta, mean, invstd = ctx.saved_tensors
-        N, C, H, W = x.shape
-        gp = gp.contiguous()
-        L = _lib.lib()
-        gx = torch.empty_like(x)
-        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-        ws, nb = _lib.workspace(L.cpg_bn_workspace_bytes(N, C, H * W), x.device)
-        rc = L.cpg_bn_relu_pool_bwd(_lib.dptr(x), _lib.dptr(gp, name='grad_output'), _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(mean),
-                                    _lib.dptr(invstd), _lib.dptr(gx), _lib.dptr(dgamma), _lib.dptr(dbeta), N, C, H, W,
-                                    int(ctx.training), _lib.dptr(ws), nb, _lib.stream_ptr())
-        _lib.check('cpg_bn_relu_pool_bwd', rc)
-        return gx, dgamma, dbeta, None, None, None, None, None, None
+        return _pool_backward('cpg_bn_relu_pool_bwd', ctx, gp)
 
 
 class _BnReluPool3Fn(torch.autograd.Function):
     """BatchNorm2d -> ReLU -> MaxPool2d(3, 2, 1) (the ResNet stem's tail); only the pooled tensor is written."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, training, stats):
+    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, training, stats, nbt=None):
         x = x.contiguous()
         N, C, H, W = x.shape
-        L = _lib.lib()
-        if training and stats is not None:
-            mean, invstd = _finalize_stats(stats, N, C, H * W, eps, momentum, running_mean, running_var, x.device)
-        elif training:
-            mean = torch.empty(C, dtype=torch.float32, device=x.device)
-            invstd = torch.empty(C, dtype=torch.float32, device=x.device)
+        mean, invstd, nbt = _batch_stats(stats, nbt, N, C, H * W, eps, momentum, running_mean, running_var, training, x.device)
+        if training and stats is None:
             # (the producing conv has no fused-statistics kernel -- narrow test nets: torch's own reduction for the statistics)
             var, mu = torch.var_mean(x, dim=(0, 2, 3), unbiased=False)
             mean.copy_(mu)
@@ -278,37 +234,42 @@ class _BnReluPool3Fn(torch.autograd.Function):
             with torch.no_grad():
                 running_mean.mul_(1 - momentum).add_(mu, alpha=momentum)
                 running_var.mul_(1 - momentum).add_(var * (n / max(n - 1, 1)), alpha=momentum)
-        else:
-            mean, invstd = running_mean, torch.rsqrt(running_var + eps)
         y = torch.empty((N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
-        rc = L.cpg_bn_relu_pool3_fwd(_lib.dptr(x, name='input'), _lib.dptr(gamma, name='bn.weight'), _lib.dptr(beta, name='bn.bias'),
-                                     _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(y), N, C, H, W, _lib.stream_ptr())
-        _lib.check('cpg_bn_relu_pool3_fwd', rc)
+        _lib.call('cpg_bn_relu_pool3_fwd', _lib.dptr(x, name='input'), _lib.dptr(gamma, name='bn.weight'), _lib.dptr(beta, name='bn.bias'),
+                  _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(y), N, C, H, W, _lib.stream_ptr())
+        _count(nbt)
         ctx.save_for_backward(x, gamma, beta, mean, invstd)
         ctx.training = bool(training)
         return y
 
     @staticmethod
     def backward(ctx, gp):
-        x, gamma, beta, mean, invstd = ctx.saved_tensors
-        N, C, H, W = x.shape
-        gp = gp.contiguous()
-        L = _lib.lib()
-        gx = torch.empty_like(x)
-        dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
-        ws, nb = _lib.workspace(L.cpg_bn_workspace_bytes(N, C, H * W), x.device)
-        rc = L.cpg_bn_relu_pool3_bwd(_lib.dptr(x), _lib.dptr(gp, name='grad_output'), _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(mean),
-                                     _lib.dptr(invstd), _lib.dptr(gx), _lib.dptr(dgamma), _lib.dptr(dbeta), N, C, H, W,
-                                     int(ctx.training), _lib.dptr(ws), nb, _lib.stream_ptr())
-        _lib.check('cpg_bn_relu_pool3_bwd', rc)
-        return gx, dgamma, dbeta, None, None, None, None, None, None
+        return _pool_backward('cpg_bn_relu_pool3_bwd', ctx, gp)
+
+
+def _is_pool(m, kernel, stride, padding):
+    """`m` is a plain nn.MaxPool2d(kernel, stride, padding)."""
+    def pair(v):
+        return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    return (isinstance(m, nn.MaxPool2d) and pair(m.kernel_size) == (kernel, kernel) and pair(m.stride) == (stride, stride)
+            and pair(m.padding) == (padding, padding) and pair(m.dilation) == (1, 1) and not m.ceil_mode and not m.return_indices)
+
+
+def _is_pool2(m):
+    return _is_pool(m, 2, 2, 0)
 
 
 def _is_pool3(m):
-    def pair(v):
-        return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
-    return (isinstance(m, nn.MaxPool2d) and pair(m.kernel_size) == (3, 3) and pair(m.stride) == (2, 2) and pair(m.padding) == (1, 1)
-            and pair(m.dilation) == (1, 1) and not m.ceil_mode and not m.return_indices)
+    return _is_pool(m, 3, 2, 1)
+
+
+def _stats_from_conv(bn, fuse_stats, x=None, need_grad=False):
+    """`bn` can take its batch statistics from the epilogue of the conv in front of it: a training-mode, stat-tracking, affine
+    BatchNorm2d with an exponential-average momentum, under the caller's `fuse_stats` switch (FusedSequential's -- an instance's in
+    its forward, the class's in the free functions).  x: the conv's input, where the site has not yet established that it is on the
+    device; need_grad: the site only fuses under autograd."""
+    return (fuse_stats and isinstance(bn, nn.BatchNorm2d) and bn.training and bn.track_running_stats and bn.affine
+            and bn.momentum is not None and (x is None or x.is_cuda) and (not need_grad or torch.is_grad_enabled()))
 
 
 def conv_bn_act_pool(conv, bn, act, pool, x):
@@ -317,35 +278,18 @@ def conv_bn_act_pool(conv, bn, act, pool, x):
     y, stats = _conv_with_stats(conv, bn, x)
     if (ENABLED and FusedSequential.fuse_pool and type(act) is nn.ReLU and _is_pool3(pool) and fusable(bn, y) and bn.track_running_stats
             and _lib.lib().cpg_bn_relu_pool3_supported(int(y.shape[2]), int(y.shape[3]))):
-        training = bn.training
-        if training and bn.num_batches_tracked is not None:
-            _count_batch(bn)
-        out = _BnReluPool3Fn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, training,
-                                   stats if training else None)
-        _settle_count()
-        return out
+        args, training, nbt = _bn_args(bn)
+        return _BnReluPool3Fn.apply(y, *args, stats if training else None, nbt)
     if stats is not None and type(act) is nn.ReLU and fusable(bn, y):
         return pool(bn_relu(y, bn, relu=True, stats=stats))
     return pool(bn_act(bn, act, y))
 
 
-def _is_pool2(m):
-    def pair(v):
-        return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
-    return (isinstance(m, nn.MaxPool2d) and pair(m.kernel_size) == (2, 2) and pair(m.stride) == (2, 2) and pair(m.padding) == (0, 0)
-            and pair(m.dilation) == (1, 1) and not m.ceil_mode and not m.return_indices)
-
-
 def bn_relu_pool(x, bn, stats=None):
     """max_pool2d(relu(bn(x)), 2, 2) with `bn` an nn.BatchNorm2d module; H and W must be even.  `stats`: partial sums
     of x from the conv that produced it (SharableConv2d.forward_with_bn_stats)."""
-    training = bn.training or not bn.track_running_stats
-    rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
-    if training and bn.track_running_stats and bn.num_batches_tracked is not None:
-        _count_batch(bn)
-    out = _BnReluPoolFn.apply(x, bn.weight, bn.bias, rm, rv, bn.eps, bn.momentum, training, stats if training else None)
-    _settle_count()
-    return out
+    args, training, nbt = _bn_args(bn)
+    return _BnReluPoolFn.apply(x, *args, stats if training else None, nbt)
 
 
 def fusable(bn, x):
@@ -358,14 +302,8 @@ def fusable(bn, x):
 def bn_relu(x, bn, relu=True, stats=None, hint=None):
     """y = relu(bn(x)) with `bn` an nn.BatchNorm2d module (its buffers are updated as torch would).  hint: a BnBwdHint when the
     caller hands y to exactly one masked 3x3 conv (FusedSequential does)."""
-    training = bn.training or not bn.track_running_stats
-    rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
-    if training and bn.track_running_stats and bn.num_batches_tracked is not None:
-        _count_batch(bn)
-    out = _BnReluFn.apply(x, bn.weight, bn.bias, rm, rv, bn.eps, bn.momentum, training, relu,
-                          stats if (training and rm is not None) else None, hint if training else None)
-    _settle_count()
-    return out
+    args, training, nbt = _bn_args(bn)
+    return _BnReluFn.apply(x, *args, relu, stats if (training and bn.track_running_stats) else None, hint if training else None, nbt)
 
 
 class _PReluFn(torch.autograd.Function):
@@ -374,14 +312,13 @@ class _PReluFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, res=None, bias_sink=None):
-        ctx.bias_sink = bias_sink        # layers.BiasGradSink of the biased conv that produced x (its only consumer is this PReLU)
+        ctx.bias_sink = bias_sink        # BiasGradSink of the biased conv that produced x (its only consumer is this PReLU)
         N, C = x.shape[0], x.shape[1]
         HW = x.numel() // max(N * C, 1)
         y = torch.empty_like(x)
         if x.numel():
-            rc = _lib.lib().cpg_prelu_fwd(_lib.dptr(x, name='input'), _lib.dptr(res, name='residual'), _lib.dptr(weight, name='prelu.weight'),
-                                          _lib.dptr(y), N, C, HW, weight.numel(), _lib.stream_ptr())
-            _lib.check('cpg_prelu_fwd', rc)
+            _lib.call('cpg_prelu_fwd', _lib.dptr(x, name='input'), _lib.dptr(res, name='residual'), _lib.dptr(weight, name='prelu.weight'),
+                      _lib.dptr(y), N, C, HW, weight.numel(), _lib.stream_ptr())
         ctx.save_for_backward(x, weight)
         ctx.has_res = res is not None
         return y
@@ -395,31 +332,39 @@ class _PReluFn(torch.autograd.Function):
             return torch.zeros_like(x), torch.zeros_like(weight), (gy if ctx.has_res else None), None
         N, C = x.shape[0], x.shape[1]
         HW = x.numel() // (N * C)
-        L = _lib.lib()
-        ws, nb = _lib.workspace(L.cpg_prelu_workspace_bytes(N, C, HW), x.device)
+        ws, nb = _lib.workspace(_lib.lib().cpg_prelu_workspace_bytes(N, C, HW), x.device)
         gx = torch.empty_like(x)
         gw = torch.empty_like(weight)
+        head = (_lib.dptr(x), _lib.dptr(gy), _lib.dptr(weight), _lib.dptr(gx), _lib.dptr(gw))
+        tail = (N, C, HW, weight.numel(), _lib.dptr(ws), nb, _lib.stream_ptr())
         if sink is not None:
             gbias = torch.empty(C, dtype=torch.float32, device=x.device)
-            _lib.check('cpg_prelu_bwd_bias', L.cpg_prelu_bwd_bias(_lib.dptr(x), _lib.dptr(gy), _lib.dptr(weight), _lib.dptr(gx), _lib.dptr(gw),
-                                                                  _lib.dptr(gbias), N, C, HW, weight.numel(), _lib.dptr(ws), nb, _lib.stream_ptr()))
+            _lib.call('cpg_prelu_bwd_bias', *head, _lib.dptr(gbias), *tail)
             sink.gb = gbias
         else:
-            _lib.check('cpg_prelu_bwd', L.cpg_prelu_bwd(_lib.dptr(x), _lib.dptr(gy), _lib.dptr(weight), _lib.dptr(gx), _lib.dptr(gw),
-                                                        N, C, HW, weight.numel(), _lib.dptr(ws), nb, _lib.stream_ptr()))
+            _lib.call('cpg_prelu_bwd', *head, *tail)
         return gx, gw, (gy if ctx.has_res else None), None
+
+
+def _dense4d(t):
+    return t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()
+
+
+def _prelu_fits(mod, x, conv=None):
+    """The eligibility that prelu, conv_prelu and conv_prelu_skip share: a plain nn.PReLU with one slope, or one per channel, on a HIP
+    tensor; with `conv` (the masked conv in front of it) also that the pair runs under autograd, in fp32, as ONE conv call (a grouped
+    conv runs one call per group: each computes its own bias gradient)."""
+    return (ENABLED and type(mod) is nn.PReLU and x.is_cuda and mod.weight.numel() in (1, x.shape[1] if conv is None else conv.out_channels)
+            and (conv is None or (torch.is_grad_enabled() and conv._math() == 'fp32' and getattr(conv, 'groups', 1) == 1)))
 
 
 def conv_prelu(conv, mod, x, res=None):
     """mod(conv(x)) [+ res] for SphereNet's biased conv -> PReLU pairs (models/spherenet.py:203-247): the PReLU's backward pass also
     delivers the conv's bias gradient (the per-channel sum of the gradient it writes), so the conv's backward runs no bias reduction."""
-    from .layers import BiasGradSink
-    if (ENABLED and type(mod) is nn.PReLU and x.is_cuda and getattr(conv, 'bias', None) is not None and torch.is_grad_enabled()
-            and mod.weight.numel() in (1, conv.out_channels) and conv._math() == 'fp32'
-            and getattr(conv, 'groups', 1) == 1):           # (a grouped conv runs one call per group: each computes its own bias gradient)
+    if getattr(conv, 'bias', None) is not None and _prelu_fits(mod, x, conv):
         sink = BiasGradSink()
         y = conv(x, bias_sink=sink)
-        if y.dtype == torch.float32 and y.dim() == 4 and y.is_contiguous() and (res is None or (res.shape == y.shape and res.is_contiguous())):
+        if _dense4d(y) and (res is None or (res.shape == y.shape and res.is_contiguous())):
             return _PReluFn.apply(y, mod.weight, res, sink)
         return prelu(mod, y, res)
     return prelu(mod, conv(x), res)
@@ -430,12 +375,10 @@ def conv_prelu_skip(conv, mod, x):
     x feeds this conv and the unit's sum.  The returned x is routed through the conv's autograd node, which then receives BOTH gradients
     of x and adds the sum's in its input-gradient epilogue (cpg_conv2d_dgrad_add: the two-wave Winograd kernel's ADD instances) instead of
     leaving a separate add kernel to autograd.  Falls back to (conv_prelu(conv, mod, x), x) when the pair does not qualify."""
-    from .layers import BiasGradSink
-    if (ENABLED and type(mod) is nn.PReLU and x.is_cuda and torch.is_grad_enabled() and x.requires_grad and mod.weight.numel() in (1, conv.out_channels)
-            and conv._math() == 'fp32' and getattr(conv, 'groups', 1) == 1 and x.dim() == 4 and x.is_contiguous()):
+    if x.requires_grad and _prelu_fits(mod, x, conv) and x.dim() == 4 and x.is_contiguous():
         sink = BiasGradSink() if getattr(conv, 'bias', None) is not None else None
         y, _, skip = conv.forward_with_skip(x, bias_sink=sink, want_stats=False)
-        if y.dtype == torch.float32 and y.is_contiguous():
+        if _dense4d(y):                  # (a conv output: always 4-D)
             return _PReluFn.apply(y, mod.weight, None, sink), skip
         return prelu(mod, y), skip
     return conv_prelu(conv, mod, x), x
@@ -443,16 +386,11 @@ def conv_prelu_skip(conv, mod, x):
 
 def prelu(mod, x, res=None):
     """mod(x) [+ res] for an nn.PReLU module (models/spherenet.py); HIP kernels when the tensor qualifies."""
-    if (ENABLED and type(mod) is nn.PReLU and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
-            and mod.weight.numel() in (1, x.shape[1]) and (res is None or (res.shape == x.shape and res.is_contiguous()
-                                                                            and res.dtype == torch.float32 and res.is_cuda))):
+    if (_dense4d(x) and _prelu_fits(mod, x)
+            and (res is None or (res.shape == x.shape and res.is_contiguous() and res.dtype == torch.float32 and res.is_cuda))):
         return _PReluFn.apply(x, mod.weight, res)
     y = mod(x)
     return y if res is None else res + y
-
-
-RELU_BYTE_MASK = True   # relu(bn(x) + res): the forward leaves the ReLU mask as one byte per four outputs for the backward
-ENABLED = True      # module-wide switch (tests compare the fused against the stock evaluation)
 
 
 def bn_act(bn, act, x):
@@ -468,13 +406,8 @@ def bn_add_act(bn, act, x, res, stats=None):
     """act(bn(x) + res), the tail of a residual block; fused when `act` is a plain nn.ReLU and `bn` qualifies.  stats: partial sums
     of x from the conv that produced it (conv_bn_add_act)."""
     if ENABLED and type(act) is nn.ReLU and fusable(bn, x) and bn.track_running_stats and res.shape == x.shape:
-        training = bn.training
-        if training and bn.num_batches_tracked is not None:
-            _count_batch(bn)
-        out = _BnAddReluFn.apply(x, res, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, bn.momentum, training,
-                                 stats if training else None)
-        _settle_count()
-        return out
+        args, training, nbt = _bn_args(bn)
+        return _BnAddReluFn.apply(x, res, *args, stats if training else None, nbt)
     out = bn(x)
     out = out + res
     return act(out)
@@ -483,8 +416,7 @@ def bn_add_act(bn, act, x, res, stats=None):
 def _conv_with_stats(conv, bn, x):
     """(conv(x), partial sums for `bn` or None): the conv's epilogue accumulates the BatchNorm statistics when the pair qualifies
     (a masked conv with a fused-statistics kernel feeding a training-mode, stat-tracking BatchNorm2d)."""
-    if (ENABLED and FusedSequential.fuse_stats and hasattr(conv, 'forward_with_bn_stats') and isinstance(bn, nn.BatchNorm2d) and bn.training
-            and bn.track_running_stats and bn.affine and bn.momentum is not None and x.is_cuda and torch.is_grad_enabled()):
+    if ENABLED and hasattr(conv, 'forward_with_bn_stats') and _stats_from_conv(bn, FusedSequential.fuse_stats, x, need_grad=True):
         return conv.forward_with_bn_stats(x)
     return conv(x), None
 
@@ -497,37 +429,31 @@ def conv_bn_act(conv, bn, act, x):
     return bn_act(bn, act, y)
 
 
-FUSE_STEM_WGRAD = True     # ... and its weight gradient inside the BatchNorm backward's apply pass (cpg_stem_bn_relu_bwd_wgrad)
-FUSE_STEM = True           # conv(<= 3 -> 64 channels, 3x3 s1 p1) -> BatchNorm2d -> ReLU: the conv output is never written (cpg_stem_bn_*)
-
-
 class _StemConvBnReluFn(torch.autograd.Function):
     """z = relu(bn(conv(x))) for the network stem (models/vgg.py:137-141) with the conv output recomputed in every pass that needs it
     instead of stored: forward = statistics pass + BatchNorm/ReLU pass over the image, backward = reduction pass + apply pass over gz
     (each recomputes conv(x)), then the stem's weight gradient from the resulting gy.  The image gets no gradient."""
 
     @staticmethod
-    def forward(ctx, x, weight, pm, thr, gamma, beta, running_mean, running_var, eps, momentum):
-        from .layers import _conv_desc
+    def forward(ctx, x, weight, pm, thr, gamma, beta, running_mean, running_var, eps, momentum, nbt=None):
         x = x.contiguous()
         w = weight.contiguous()
         p = None if pm is None else pm.contiguous()
         d = _conv_desc(x.shape, w.shape, (1, 1), (1, 1), (1, 1), 1)
-        L = _lib.lib()
         s = _lib.stream_ptr()
+        thr = float(thr)
         N, K, H, W = x.shape[0], w.shape[0], x.shape[2], x.shape[3]
-        tiles = L.cpg_stem_bn_tiles(ctypes.byref(d))
+        tiles = _lib.lib().cpg_stem_bn_tiles(ctypes.byref(d))
         stats = torch.empty((K, tiles, 2), dtype=torch.float32, device=x.device)
-        rc = L.cpg_stem_bn_stats(ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'), _lib.dptr(p, name='piggymask'),
-                                 float(thr), None, _lib.dptr(stats), stats.numel() * 4, s)
-        _lib.check('cpg_stem_bn_stats', rc)
-        mean, invstd = _finalize_stats(stats, N, K, H * W, eps, momentum, running_mean, running_var, x.device)
+        _lib.call('cpg_stem_bn_stats', ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'), _lib.dptr(p, name='piggymask'),
+                  thr, None, _lib.dptr(stats), stats.numel() * 4, s)
+        mean, invstd, nbt = _batch_stats(stats, nbt, N, K, H * W, eps, momentum, running_mean, running_var, True, x.device)
         z = torch.empty((N, K, H, W), dtype=torch.float32, device=x.device)
-        rc = L.cpg_stem_bn_relu_fwd(ctypes.byref(d), _lib.dptr(x), _lib.dptr(w), _lib.dptr(p), float(thr), None, _lib.dptr(gamma, name='bn.weight'),
-                                    _lib.dptr(beta, name='bn.bias'), _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(z), s)
-        _lib.check('cpg_stem_bn_relu_fwd', rc)
+        _lib.call('cpg_stem_bn_relu_fwd', ctypes.byref(d), _lib.dptr(x), _lib.dptr(w), _lib.dptr(p), thr, None, _lib.dptr(gamma, name='bn.weight'),
+                  _lib.dptr(beta, name='bn.bias'), _lib.dptr(mean), _lib.dptr(invstd), _lib.dptr(z), s)
+        _count(nbt)
         ctx.save_for_backward(x, w, p, gamma, beta, mean, invstd)
-        ctx.desc, ctx.thr, ctx.tiles = d, float(thr), tiles
+        ctx.desc, ctx.thr, ctx.tiles = d, thr, tiles
         return z
 
     @staticmethod
@@ -541,12 +467,10 @@ class _StemConvBnReluFn(torch.autograd.Function):
         partials = torch.empty((K, tiles, 2), dtype=torch.float32, device=x.device)
         args = (ctypes.byref(d), _lib.dptr(x), _lib.dptr(w), _lib.dptr(p), thr, None, _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(mean),
                 _lib.dptr(invstd))
-        rc = L.cpg_stem_bn_relu_bwd_reduce(*args, _lib.dptr(gz, name='grad_output'), _lib.dptr(partials), partials.numel() * 4, s)
-        _lib.check('cpg_stem_bn_relu_bwd_reduce', rc)
+        _lib.call('cpg_stem_bn_relu_bwd_reduce', *args, _lib.dptr(gz, name='grad_output'), _lib.dptr(partials), partials.numel() * 4, s)
         dgamma, dbeta = torch.empty_like(gamma), torch.empty_like(beta)
         coef = torch.empty(2 * K, dtype=torch.float32, device=x.device)
-        rc = L.cpg_bn_bwd_finalize_partials(_lib.dptr(partials), tiles, N, K, H * W, _lib.dptr(dgamma), _lib.dptr(dbeta), _lib.dptr(coef), s)
-        _lib.check('cpg_bn_bwd_finalize_partials', rc)
+        _lib.call('cpg_bn_bwd_finalize_partials', _lib.dptr(partials), tiles, N, K, H * W, _lib.dptr(dgamma), _lib.dptr(dbeta), _lib.dptr(coef), s)
         gw = gpm = None
         if ctx.needs_input_grad[1] or (p is not None and ctx.needs_input_grad[2]):
             gw = torch.empty_like(w)
@@ -554,26 +478,23 @@ class _StemConvBnReluFn(torch.autograd.Function):
             if FUSE_STEM_WGRAD:
                 # gy is contracted with the image patch in the pass that forms it (never written)
                 ws, nbytes = _lib.workspace(L.cpg_stem_bn_wgrad_workspace(ctypes.byref(d)), x.device)
-                rc = L.cpg_stem_bn_relu_bwd_wgrad(*args, _lib.dptr(coef), _lib.dptr(gz), _lib.dptr(gw), _lib.dptr(gpm), _lib.dptr(ws), nbytes, s)
-                _lib.check('cpg_stem_bn_relu_bwd_wgrad', rc)
+                _lib.call('cpg_stem_bn_relu_bwd_wgrad', *args, _lib.dptr(coef), _lib.dptr(gz), _lib.dptr(gw), _lib.dptr(gpm), _lib.dptr(ws),
+                          nbytes, s)
             else:
                 gy = torch.empty((N, K, H, W), dtype=torch.float32, device=x.device)
-                rc = L.cpg_stem_bn_relu_bwd_apply(*args, _lib.dptr(coef), _lib.dptr(gz), _lib.dptr(gy), s)
-                _lib.check('cpg_stem_bn_relu_bwd_apply', rc)
+                _lib.call('cpg_stem_bn_relu_bwd_apply', *args, _lib.dptr(coef), _lib.dptr(gz), _lib.dptr(gy), s)
                 ws, nbytes = _lib.workspace(L.cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
-                rc = L.cpg_conv2d_wgrad(ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), _lib.dptr(w), _lib.dptr(p), thr, _lib.dptr(gw), _lib.dptr(gpm),
-                                        None, _lib.dptr(ws), nbytes, s)
-                _lib.check('cpg_conv2d_wgrad', rc)
-        return None, gw, gpm, None, dgamma, dbeta, None, None, None, None
+                _lib.call('cpg_conv2d_wgrad', ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), _lib.dptr(w), _lib.dptr(p), thr, _lib.dptr(gw),
+                          _lib.dptr(gpm), None, _lib.dptr(ws), nbytes, s)
+        return (None, gw, gpm, None, dgamma, dbeta) + (None,) * 5
 
 
 def stem_conv_bn_relu(conv, bn, x):
     """relu(bn(conv(x))) through _StemConvBnReluFn when the triple qualifies (a bias-free masked 3x3 s1 p1 stem in fp32 feeding a
     training-mode, stat-tracking BatchNorm2d, an input that needs no gradient), else None."""
-    from .layers import _conv_desc
-    if not (ENABLED and FUSE_STEM and FusedSequential.fuse and FusedSequential.fuse_stats and hasattr(conv, 'forward_with_bn_stats')
-            and isinstance(bn, nn.BatchNorm2d) and bn.training and bn.track_running_stats and bn.affine and bn.momentum is not None
-            and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and torch.is_grad_enabled() and not x.requires_grad
+    if not (ENABLED and FUSE_STEM and FusedSequential.fuse and hasattr(conv, 'forward_with_bn_stats')
+            and _stats_from_conv(bn, FusedSequential.fuse_stats, x, need_grad=True)
+            and x.dim() == 4 and x.dtype == torch.float32 and not x.requires_grad
             and conv.bias is None and conv._math() == 'fp32' and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1)
             and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and conv.groups == 1 and x.shape[0] > 0
             and x.shape[1] == conv.weight.shape[1] and bn.weight.dtype == torch.float32):
@@ -581,15 +502,8 @@ def stem_conv_bn_relu(conv, bn, x):
     d = _conv_desc(x.shape, conv.weight.shape, (1, 1), (1, 1), (1, 1), 1)
     if not _lib.lib().cpg_stem_bn_supported(ctypes.byref(d)):
         return None
-    if bn.num_batches_tracked is not None:
-        _count_batch(bn)
-    out = _StemConvBnReluFn.apply(x, conv.weight, conv.piggymask, conv.info['threshold'], bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                  bn.eps, bn.momentum)
-    _settle_count()
-    return out
-
-
-FUSE_SKIP_ADD = True       # residual blocks: the identity branch's gradient is added in conv1's input-gradient epilogue
+    return _StemConvBnReluFn.apply(x, conv.weight, conv.piggymask, conv.info['threshold'], bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                   bn.eps, bn.momentum, bn.num_batches_tracked)
 
 
 def conv_bn_act_skip(conv, bn, act, x):
@@ -600,9 +514,8 @@ def conv_bn_act_skip(conv, bn, act, x):
             and conv._math() == 'fp32' and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.in_channels % 16 == 0
             and conv.out_channels % 16 == 0):
         y, stats, skip = conv.forward_with_skip(x)
-        use_stats = (stats is not None and FusedSequential.fuse_stats and isinstance(bn, nn.BatchNorm2d) and bn.training and bn.track_running_stats
-                     and bn.affine and bn.momentum is not None)
-        if use_stats and (act is None or type(act) is nn.ReLU) and fusable(bn, y):
+        if (stats is not None and _stats_from_conv(bn, FusedSequential.fuse_stats) and (act is None or type(act) is nn.ReLU)
+                and fusable(bn, y)):
             return bn_relu(y, bn, relu=act is not None, stats=stats), skip
         return bn_act(bn, act, y), skip
     return conv_bn_act(conv, bn, act, x), x
@@ -626,67 +539,78 @@ class FusedSequential(nn.Sequential):
     #                         {4 * (4-channel input chunks up to the last live one), output blocks skipped by the dead-channel test}
 
     def forward(self, input):
+        """Every step looks at the next four modules (None past the end) and at
+            input   the activation so far,
+            stats   its partial sums, when the module that produced it was asked for them,
+            hint    the BnBwdHint for the conv that consumes it, when it came out of a fused BatchNorm -> ReLU,
+        and either declines (None) or returns (modules consumed, input, stats, hint).  _conv takes whatever the others leave."""
         mods = list(self._modules.values())
-        i, n = 0, len(mods)
-        stats = None            # partial sums of `input`, when the module that produced it was asked for them
-        hint = None             # BnBwdHint for the conv that consumes `input`, when `input` came out of a fused BatchNorm -> ReLU
+        n = len(mods)
+        mods += [None] * 3
+        steps = (self._bn_relu, self._lone_bn, self._conv_bn_relu_eval, self._stem, self._conv)
+        i, stats, hint = 0, None, None
         while i < n:
-            m = mods[i]
-            if (self.fuse and ENABLED and i + 1 < n and isinstance(m, nn.BatchNorm2d) and isinstance(mods[i + 1], nn.ReLU)
-                    and fusable(m, input)):
-                if (self.fuse_pool and i + 2 < n and _is_pool2(mods[i + 2]) and input.shape[2] % 2 == 0
-                        and input.shape[3] % 2 == 0 and m.track_running_stats):
-                    input = bn_relu_pool(input, m, stats)
-                    i += 3
-                    hint = None
-                else:
-                    # BatchNorm -> ReLU feeding a masked conv directly: let that conv's input-gradient kernel do this
-                    # BatchNorm's backward reduction (only this Sequential knows that nothing else reads the activation)
-                    nxt2 = mods[i + 2] if i + 2 < n else None
-                    hint = BnBwdHint(ENABLE_BWD_HINT, ENABLE_WGRAD_RIDER) if (
-                        (ENABLE_BWD_HINT or ENABLE_WGRAD_RIDER) and m.training and torch.is_grad_enabled()
-                        and hasattr(nxt2, 'forward_with_bn_stats')) else None
-                    input = bn_relu(input, m, relu=True, stats=stats, hint=hint)
-                    i += 2
-                stats = None
-                continue
-            if self.fuse and ENABLED and isinstance(m, nn.BatchNorm2d) and fusable(m, input):
-                input = bn_relu(input, m, relu=False, stats=stats)       # a lone BatchNorm2d (ResNet shortcut: conv1x1 -> BN)
-                i += 1
-                stats = None
-                continue
-            nxt = mods[i + 1] if i + 1 < n else None
-            if (self.fuse and self.fuse_eval and ENABLED and not torch.is_grad_enabled() and hasattr(m, 'forward_bn_eval')
-                    and isinstance(nxt, nn.BatchNorm2d) and not nxt.training and nxt.track_running_stats and nxt.affine
-                    and i + 2 < n and isinstance(mods[i + 2], nn.ReLU) and input.is_cuda
-                    and not (self.fuse_pool and i + 3 < n and _is_pool2(mods[i + 3]))):
-                # (a following MaxPool2d keeps the conv + fused BN/ReLU/pool pair: same HBM traffic, and the un-pooled
-                # activation is never written either way)
-                st = None
-                if self.skip_log is not None:
-                    st = torch.zeros(2, dtype=torch.int32, device=input.device)
-                y = m.forward_bn_eval(input, nxt, relu=True, skip_stats=st)
-                if y is not None:
-                    if st is not None:
-                        self.skip_log.append(st)
-                    input, stats = y, None
-                    i += 3
-                    continue
-            if (self.fuse and FUSE_STEM and i + 2 < n and isinstance(nxt, nn.BatchNorm2d) and type(mods[i + 2]) is nn.ReLU
-                    and hasattr(m, 'forward_with_bn_stats') and getattr(m, 'in_channels', 99) <= 3
-                    and not (self.fuse_pool and i + 3 < n and _is_pool2(mods[i + 3]))):
-                z = stem_conv_bn_relu(m, nxt, input)         # the stem: conv -> BatchNorm2d -> ReLU without ever writing the conv output
-                if z is not None:
-                    input, stats, hint = z, None, None
-                    i += 3
-                    continue
-            if (self.fuse and self.fuse_stats and ENABLED and hasattr(m, 'forward_with_bn_stats') and isinstance(nxt, nn.BatchNorm2d)
-                    and nxt.training and nxt.track_running_stats and nxt.affine and nxt.momentum is not None and input.is_cuda):
-                input, stats = m.forward_with_bn_stats(input, bn_hint=hint)
-            elif hint is not None and hasattr(m, 'forward_with_bn_stats'):
-                input, stats = m(input, bn_hint=hint), None
-            else:
-                input, stats = m(input), None
-            hint = None
-            i += 1
+            window = mods[i:i + 4]
+            for step in steps:
+                done = step(window, input, stats, hint)
+                if done is not None:
+                    break
+            k, input, stats, hint = done
+            i += k
         return input
+
+    def _bn_relu(self, mods, input, stats, hint):
+        """BatchNorm2d -> ReLU, with the MaxPool2d(2, 2) behind them when the plane is even."""
+        m, relu, nxt2, _ = mods
+        if not (self.fuse and ENABLED and isinstance(m, nn.BatchNorm2d) and isinstance(relu, nn.ReLU) and fusable(m, input)):
+            return None
+        if self.fuse_pool and _is_pool2(nxt2) and input.shape[2] % 2 == 0 and input.shape[3] % 2 == 0 and m.track_running_stats:
+            return 3, bn_relu_pool(input, m, stats), None, None
+        # BatchNorm -> ReLU feeding a masked conv directly: let that conv's backward do part of this BatchNorm's backward
+        # (only this Sequential knows that nothing else reads the activation)
+        hint = BnBwdHint(ENABLE_BWD_HINT, ENABLE_WGRAD_RIDER) if (
+            (ENABLE_BWD_HINT or ENABLE_WGRAD_RIDER) and m.training and torch.is_grad_enabled()
+            and hasattr(nxt2, 'forward_with_bn_stats')) else None
+        return 2, bn_relu(input, m, relu=True, stats=stats, hint=hint), None, hint
+
+    def _lone_bn(self, mods, input, stats, hint):
+        """A BatchNorm2d with no ReLU behind it (ResNet shortcut: conv1x1 -> BN)."""
+        m = mods[0]
+        if not (self.fuse and ENABLED and isinstance(m, nn.BatchNorm2d) and fusable(m, input)):
+            return None
+        return 1, bn_relu(input, m, relu=False, stats=stats), None, hint
+
+    def _conv_bn_relu_eval(self, mods, input, stats, hint):
+        """Inference: conv -> BatchNorm2d(eval) -> ReLU as one kernel.  (A following MaxPool2d keeps the conv + fused BN/ReLU/pool pair:
+        same HBM traffic, and the un-pooled activation is never written either way.)"""
+        m, bn, relu, nxt3 = mods
+        if not (self.fuse and self.fuse_eval and ENABLED and not torch.is_grad_enabled() and hasattr(m, 'forward_bn_eval')
+                and isinstance(bn, nn.BatchNorm2d) and not bn.training and bn.track_running_stats and bn.affine
+                and isinstance(relu, nn.ReLU) and input.is_cuda and not (self.fuse_pool and _is_pool2(nxt3))):
+            return None
+        st = None if self.skip_log is None else torch.zeros(2, dtype=torch.int32, device=input.device)
+        y = m.forward_bn_eval(input, bn, relu=True, skip_stats=st)
+        if y is None:
+            return None
+        if st is not None:
+            self.skip_log.append(st)
+        return 3, y, None, hint
+
+    def _stem(self, mods, input, stats, hint):
+        """The stem: conv -> BatchNorm2d -> ReLU without ever writing the conv output (a following MaxPool2d keeps the pair, as above)."""
+        m, bn, relu, nxt3 = mods
+        if not (self.fuse and FUSE_STEM and isinstance(bn, nn.BatchNorm2d) and type(relu) is nn.ReLU
+                and hasattr(m, 'forward_with_bn_stats') and getattr(m, 'in_channels', 99) <= 3
+                and not (self.fuse_pool and _is_pool2(nxt3))):
+            return None
+        z = stem_conv_bn_relu(m, bn, input)
+        return None if z is None else (3, z, None, None)
+
+    def _conv(self, mods, input, stats, hint):
+        """Any other module; a masked conv in front of a training-mode BatchNorm2d also returns that BatchNorm's partial sums."""
+        m, nxt = mods[0], mods[1]
+        if self.fuse and ENABLED and hasattr(m, 'forward_with_bn_stats') and _stats_from_conv(nxt, self.fuse_stats, input):
+            return (1,) + tuple(m.forward_with_bn_stats(input, bn_hint=hint)) + (None,)
+        if hint is not None and hasattr(m, 'forward_with_bn_stats'):
+            return 1, m(input, bn_hint=hint), None, None
+        return 1, m(input), None, None

@@ -47,9 +47,8 @@ class Binarizer(torch.autograd.Function):
     def forward(ctx, inputs, threshold):
         out = torch.empty_like(inputs, memory_format=torch.contiguous_format)
         src = inputs.contiguous()
-        rc = _lib.lib().cpg_binarize_mask_weight(None, _lib.dptr(src, name='inputs'), float(threshold),
-                                                 _lib.dptr(out), src.numel(), _lib.stream_ptr())
-        _lib.check('cpg_binarize_mask_weight', rc)
+        _lib.call('cpg_binarize_mask_weight', None, _lib.dptr(src, name='inputs'), float(threshold), _lib.dptr(out), src.numel(),
+                  _lib.stream_ptr())
         return out
 
     @staticmethod
@@ -76,30 +75,20 @@ def _out_hw(d):
 
 # CPG_PACK_CACHE=0: every conv call packs its own weight operand (the behaviour up to round 5; A/B switch)
 PACK_CACHE = os.environ.get('CPG_PACK_CACHE', '1') not in ('0', '')
-_PACK_BYTES = {}
 
 
-def _pack_bytes(L, d, which):
-    """cpg_conv2d_pack_bytes per (shape, pass), memoised: the answer depends on the shape and the library options only
-    (cpg_amd._lib.set_option clears the table)."""
-    key = (d.N, d.C, d.H, d.W, d.K, d.R, d.S, d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w, d.groups, which)
-    v = _PACK_BYTES.get(key)
-    if v is None:
-        v = _PACK_BYTES[key] = int(L.cpg_conv2d_pack_bytes(ctypes.byref(d), which))
-    return v
-
-
-def _with_packed(L, pk, call):
-    """Run `call()` -- ONE conv entry point -- with the calling thread armed to stream the packed operand `pk` (None: plain call).
-    The library disarms itself inside that entry point; an exception raised on the way there (an argument that does not convert: a CPU
-    or non-fp32 tensor) disarms here, so that no LATER call of this thread can pick up an operand that was not meant for it."""
+def _call_packed(pk, name, *args):
+    """_lib.call of ONE conv entry point with the calling thread armed to stream the packed operand `pk` (None: plain call).
+    The library disarms itself inside that entry point; an exception raised on the way there (an argument that does not convert)
+    disarms here (once more, harmlessly, when the entry point itself failed), so that no LATER call of this thread can pick up an
+    operand that was not meant for it."""
     if pk is None:
-        return call()
-    _lib.check('cpg_conv2d_use_packed', L.cpg_conv2d_use_packed(_lib.dptr(pk), pk.numel() * 4))
+        return _lib.call(name, *args)
+    _lib.call('cpg_conv2d_use_packed', _lib.dptr(pk), pk.numel() * 4)
     try:
-        return call()
+        _lib.call(name, *args)
     except BaseException:
-        L.cpg_conv2d_use_packed(None, 0)
+        _lib.lib().cpg_conv2d_use_packed(None, 0)
         raise
 
 
@@ -112,8 +101,50 @@ class BiasGradSink(object):
     def __init__(self):
         self.gb = None
 
+    def take(self):
+        gb, self.gb = self.gb, None
+        return gb
 
-def _bn_bwd_rider(L, hint, gz, s):
+
+class BnBwdHint(object):
+    """Link between a training-mode BatchNorm2d -> ReLU (fused_bn._BnReluFn) and the masked 3x3 conv that is the ONLY consumer of its
+    output: the conv's input-gradient kernel does the BatchNorm's backward reduction in its epilogue (cpg_conv2d_dgrad_bnbwd) and
+    leaves the partial sums in `partials` / `tiles` for _BnReluFn.backward (cpg_bn_bwd_from_partials) -- `epilogue` --, or the conv's
+    weight-gradient kernel runs the BatchNorm's backward apply pass as a side job (cpg_conv2d_wgrad_attach_bn_bwd) and store()s
+    (gx, dgamma, dbeta), computed from the gradient tensor `gz` -- `rider`.  One hint per forward pass."""
+    __slots__ = ('ypre', 'gamma', 'beta', 'mean', 'invstd', 'partials', 'tiles', 'out_shape', 'epilogue', 'rider', 'gz', 'result')
+
+    def __init__(self, epilogue=True, rider=False):
+        self.partials, self.tiles = None, 0
+        self.epilogue, self.rider = epilogue, rider
+        self.clear()
+
+    def fill(self, ypre, gamma, beta, mean, invstd, out_shape):
+        """_BnReluFn.forward: the BatchNorm's input, parameters and batch statistics, and the shape of the activation it handed on."""
+        self.ypre, self.gamma, self.beta, self.mean, self.invstd, self.out_shape = ypre, gamma, beta, mean, invstd, tuple(out_shape)
+
+    def usable(self, x):
+        """The conv's input `x` is the activation this hint was filled for."""
+        return self.ypre is not None and tuple(x.shape) == self.out_shape and x.is_cuda
+
+    def store(self, gz, result):
+        """The rider's (gx, dgamma, dbeta) and the gradient tensor they were computed from."""
+        self.gz, self.result = gz, result
+
+    def take(self, gy):
+        """_BnReluFn.backward: the stored result if it was computed from exactly the tensor `gy`, else None.  Either way the hint
+        only lives for one backward pass: its tensors are dropped."""
+        gz, result = self.gz, self.result
+        self.clear()
+        if result is not None and gz is not None and gz.data_ptr() == gy.data_ptr() and gz.shape == gy.shape:
+            return result
+        return None
+
+    def clear(self):
+        self.ypre = self.gamma = self.beta = self.mean = self.invstd = self.out_shape = self.gz = self.result = None
+
+
+def _bn_bwd_rider(hint, gz, s):
     """Reduce + finalize of the BatchNorm -> ReLU backward behind `hint` on gz (cpg_bn_relu_bwd's first two launches) and the buffers of
     its apply pass: (ypre, gy, dgamma, dbeta, table), or None when the tensors do not suit the rider (alignment, 4 | HW, 2 GiB)."""
     y = hint.ypre
@@ -124,11 +155,10 @@ def _bn_bwd_rider(L, hint, gz, s):
     gyb = torch.empty_like(y)
     dgamma, dbeta = torch.empty_like(hint.gamma), torch.empty_like(hint.beta)
     table = torch.empty((C, 8), dtype=torch.float32, device=y.device)
-    wsb, nbb = _lib.workspace(L.cpg_bn_workspace_bytes(N, C, HW), y.device)
-    rc = L.cpg_bn_relu_bwd_reduce(_lib.dptr(y), _lib.dptr(gz, name='grad_output'), _lib.dptr(hint.gamma), _lib.dptr(hint.beta),
-                                  _lib.dptr(hint.mean), _lib.dptr(hint.invstd), _lib.dptr(dgamma), _lib.dptr(dbeta), _lib.dptr(table),
-                                  N, C, HW, _lib.dptr(wsb), nbb, s)
-    _lib.check('cpg_bn_relu_bwd_reduce', rc)
+    wsb, nbb = _lib.workspace(_lib.lib().cpg_bn_workspace_bytes(N, C, HW), y.device)
+    _lib.call('cpg_bn_relu_bwd_reduce', _lib.dptr(y), _lib.dptr(gz, name='grad_output'), _lib.dptr(hint.gamma), _lib.dptr(hint.beta),
+              _lib.dptr(hint.mean), _lib.dptr(hint.invstd), _lib.dptr(dgamma), _lib.dptr(dbeta), _lib.dptr(table), N, C, HW,
+              _lib.dptr(wsb), nbb, s)
     return y, gyb, dgamma, dbeta, table
 
 
@@ -137,15 +167,16 @@ class _MaskedConv2dFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, pm, bias, thr, stride, padding, dilation, groups, bn_stats=False, math='fp32', bn_hint=None, bias_sink=None):
-        # bn_hint (fused_bn.BnBwdHint or None): `x` is relu(bn(ypre)) of the layer below and nothing else consumes it -- the
-        # input-gradient kernel may then do that BatchNorm's backward reduction in its epilogue (cpg_conv2d_dgrad_bnbwd, hint.epilogue),
-        # or the weight-gradient kernel that BatchNorm's backward apply pass as a side job (cpg_conv2d_wgrad_attach_bn_bwd, hint.rider)
+        """bn_stats: also return the per-(channel, pixel tile) {sum, sum of squares} of y that the kernel accumulates
+        in its epilogue (cpg_conv2d_fwd_bnstats) -- a second, non-differentiable output, empty when the shape has
+        no fused-statistics kernel.
+        bn_hint (BnBwdHint or None): `x` is relu(bn(ypre)) of the layer below and nothing else consumes it -- the
+        input-gradient kernel may then do that BatchNorm's backward reduction in its epilogue (cpg_conv2d_dgrad_bnbwd, hint.epilogue),
+        or the weight-gradient kernel that BatchNorm's backward apply pass as a side job (cpg_conv2d_wgrad_attach_bn_bwd, hint.rider).
+        bias_sink (BiasGradSink or None): the activation behind this conv delivers the bias gradient."""
         ctx.bn_hint = bn_hint
         ctx.set_materialize_grads(False)         # (no zero-filled "gradient" tensor for the statistics output on every backward)
-        ctx.bias_sink = bias_sink if bias is not None else None     # BiasGradSink: the activation behind this conv delivers the bias gradient
-        """bn_stats: also return the per-(channel, pixel tile) {sum, sum of squares} of y that the kernel accumulates
-        in its epilogue (cpg_conv2d_fwd_bnstats) -- a second, non-differentiable output, or None when the shape has
-        no fused-statistics kernel."""
+        ctx.bias_sink = bias_sink if bias is not None else None
         if x.dim() != 4 or x.shape[1] != weight.shape[1] * groups:
             raise RuntimeError('SharableConv2d: input %s does not match weight %s (groups=%d)'
                                % (tuple(x.shape), tuple(weight.shape), groups))
@@ -158,64 +189,46 @@ class _MaskedConv2dFn(torch.autograd.Function):
             raise RuntimeError('SharableConv2d: kernel larger than padded input')
         y = torch.empty((d.N, d.K, oh, ow), dtype=torch.float32, device=x.device)
         L = _lib.lib()
+        thr = float(thr)
         ctx.empty = d.N == 0 or d.K == 0
-        ctx.bf16 = ctx.x3 = False
+        ctx.bf16 = not ctx.empty and math in ('bf16', 'bf16x3') and bool(L.cpg_conv2d_bf16_supported(ctypes.byref(d)))
+        ctx.x3 = math == 'bf16x3'
+        ctx.packed_dgrad = stats = None
         if ctx.empty:                   # an empty batch (or no output channels) is legal for F.conv2d: empty output, zero parameter gradients
             _lib.dptr(x, name='input'), _lib.dptr(w, name='weight')            # still no CPU / dtype fallback
-            ctx.save_for_backward(x, w, p)
-            ctx.desc, ctx.thr, ctx.has_bias = d, float(thr), bias is not None
-            if not bn_stats:
-                return y
-            stats = torch.empty(0, dtype=torch.float32, device=x.device)
-            ctx.mark_non_differentiable(stats)
-            return y, stats
-        ctx.bf16 = math in ('bf16', 'bf16x3') and bool(L.cpg_conv2d_bf16_supported(ctypes.byref(d)))
-        ctx.x3 = math == 'bf16x3'
-        if ctx.bf16:
+        elif ctx.bf16:
             # opt-in bf16 MFMA forward (no fused BatchNorm statistics on this path: the BatchNorm runs its own pass)
             ws, nbytes = _lib.workspace(L.cpg_conv2d_bf16_workspace_bytes(ctypes.byref(d)), x.device)
-            fwd = L.cpg_conv2d_fwd_bf16x3 if ctx.x3 else L.cpg_conv2d_fwd_bf16
-            rc = fwd(ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'),
-                     _lib.dptr(p, name='piggymask'), float(thr), _lib.dptr(bias, name='bias'), _lib.dptr(y),
-                     _lib.dptr(ws), nbytes, _lib.stream_ptr())
-            _lib.check('cpg_conv2d_fwd_bf16', rc)
-            ctx.save_for_backward(x, w, p)
-            ctx.desc, ctx.thr, ctx.has_bias = d, float(thr), bias is not None
-            if not bn_stats:
-                return y
-            stats = torch.empty(0, dtype=torch.float32, device=x.device)
-            ctx.mark_non_differentiable(stats)
-            return y, stats
-        ws, nbytes = _lib.workspace(L.cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
-        tiles = L.cpg_conv2d_bnstats_tiles(ctypes.byref(d)) if bn_stats else 0
-        stats = None
-        # Packed weight operands (cpg_conv2d_pack, ABI 3): when this layer's forward AND its input gradient stream one, both are produced
-        # here in ONE launch; the forward takes its own now, the input gradient's rides in ctx until backward (the weights cannot change in
-        # between: autograd's version check on the saved w / pm guards exactly that).  One launch instead of two per layer and step.
-        ctx.packed_dgrad = pk_f = None
-        if PACK_CACHE and ctx.needs_input_grad[0]:
-            uses_bnbwd = bn_hint is not None and bn_hint.epilogue and L.cpg_conv2d_dgrad_bnbwd_tiles(ctypes.byref(d)) > 0      # (that launch packs for the direct kernels)
-            nb_f, nb_d = _pack_bytes(L, d, 2 if tiles > 0 else 0), (0 if uses_bnbwd else _pack_bytes(L, d, 1))
-            if nb_f and nb_d:
-                pk_f = torch.empty(nb_f // 4, dtype=torch.float32, device=x.device)
-                pk_d = torch.empty(nb_d // 4, dtype=torch.float32, device=x.device)
-                rc = L.cpg_conv2d_pack(ctypes.byref(d), _lib.dptr(w, name='weight'), _lib.dptr(p, name='piggymask'), float(thr),
-                                       2 if tiles > 0 else 0, _lib.dptr(pk_f), nb_f, 1, _lib.dptr(pk_d), nb_d, _lib.stream_ptr())
-                _lib.check('cpg_conv2d_pack', rc)
-                ctx.packed_dgrad = pk_d
-        if tiles > 0:
-            stats = torch.empty((d.K, tiles, 2), dtype=torch.float32, device=x.device)
-            rc = _with_packed(L, pk_f, lambda: L.cpg_conv2d_fwd_bnstats(
-                ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'), _lib.dptr(p, name='piggymask'), float(thr),
-                _lib.dptr(bias, name='bias'), _lib.dptr(y), _lib.dptr(stats), stats.numel() * 4, _lib.dptr(ws), nbytes, _lib.stream_ptr()))
-            _lib.check('cpg_conv2d_fwd_bnstats', rc)
+            _lib.call('cpg_conv2d_fwd_bf16x3' if ctx.x3 else 'cpg_conv2d_fwd_bf16', ctypes.byref(d), _lib.dptr(x, name='input'),
+                      _lib.dptr(w, name='weight'), _lib.dptr(p, name='piggymask'), thr, _lib.dptr(bias, name='bias'), _lib.dptr(y),
+                      _lib.dptr(ws), nbytes, _lib.stream_ptr())
         else:
-            rc = _with_packed(L, pk_f, lambda: L.cpg_conv2d_fwd(
-                ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'), _lib.dptr(p, name='piggymask'), float(thr),
-                _lib.dptr(bias, name='bias'), _lib.dptr(y), _lib.dptr(ws), nbytes, _lib.stream_ptr()))
-            _lib.check('cpg_conv2d_fwd', rc)
+            ws, nbytes = _lib.workspace(L.cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
+            tiles = L.cpg_conv2d_bnstats_tiles(ctypes.byref(d)) if bn_stats else 0
+            # Packed weight operands (cpg_conv2d_pack, ABI 3): when this layer's forward AND its input gradient stream one, both are
+            # produced here in ONE launch; the forward takes its own now, the input gradient's rides in ctx until backward (the weights
+            # cannot change in between: autograd's version check on the saved w / pm guards exactly that).  One launch instead of two
+            # per layer and step.
+            pk_f = None
+            if PACK_CACHE and ctx.needs_input_grad[0]:
+                uses_bnbwd = bn_hint is not None and bn_hint.epilogue and L.cpg_conv2d_dgrad_bnbwd_tiles(ctypes.byref(d)) > 0      # (that launch packs for the direct kernels)
+                nb_f, nb_d = _lib.pack_bytes(d, 2 if tiles > 0 else 0), (0 if uses_bnbwd else _lib.pack_bytes(d, 1))
+                if nb_f and nb_d:
+                    pk_f = torch.empty(nb_f // 4, dtype=torch.float32, device=x.device)
+                    pk_d = torch.empty(nb_d // 4, dtype=torch.float32, device=x.device)
+                    _lib.call('cpg_conv2d_pack', ctypes.byref(d), _lib.dptr(w, name='weight'), _lib.dptr(p, name='piggymask'), thr,
+                              2 if tiles > 0 else 0, _lib.dptr(pk_f), nb_f, 1, _lib.dptr(pk_d), nb_d, _lib.stream_ptr())
+                    ctx.packed_dgrad = pk_d
+            head = (ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'), _lib.dptr(p, name='piggymask'), thr,
+                    _lib.dptr(bias, name='bias'), _lib.dptr(y))
+            if tiles > 0:
+                stats = torch.empty((d.K, tiles, 2), dtype=torch.float32, device=x.device)
+                _call_packed(pk_f, 'cpg_conv2d_fwd_bnstats', *head, _lib.dptr(stats), stats.numel() * 4, _lib.dptr(ws), nbytes,
+                             _lib.stream_ptr())
+            else:
+                _call_packed(pk_f, 'cpg_conv2d_fwd', *head, _lib.dptr(ws), nbytes, _lib.stream_ptr())
         ctx.save_for_backward(x, w, p)
-        ctx.desc, ctx.thr, ctx.has_bias = d, float(thr), bias is not None
+        ctx.desc, ctx.thr, ctx.has_bias = d, thr, bias is not None
         if not bn_stats:
             return y
         if stats is None:
@@ -229,88 +242,92 @@ class _MaskedConv2dFn(torch.autograd.Function):
         epilogue where the shape class has that (cpg_conv2d_dgrad_add), by one add otherwise."""
         if gy is None:                           # the conv's output is unused: only a skip gradient (if any) flows
             return (addend,) + (None,) * 12
-        x, w, p = ctx.saved_tensors
-        d, thr = ctx.desc, ctx.thr
+        x, w, p = saved = ctx.saved_tensors
+        d = ctx.desc
         if ctx.empty:
             # (an empty OUTPUT with a non-empty input -- out_channels == 0 -- still passes a residual branch's gradient through)
             return (addend if addend is not None else torch.zeros_like(x), torch.zeros_like(w), None if p is None else torch.zeros_like(p),
-                    torch.zeros(d.K, dtype=torch.float32, device=x.device) if ctx.has_bias else None, None, None, None, None, None, None,
-                    None, None, None)
+                    torch.zeros(d.K, dtype=torch.float32, device=x.device) if ctx.has_bias else None) + (None,) * 9
         gy = gy.contiguous()
-        L = _lib.lib()
-        s = _lib.stream_ptr()
-        gx = gw = gpm = gb = None
         hint, ctx.bn_hint = ctx.bn_hint, None
-        ws, nbytes = _lib.workspace(L.cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
-        if ctx.needs_input_grad[0] and ctx.bf16:
+        ws = _lib.workspace(_lib.lib().cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
+        gx = _MaskedConv2dFn._input_grad(ctx, saved, gy, hint, addend, ws)
+        gw = gpm = gb = None
+        if ctx.needs_input_grad[1] or (p is not None and ctx.needs_input_grad[2]) or (ctx.has_bias and ctx.needs_input_grad[3]):
+            gw, gpm, gb = _MaskedConv2dFn._weight_grad(ctx, saved, gy, hint, gx, ws)
+        return (gx, gw, gpm, gb) + (None,) * 9
+
+    @staticmethod
+    def _input_grad(ctx, saved, gy, hint, addend, ws):
+        """The input gradient with `addend` added (None when neither is asked for); with hint.epilogue also the partial sums of the
+        BatchNorm backward below, left in the hint."""
+        x, w, p = saved
+        d, thr = ctx.desc, ctx.thr
+        (ws, nbytes), s = ws, _lib.stream_ptr()
+        L = _lib.lib()
+        gx = None
+        if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            ws16, nb16 = _lib.workspace(L.cpg_conv2d_bf16_workspace_bytes(ctypes.byref(d)), x.device)
-            dgrad = L.cpg_conv2d_dgrad_bf16x3 if ctx.x3 else L.cpg_conv2d_dgrad_bf16
-            rc = dgrad(ctypes.byref(d), _lib.dptr(gy, name='grad_output'), _lib.dptr(w), _lib.dptr(p), thr,
-                       _lib.dptr(gx), _lib.dptr(ws16), nb16, s)
-            _lib.check('cpg_conv2d_dgrad_bf16', rc)
-        elif ctx.needs_input_grad[0]:
-            gx = torch.empty_like(x)
-            tiles = L.cpg_conv2d_dgrad_bnbwd_tiles(ctypes.byref(d)) if (hint is not None and hint.epilogue and hint.usable(x)) else 0
-            if tiles > 0:
+            head = (ctypes.byref(d), _lib.dptr(gy, name='grad_output'), _lib.dptr(w), _lib.dptr(p), thr)
+            # (the BatchNorm backward reduction below this conv, where the hint asks for it and the shape has the kernel)
+            tiles = L.cpg_conv2d_dgrad_bnbwd_tiles(ctypes.byref(d)) if (
+                not ctx.bf16 and hint is not None and hint.epilogue and hint.usable(x)) else 0
+            if ctx.bf16:
+                ws16, nb16 = _lib.workspace(L.cpg_conv2d_bf16_workspace_bytes(ctypes.byref(d)), x.device)
+                _lib.call('cpg_conv2d_dgrad_bf16x3' if ctx.x3 else 'cpg_conv2d_dgrad_bf16', *head, _lib.dptr(gx), _lib.dptr(ws16), nb16, s)
+            elif tiles > 0:
                 # gx becomes g * [bn(ypre) > 0] and the BatchNorm's two backward sums come out per (channel, pixel tile)
                 partials = torch.empty((d.C, tiles, 2), dtype=torch.float32, device=x.device)
-                rc = L.cpg_conv2d_dgrad_bnbwd(ctypes.byref(d), _lib.dptr(gy, name='grad_output'), _lib.dptr(w), _lib.dptr(p), thr,
-                                              _lib.dptr(hint.ypre), _lib.dptr(hint.gamma), _lib.dptr(hint.beta), _lib.dptr(hint.mean),
-                                              _lib.dptr(hint.invstd), _lib.dptr(gx), _lib.dptr(partials), partials.numel() * 4,
-                                              _lib.dptr(ws), nbytes, s)
-                _lib.check('cpg_conv2d_dgrad_bnbwd', rc)
+                _lib.call('cpg_conv2d_dgrad_bnbwd', *head, _lib.dptr(hint.ypre), _lib.dptr(hint.gamma), _lib.dptr(hint.beta),
+                          _lib.dptr(hint.mean), _lib.dptr(hint.invstd), _lib.dptr(gx), _lib.dptr(partials), partials.numel() * 4,
+                          _lib.dptr(ws), nbytes, s)
                 hint.partials, hint.tiles = partials, tiles
-            elif addend is not None and L.cpg_conv2d_dgrad_add_supported(ctypes.byref(d)) and addend.shape == x.shape:
-                addend = addend.contiguous()
-                pk, ctx.packed_dgrad = getattr(ctx, 'packed_dgrad', None), None      # (the operand packed at forward time, one-shot)
-                ad = addend
-                rc = _with_packed(L, pk, lambda: L.cpg_conv2d_dgrad_add(
-                    ctypes.byref(d), _lib.dptr(gy, name='grad_output'), _lib.dptr(w), _lib.dptr(p), thr, _lib.dptr(ad, name='skip gradient'),
-                    _lib.dptr(gx), _lib.dptr(ws), nbytes, s))
-                _lib.check('cpg_conv2d_dgrad_add', rc)
-                addend = None
             else:
-                pk, ctx.packed_dgrad = getattr(ctx, 'packed_dgrad', None), None
-                rc = _with_packed(L, pk, lambda: L.cpg_conv2d_dgrad(
-                    ctypes.byref(d), _lib.dptr(gy, name='grad_output'), _lib.dptr(w), _lib.dptr(p), thr, _lib.dptr(gx), _lib.dptr(ws), nbytes, s))
-                _lib.check('cpg_conv2d_dgrad', rc)
+                pk, ctx.packed_dgrad = ctx.packed_dgrad, None      # (the operand packed at forward time, one-shot)
+                if addend is not None and L.cpg_conv2d_dgrad_add_supported(ctypes.byref(d)) and addend.shape == x.shape:
+                    ad = addend.contiguous()
+                    _call_packed(pk, 'cpg_conv2d_dgrad_add', *head, _lib.dptr(ad, name='skip gradient'), _lib.dptr(gx), _lib.dptr(ws),
+                                 nbytes, s)
+                    addend = None
+                else:
+                    _call_packed(pk, 'cpg_conv2d_dgrad', *head, _lib.dptr(gx), _lib.dptr(ws), nbytes, s)
         if addend is not None:                  # (no fused path for this launch)
             gx = addend.clone() if gx is None else gx.add_(addend)
-        if ctx.needs_input_grad[1] or (p is not None and ctx.needs_input_grad[2]) or (ctx.has_bias and ctx.needs_input_grad[3]):
-            gw = torch.empty_like(w)
-            gpm = None if p is None else torch.empty_like(p)
-            gb = torch.empty(d.K, dtype=torch.float32, device=x.device) if ctx.has_bias else None
-            sink, ctx.bias_sink = getattr(ctx, 'bias_sink', None), None
-            given = sink.gb if sink is not None else None
-            if given is not None:                # the PReLU behind this conv already summed gy per channel (cpg_prelu_bwd_bias)
-                sink.gb, gb = None, None
-            rider = None
-            if (hint is not None and hint.rider and not ctx.bf16 and gx is not None and hint.partials is None and hint.usable(x)
-                    and L.cpg_conv2d_wgrad_rider_supported(ctypes.byref(d))):
-                # x = relu(bn(ypre)) and gx is the whole gradient reaching it: that BatchNorm's reduce + finalize now, its apply pass
-                # inside this layer's weight-gradient kernel; _BnReluFn.backward finds the three results in the hint
-                rider = _bn_bwd_rider(L, hint, gx, s)
-            if ctx.bf16 and not ctx.has_bias and L.cpg_conv2d_wgrad_bf16_supported(ctypes.byref(d)):
-                wsw, nbw = _lib.workspace(L.cpg_conv2d_wgrad_bf16_workspace_bytes(ctypes.byref(d)), x.device)
-                wgrad = L.cpg_conv2d_wgrad_bf16x3 if ctx.x3 else L.cpg_conv2d_wgrad_bf16
-                rc = wgrad(ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), _lib.dptr(w), _lib.dptr(p), thr,
-                           _lib.dptr(gw), _lib.dptr(gpm), _lib.dptr(wsw), nbw, s)
-                _lib.check('cpg_conv2d_wgrad_bf16', rc)
-            else:
-                if rider is not None:
-                    ypre, gyb, table = rider[0], rider[1], rider[4]
-                    _lib.check('cpg_conv2d_wgrad_attach_bn_bwd', L.cpg_conv2d_wgrad_attach_bn_bwd(
-                        _lib.dptr(ypre), _lib.dptr(gx), _lib.dptr(gyb), _lib.dptr(table), ypre.shape[0], ypre.shape[1],
-                        ypre.numel() // (ypre.shape[0] * ypre.shape[1])))
-                rc = L.cpg_conv2d_wgrad(ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), _lib.dptr(w), _lib.dptr(p), thr,
-                                        _lib.dptr(gw), _lib.dptr(gpm), _lib.dptr(gb), _lib.dptr(ws), nbytes, s)
-                _lib.check('cpg_conv2d_wgrad', rc)
-                if rider is not None:
-                    hint.gz, hint.result = gx, rider[1:4]
-            if given is not None:
-                gb = given
-        return gx, gw, gpm, gb, None, None, None, None, None, None, None, None, None
+        return gx
+
+    @staticmethod
+    def _weight_grad(ctx, saved, gy, hint, gx, ws):
+        """(gw, gpm, gb); with hint.rider also the whole backward of the BatchNorm -> ReLU below, stored in the hint."""
+        x, w, p = saved
+        d, thr = ctx.desc, ctx.thr
+        (ws, nbytes), s = ws, _lib.stream_ptr()
+        L = _lib.lib()
+        gw = torch.empty_like(w)
+        gpm = None if p is None else torch.empty_like(p)
+        gb = torch.empty(d.K, dtype=torch.float32, device=x.device) if ctx.has_bias else None
+        sink, ctx.bias_sink = ctx.bias_sink, None
+        given = sink.take() if sink is not None else None
+        if given is not None:                # the PReLU behind this conv already summed gy per channel (cpg_prelu_bwd_bias)
+            gb = None
+        rider = None
+        if (hint is not None and hint.rider and not ctx.bf16 and gx is not None and hint.partials is None and hint.usable(x)
+                and L.cpg_conv2d_wgrad_rider_supported(ctypes.byref(d))):
+            # x = relu(bn(ypre)) and gx is the whole gradient reaching it: that BatchNorm's reduce + finalize now, its apply pass
+            # inside this layer's weight-gradient kernel; _BnReluFn.backward takes the three results from the hint
+            rider = _bn_bwd_rider(hint, gx, s)
+        head = (ctypes.byref(d), _lib.dptr(x), _lib.dptr(gy), _lib.dptr(w), _lib.dptr(p), thr, _lib.dptr(gw), _lib.dptr(gpm))
+        if ctx.bf16 and not ctx.has_bias and L.cpg_conv2d_wgrad_bf16_supported(ctypes.byref(d)):
+            wsw, nbw = _lib.workspace(L.cpg_conv2d_wgrad_bf16_workspace_bytes(ctypes.byref(d)), x.device)
+            _lib.call('cpg_conv2d_wgrad_bf16x3' if ctx.x3 else 'cpg_conv2d_wgrad_bf16', *head, _lib.dptr(wsw), nbw, s)
+        else:
+            if rider is not None:
+                ypre, gyb, table = rider[0], rider[1], rider[4]
+                _lib.call('cpg_conv2d_wgrad_attach_bn_bwd', _lib.dptr(ypre), _lib.dptr(gx), _lib.dptr(gyb), _lib.dptr(table), ypre.shape[0],
+                          ypre.shape[1], ypre.numel() // (ypre.shape[0] * ypre.shape[1]))
+            _lib.call('cpg_conv2d_wgrad', *head, _lib.dptr(gb), _lib.dptr(ws), nbytes, s)
+            if rider is not None:
+                hint.store(gx, rider[1:4])
+        return gw, gpm, (given if given is not None else gb)
 
 
 class _MaskedConv2dSkipFn(torch.autograd.Function):
@@ -355,14 +372,10 @@ class _MaskedLinearFn(torch.autograd.Function):
         ctx.empty = batch == 0
         if ctx.empty:                   # F.linear accepts zero rows
             _lib.dptr(x2, name='input'), _lib.dptr(w, name='weight')
-            ctx.save_for_backward(x2, w, p)
-            ctx.thr, ctx.has_bias, ctx.lead = float(thr), bias is not None, lead
-            return y
-        ws, nbytes = _lib.workspace(L.cpg_linear_workspace_bytes(batch, fin, fout), x.device)
-        rc = L.cpg_linear_fwd(_lib.dptr(x2, name='input'), _lib.dptr(w, name='weight'), _lib.dptr(p, name='piggymask'),
-                              float(thr), _lib.dptr(bias, name='bias'), _lib.dptr(y), batch, fin, fout,
-                              _lib.dptr(ws), nbytes, _lib.stream_ptr())
-        _lib.check('cpg_linear_fwd', rc)
+        else:
+            ws, nbytes = _lib.workspace(L.cpg_linear_workspace_bytes(batch, fin, fout), x.device)
+            _lib.call('cpg_linear_fwd', _lib.dptr(x2, name='input'), _lib.dptr(w, name='weight'), _lib.dptr(p, name='piggymask'),
+                      float(thr), _lib.dptr(bias, name='bias'), _lib.dptr(y), batch, fin, fout, _lib.dptr(ws), nbytes, _lib.stream_ptr())
         ctx.save_for_backward(x2, w, p)
         ctx.thr, ctx.has_bias, ctx.lead = float(thr), bias is not None, lead
         # data parallel: a very large weight hands its gradient to the exchange in row blocks (cpg_amd.dist._ChunkedGradient)
@@ -385,13 +398,12 @@ class _MaskedLinearFn(torch.autograd.Function):
         gx = gw = gpm = gb = None
         if ctx.needs_input_grad[0]:
             gx = torch.empty((*ctx.lead, fin), dtype=torch.float32, device=x2.device)
-            rc = L.cpg_linear_dgrad(_lib.dptr(gy2, name='grad_output'), _lib.dptr(w), _lib.dptr(p), thr, _lib.dptr(gx),
-                                    batch, fin, fout, _lib.dptr(ws), nbytes, s)
-            _lib.check('cpg_linear_dgrad', rc)
+            _lib.call('cpg_linear_dgrad', _lib.dptr(gy2, name='grad_output'), _lib.dptr(w), _lib.dptr(p), thr, _lib.dptr(gx),
+                      batch, fin, fout, _lib.dptr(ws), nbytes, s)
         if ctx.needs_input_grad[1] or (p is not None and ctx.needs_input_grad[2]) or (ctx.has_bias and ctx.needs_input_grad[3]):
             gpm = None if p is None else torch.empty_like(p)
             gb = torch.empty(fout, dtype=torch.float32, device=x2.device) if ctx.has_bias else None
-            ch = getattr(ctx, 'dp_chunk', None)
+            ch = ctx.dp_chunk
             if ch is not None and ch.active() and fout % ch.nchunks == 0:
                 # the same GEMM in blocks of output rows, each block's all-reduce started as soon as its kernels are launched
                 gw = ch.buffer(w)
@@ -400,16 +412,14 @@ class _MaskedLinearFn(torch.autograd.Function):
                 for i in range(ch.nchunks):
                     r0, r1 = i * rows, (i + 1) * rows
                     gyc = gy2[:, r0:r1].contiguous()
-                    rc = L.cpg_linear_wgrad(_lib.dptr(x2), _lib.dptr(gyc), _lib.dptr(w[r0:r1]), _lib.dptr(None if p is None else p[r0:r1]), thr,
-                                            _lib.dptr(gw[r0:r1]), _lib.dptr(None if gpm is None else gpm[r0:r1]),
-                                            _lib.dptr(None if gb is None else gb[r0:r1]), batch, fin, rows, _lib.dptr(wsc), nbc, s)
-                    _lib.check('cpg_linear_wgrad', rc)
+                    _lib.call('cpg_linear_wgrad', _lib.dptr(x2), _lib.dptr(gyc), _lib.dptr(w[r0:r1]), _lib.dptr(None if p is None else p[r0:r1]),
+                              thr, _lib.dptr(gw[r0:r1]), _lib.dptr(None if gpm is None else gpm[r0:r1]),
+                              _lib.dptr(None if gb is None else gb[r0:r1]), batch, fin, rows, _lib.dptr(wsc), nbc, s)
                     ch.ready(gw, r0, r1)
             else:
                 gw = torch.empty_like(w)
-                rc = L.cpg_linear_wgrad(_lib.dptr(x2), _lib.dptr(gy2), _lib.dptr(w), _lib.dptr(p), thr, _lib.dptr(gw),
-                                        _lib.dptr(gpm), _lib.dptr(gb), batch, fin, fout, _lib.dptr(ws), nbytes, s)
-                _lib.check('cpg_linear_wgrad', rc)
+                _lib.call('cpg_linear_wgrad', _lib.dptr(x2), _lib.dptr(gy2), _lib.dptr(w), _lib.dptr(p), thr, _lib.dptr(gw),
+                          _lib.dptr(gpm), _lib.dptr(gb), batch, fin, fout, _lib.dptr(ws), nbytes, s)
         return gx, gw, gpm, gb, None
 
 
@@ -531,13 +541,11 @@ class SharableConv2d(_Sharable):
         oh, ow = _out_hw(d)
         y = torch.empty((d.N, d.K, oh, ow), dtype=torch.float32, device=x.device)
         ws, nbytes = _lib.workspace(L.cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
-        rc = L.cpg_conv2d_fwd_bn_eval(ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'), _lib.dptr(p, name='piggymask'),
-                                      float(self.info['threshold']), _lib.dptr(self.bias, name='bias'), _lib.dptr(bn.weight, name='bn.weight'),
-                                      _lib.dptr(bn.bias, name='bn.bias'), _lib.dptr(bn.running_mean, name='running_mean'),
-                                      _lib.dptr(bn.running_var, name='running_var'), float(bn.eps), int(bool(relu)), _lib.dptr(y),
-                                      None if skip_stats is None else ctypes.c_void_p(skip_stats.data_ptr()),
-                                      _lib.dptr(ws), nbytes, _lib.stream_ptr())
-        _lib.check('cpg_conv2d_fwd_bn_eval', rc)
+        _lib.call('cpg_conv2d_fwd_bn_eval', ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'),
+                  _lib.dptr(p, name='piggymask'), float(self.info['threshold']), _lib.dptr(self.bias, name='bias'),
+                  _lib.dptr(bn.weight, name='bn.weight'), _lib.dptr(bn.bias, name='bn.bias'), _lib.dptr(bn.running_mean, name='running_mean'),
+                  _lib.dptr(bn.running_var, name='running_var'), float(bn.eps), int(bool(relu)), _lib.dptr(y),
+                  None if skip_stats is None else ctypes.c_void_p(skip_stats.data_ptr()), _lib.dptr(ws), nbytes, _lib.stream_ptr())
         return y
 
     def extra_repr(self):

@@ -47,7 +47,6 @@ class MaskedSGD(torch.optim.SGD):
     def step(self, closure=None):
         if not self._masked:
             self._refresh()
-        L = _lib.lib()
         s = _lib.stream_ptr()
         pr = self.pruner
         held = []
@@ -74,14 +73,12 @@ class MaskedSGD(torch.optim.SGD):
                     continue
                 if not MULTI_TENSOR:
                     for w_, g_, b_, o_, n_ in rows:
-                        rc = L.cpg_sgd_route_step(w_, g_, b_, o_, int(pr.current_dataset_idx), float(pr.args.weight_decay), float(group['lr']),
-                                                  float(group['momentum']), int(bool(group['nesterov'])), int(first), n_, s)
-                        _lib.check('cpg_sgd_route_step', rc)
+                        _lib.call('cpg_sgd_route_step', w_, g_, b_, o_, int(pr.current_dataset_idx), float(pr.args.weight_decay), float(group['lr']),
+                                  float(group['momentum']), int(bool(group['nesterov'])), int(first), n_, s)
                     continue
                 items = (_lib.SgdItem * len(rows))(*rows)
-                rc = L.cpg_sgd_route_step_multi(items, len(rows), int(pr.current_dataset_idx), float(pr.args.weight_decay), float(group['lr']),
-                                                float(group['momentum']), int(bool(group['nesterov'])), int(first), s)
-                _lib.check('cpg_sgd_route_step_multi', rc)
+                _lib.call('cpg_sgd_route_step_multi', items, len(rows), int(pr.current_dataset_idx), float(pr.args.weight_decay), float(group['lr']),
+                          float(group['momentum']), int(bool(group['nesterov'])), int(first), s)
         loss = super().step(closure)
         for p, g in held:
             p.grad = g
@@ -112,7 +109,6 @@ class MaskedAdam(torch.optim.Adam):
     @torch.no_grad()
     def step(self, closure=None):
         self._refresh()                          # piggymasks are re-created between phases (driver._fresh_piggymasks)
-        L = _lib.lib()
         s = _lib.stream_ptr()
         pr = self.pruner
         mode = {'finetune': _lib.MODE_FINETUNE, 'prune': _lib.MODE_PRUNE}.get(pr.args.mode)
@@ -152,14 +148,12 @@ class MaskedAdam(torch.optim.Adam):
             for step, rows in batches.items():   # (cpg_adam_route_step_multi: every piggymask of the group in one launch)
                 if not MULTI_TENSOR:
                     for p_, g_, a_, b_, o_, n_ in rows:
-                        rc = L.cpg_adam_route_step(p_, g_, a_, b_, o_, int(pr.current_dataset_idx), mode, float(group['lr']), float(beta1),
-                                                   float(beta2), float(group['eps']), step, n_, s)
-                        _lib.check('cpg_adam_route_step', rc)
+                        _lib.call('cpg_adam_route_step', p_, g_, a_, b_, o_, int(pr.current_dataset_idx), mode, float(group['lr']), float(beta1),
+                                  float(beta2), float(group['eps']), step, n_, s)
                     continue
                 items = (_lib.AdamItem * len(rows))(*rows)
-                rc = L.cpg_adam_route_step_multi(items, len(rows), int(pr.current_dataset_idx), mode, float(group['lr']), float(beta1),
-                                                 float(beta2), float(group['eps']), step, s)
-                _lib.check('cpg_adam_route_step_multi', rc)
+                _lib.call('cpg_adam_route_step_multi', items, len(rows), int(pr.current_dataset_idx), mode, float(group['lr']), float(beta1),
+                          float(beta2), float(group['eps']), step, s)
         if idle:
             torch._foreach_zero_(idle)           # (one multi-tensor kernel)
         if len(held) > len(idle):

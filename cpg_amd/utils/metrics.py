@@ -48,9 +48,8 @@ def _distance(e1, e2, metric, sim=None):
     n, d = e1.shape
     dist = torch.empty(n, dtype=torch.float32, device=e1.device)
     with torch.cuda.device(e1.device):
-        _lib.check('cpg_pair_distance', _lib.lib().cpg_pair_distance(
-            ctypes.c_void_p(e1.data_ptr()), max(int(e1.stride(0)), d), ctypes.c_void_p(e2.data_ptr()), max(int(e2.stride(0)), d), n, d,
-            metric, _lib.dptr(dist), None if sim is None else _lib.dptr(sim), _lib.stream_ptr()))
+        _lib.call('cpg_pair_distance', ctypes.c_void_p(e1.data_ptr()), max(int(e1.stride(0)), d), ctypes.c_void_p(e2.data_ptr()),
+                  max(int(e2.stride(0)), d), n, d, metric, _lib.dptr(dist), None if sim is None else _lib.dptr(sim), _lib.stream_ptr())
     return dist
 
 
@@ -87,9 +86,8 @@ def roc_counts(thresholds, dist, actual_issame, nrof_folds=10, threshold_dtype='
     counts = torch.empty((max(F, 0), T, 4), dtype=torch.int64, device=dist.device)
     best = torch.empty(max(F, 0), dtype=torch.int64, device=dist.device)
     with torch.cuda.device(dist.device):
-        _lib.check('cpg_pair_sweep', _lib.lib().cpg_pair_sweep(
-            _lib.dptr(dist), _lib.dptr(same, torch.uint8), n, thr.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), T, F,
-            ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(best.data_ptr()), _lib.stream_ptr()))
+        _lib.call('cpg_pair_sweep', _lib.dptr(dist), _lib.dptr(same, torch.uint8), n, thr.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), T, F,
+                  ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(best.data_ptr()), _lib.stream_ptr())
     return counts.cpu().numpy(), best.cpu().numpy()
 
 

@@ -100,10 +100,8 @@ class SparsePruner(object):
         for i, (name, module) in enumerate(layers):
             w = module.weight.data
             owner = self._owner(name, w)
-            rc = L.cpg_rank_prune(_lib.dptr(w, name='weight'), _lib.dptr(owner, torch.uint8, 'mask'),
-                                  int(self.current_dataset_idx), float(pruning_ratio), w.numel(),
-                                  ctypes.c_void_p(res[i].data_ptr()), _lib.dptr(ws), nbytes, s)
-            _lib.check('cpg_rank_prune', rc)
+            _lib.call('cpg_rank_prune', _lib.dptr(w, name='weight'), _lib.dptr(owner, torch.uint8, 'mask'), int(self.current_dataset_idx),
+                      float(pruning_ratio), w.numel(), ctypes.c_void_p(res[i].data_ptr()), _lib.dptr(ws), nbytes, s)
         self._mutations += 1
         self.prune_events += 1
         raw = res.cpu().numpy().tobytes()
@@ -126,10 +124,8 @@ class SparsePruner(object):
         weights = weights.contiguous()
         res = torch.zeros(_lib.PRUNE_RESULT_BYTES // 8, dtype=torch.int64, device=weights.device)
         ws, nbytes = _lib.workspace(L.cpg_rank_prune_workspace_bytes(), weights.device)
-        rc = L.cpg_rank_prune(_lib.dptr(weights, name='weights'), _lib.dptr(mask, torch.uint8, 'mask'),
-                              int(self.current_dataset_idx), float(pruning_ratio), weights.numel(),
-                              ctypes.c_void_p(res.data_ptr()), _lib.dptr(ws), nbytes, _lib.stream_ptr())
-        _lib.check('cpg_rank_prune', rc)
+        _lib.call('cpg_rank_prune', _lib.dptr(weights, name='weights'), _lib.dptr(mask, torch.uint8, 'mask'), int(self.current_dataset_idx),
+                  float(pruning_ratio), weights.numel(), ctypes.c_void_p(res.data_ptr()), _lib.dptr(ws), nbytes, _lib.stream_ptr())
         self._mutations += 1
         r = _lib.PruneResult.from_buffer_copy(res.cpu().numpy().tobytes())
         if r.status == _lib.CPG_E_KRANGE:
@@ -180,7 +176,6 @@ class SparsePruner(object):
             return self._hist
         if not layers:
             return [0] * 257
-        L = _lib.lib()
         dev = layers[0][1].weight.device
         hist = torch.zeros(257, dtype=torch.int64, device=dev)
         s = _lib.stream_ptr()
@@ -189,9 +184,8 @@ class SparsePruner(object):
             pm = None
             if with_piggymask:
                 pm = module.piggymask.data.contiguous()       # AttributeError on None, as in the reference
-            rc = L.cpg_mask_hist(_lib.dptr(owner, torch.uint8, 'mask'), _lib.dptr(pm, name='piggymask'),
-                                 int(self.inference_dataset_idx), owner.numel(), ctypes.c_void_p(hist.data_ptr()), s)
-            _lib.check('cpg_mask_hist', rc)
+            _lib.call('cpg_mask_hist', _lib.dptr(owner, torch.uint8, 'mask'), _lib.dptr(pm, name='piggymask'), int(self.inference_dataset_idx),
+                      owner.numel(), ctypes.c_void_p(hist.data_ptr()), s)
         self._hist = hist.cpu().tolist()
         self._hist_key = key
         return self._hist
@@ -226,7 +220,6 @@ class SparsePruner(object):
     def do_weight_decay_and_make_grads_zero(self):
         """Sets grads of fixed weights to 0 (utils/prune.py:195-211), one fused pass per layer."""
         assert self.masks
-        L = _lib.lib()
         s = _lib.stream_ptr()
         mode = {'finetune': _lib.MODE_FINETUNE, 'prune': _lib.MODE_PRUNE}.get(self.args.mode)
         for name, module in self._layers():
@@ -238,10 +231,8 @@ class SparsePruner(object):
                     continue       # (piggymask gradients are routed inside MaskedAdam.step() when one is attached)
                 owner = self._owner(name, w.data)
                 scratch = torch.zeros_like(w.data)
-                rc = L.cpg_route_grads(_lib.dptr(scratch), _lib.dptr(w.data.contiguous(), name='weight'),
-                                       _lib.dptr(owner, torch.uint8, 'mask'), int(self.current_dataset_idx), 0.0,
-                                       _lib.dptr(pm.grad.data, name='piggymask.grad'), mode, scratch.numel(), s)
-                _lib.check('cpg_route_grads', rc)
+                _lib.call('cpg_route_grads', _lib.dptr(scratch), _lib.dptr(w.data.contiguous(), name='weight'), _lib.dptr(owner, torch.uint8, 'mask'),
+                          int(self.current_dataset_idx), 0.0, _lib.dptr(pm.grad.data, name='piggymask.grad'), mode, scratch.numel(), s)
                 continue
             if w.grad is None:
                 # the reference still routes a piggymask grad here; without a weight grad only that part applies
@@ -258,42 +249,33 @@ class SparsePruner(object):
                 gw = torch.zeros_like(w.data)
             if not gw.is_contiguous() or (gpm is not None and not gpm.is_contiguous()):
                 raise RuntimeError('gradient of %s is not contiguous' % name)
-            rc = L.cpg_route_grads(_lib.dptr(gw, name='weight.grad'), _lib.dptr(w.data.contiguous(), name='weight'),
-                                   _lib.dptr(owner, torch.uint8, 'mask'), int(self.current_dataset_idx),
-                                   float(self.args.weight_decay), _lib.dptr(gpm, name='piggymask.grad'),
-                                   mode if mode is not None else _lib.MODE_FINETUNE, gw.numel(), s)
-            _lib.check('cpg_route_grads', rc)
+            _lib.call('cpg_route_grads', _lib.dptr(gw, name='weight.grad'), _lib.dptr(w.data.contiguous(), name='weight'),
+                      _lib.dptr(owner, torch.uint8, 'mask'), int(self.current_dataset_idx), float(self.args.weight_decay),
+                      _lib.dptr(gpm, name='piggymask.grad'), mode if mode is not None else _lib.MODE_FINETUNE, gw.numel(), s)
 
     # ------------------------------------------------------------------ mask application
     def make_pruned_zero(self):
         """Makes pruned weights 0 (utils/prune.py:213-221)."""
         assert self.masks
-        L = _lib.lib()
         s = _lib.stream_ptr()
         for name, module in self._layers():
             w = module.weight.data
-            rc = L.cpg_zero_pruned(_lib.dptr(w, name='weight'), _lib.dptr(self._owner(name, w), torch.uint8, 'mask'),
-                                   w.numel(), s)
-            _lib.check('cpg_zero_pruned', rc)
+            _lib.call('cpg_zero_pruned', _lib.dptr(w, name='weight'), _lib.dptr(self._owner(name, w), torch.uint8, 'mask'), w.numel(), s)
 
     def apply_mask(self):
         """Keep only the weights of tasks <= inference_dataset_idx, destructively (utils/prune.py:223-231)."""
-        L = _lib.lib()
         s = _lib.stream_ptr()
         for name, module in self._layers():
             w = module.weight.data
-            rc = L.cpg_apply_mask(_lib.dptr(w, name='weight'), _lib.dptr(self._owner(name, w), torch.uint8, 'mask'),
-                                  int(self.inference_dataset_idx), w.numel(), s)
-            _lib.check('cpg_apply_mask', rc)
+            _lib.call('cpg_apply_mask', _lib.dptr(w, name='weight'), _lib.dptr(self._owner(name, w), torch.uint8, 'mask'),
+                      int(self.inference_dataset_idx), w.numel(), s)
 
     def make_finetuning_mask(self):
         """Hand every free slot to the new task (utils/prune.py:233-243)."""
         assert self.masks
         self.current_dataset_idx += 1
-        L = _lib.lib()
         s = _lib.stream_ptr()
         for name, module in self._layers():
             owner = self._owner(name, module.weight.data)
-            rc = L.cpg_claim_free(_lib.dptr(owner, torch.uint8, 'mask'), int(self.current_dataset_idx), owner.numel(), s)
-            _lib.check('cpg_claim_free', rc)
+            _lib.call('cpg_claim_free', _lib.dptr(owner, torch.uint8, 'mask'), int(self.current_dataset_idx), owner.numel(), s)
         self._mutations += 1

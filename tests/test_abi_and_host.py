@@ -29,6 +29,65 @@ def test_library_exports_every_declared_symbol():
     lib = L.lib()                      # raises if the .so is missing or a symbol is absent
     assert lib.cpg_version() == L.ABI_VERSION == 3
     assert lib.cpg_rank_prune_workspace_bytes() > 0
+    # ... with the header's types: the return type and every parameter of every prototype against its row of the binding's table
+    # (a row with two slots swapped loads and links just the same)
+    import ctypes
+
+    def c_kind(decl):
+        words = decl.replace('*', ' * ').split()
+        words = [w for w in words if w != 'const']
+        if '*' in words:
+            return 'char*' if words[0] == 'char' else 'pointer'
+        return {'int': 'int', 'int32_t': 'int', 'int64_t': 'int64', 'size_t': 'size_t', 'float': 'float', 'double': 'double'}[words[0]]
+
+    def py_kind(t):
+        if t is ctypes.c_char_p:
+            return 'char*'
+        if t is ctypes.c_void_p or issubclass(t, ctypes._Pointer):
+            return 'pointer'
+        return {ctypes.c_int: 'int', ctypes.c_int32: 'int', ctypes.c_int64: 'int64', ctypes.c_size_t: 'size_t', ctypes.c_float: 'float',
+                ctypes.c_double: 'double'}[t]
+
+    code = re.sub(r'/\*.*?\*/', ' ', header, flags=re.S)
+    code = re.sub(r'//[^\n]*', ' ', code)
+    code = '\n'.join(ln for ln in code.split('\n') if not ln.lstrip().startswith('#'))
+    protos = re.findall(r'(?:\A|(?<=[;{}]))\s*([\w\s*]+?)\b(cpg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', code)
+    assert {name for _, name, _ in protos} == set(L.EXPORTS) and len(protos) == len(L.EXPORTS)
+    for ret, name, params in protos:
+        params = [] if params.strip() == 'void' else [re.sub(r'\w+$', '', p.strip()) for p in params.split(',')]     # (type without the name)
+        res, args = L._SIGNATURES[name]
+        assert (c_kind(ret), [c_kind(p) for p in params]) == (py_kind(res), [py_kind(a) for a in args]), name
+
+
+def test_call_helper_reports_the_entry_point_it_called():
+    """_lib.call looks the entry point up on lib() at call time (profilers put a proxy there) and raises under that entry point's name."""
+    with pytest.raises(L.CpgHipError, match=r"^cpg_set_option failed with status -1: .*unknown option 'CPG_NO_SUCH_SWITCH'") as e:
+        L.call('cpg_set_option', b'CPG_NO_SUCH_SWITCH', 1)
+    assert e.value.code == L.CPG_E_INVALID
+    real, seen = L.lib(), []
+
+    class Proxy(object):
+        def __getattr__(self, name):
+            seen.append(name)
+            return getattr(real, name)
+    L._lib = Proxy()
+    try:
+        L.call('cpg_set_shared_chip_hint', real.cpg_get_shared_chip_hint())
+    finally:
+        L._lib = real
+    assert seen == ['cpg_set_shared_chip_hint']
+
+
+def test_bn_bwd_hint_hands_its_result_to_the_same_gradient_only():
+    g = torch.zeros(2, 3)
+    hint = nl.BnBwdHint(epilogue=False, rider=True)
+    assert not hint.usable(g)                                   # (never filled)
+    hint.fill(g, g, g, g, g, g.shape)
+    hint.store(g, ('gx', 'dgamma', 'dbeta'))
+    assert hint.take(g.clone()) is None                         # another tensor: the rider's result is not this gradient's
+    assert hint.result is None and hint.gz is None and hint.ypre is None and not hint.usable(g)       # ... and it is dropped either way
+    hint.store(g, ('gx', 'dgamma', 'dbeta'))
+    assert hint.take(g) == ('gx', 'dgamma', 'dbeta') and hint.take(g) is None
 
 
 def test_library_exports_nothing_but_the_header():
