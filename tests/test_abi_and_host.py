@@ -132,6 +132,25 @@ def test_generated_wgrad_kernel_is_current():
     spec.loader.exec_module(gen)
     committed = open(os.path.join(ROOT, 'cpg_amd', 'csrc', 'conv3x3_wino_wgrad.hip')).read()
     assert gen.generate() == committed, 'run python tools/gen_wino_wgrad.py'
+    # ... and cpg_amd/csrc/wino_acc.h, the pinned-accumulator macros of all the Winograd kernels, is what the same script writes
+    assert gen.acc_header() == open(os.path.join(ROOT, 'cpg_amd', 'csrc', 'wino_acc.h')).read(), 'run python tools/gen_wino_wgrad.py'
+
+
+def test_pinned_accumulator_macros_are_defined_once():
+    """wino_acc.h is the one definition of the fixed-AGPR macros: no kernel source (nor the weight-gradient template) defines a
+    macro of one of its names again, or a per-family copy in the old spelling (W1_ONE_3, WW_RD_0, W3_RD_1_15, ...)."""
+    import glob
+    define = re.compile(r'^[ \t]*#[ \t]*define[ \t]+(\w+)', re.M)
+    csrc = os.path.join(ROOT, 'cpg_amd', 'csrc')
+    shared = set(define.findall(open(os.path.join(csrc, 'wino_acc.h')).read()))
+    assert {'WACC_MMA_0', 'WACC_MMA_15', 'WACC_ZERO_15', 'WACC_RD16_15', 'WACC_RD8_1_15', 'WACC_FENCE', 'WACC_LDS_BARRIER',
+            'WACC_DRAIN'} <= shared
+    sources = sorted(glob.glob(os.path.join(csrc, '*.hip'))) + [os.path.join(ROOT, 'tools', 'csrc', 'wino_wgrad_template.hip')]
+    assert len(sources) > 10
+    for path in sources:
+        names = define.findall(open(path).read())
+        assert not shared.intersection(names), path
+        assert not [n for n in names if re.match(r'W\w+?_(ONE_\d+|RD_)', n)], path
 
 
 def test_struct_layouts_match_header():

@@ -25,6 +25,7 @@
 // The sign of the transform rows / columns with a -1 (A's last row) is applied to M in the epilogue instead of to the operands.
 #include <algorithm>
 #include "cpg_dispatch.h"
+#include "wino_acc.h"
 
 using namespace cpg;
 
@@ -68,10 +69,6 @@ struct WwRider {
     int bytes;                // N * C * HW * 4 < 2^31
     unsigned total, per;      // wave-items in all / per wave
 };
-
-@@MMA@@
-@@RD@@
-#define WW_FENCE() __builtin_amdgcn_sched_barrier(0)
 
 // -DWG_TIMING (development builds, tools/attic/diag_wg_timing.py --wgrad): per-wave constant-clock stamps, as in conv3x3_wino.hip
 #ifdef WG_TIMING
@@ -404,11 +401,8 @@ void k_wgw(WwGeom g, const float *__restrict__ x, const float *__restrict__ gy, 
         }
     };
     (void)r_micro;
-    // workgroup barrier that waits for this wave's LDS traffic only (__syncthreads would also wait for the stage loads in flight)
-#define WW_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
     WW_STAMP(1);
-@@ZERO@@
+    WACC_ZERO_ALL();
     float A0[16], B0[16], A1[16], B1[16];
     // prologue: stage 0 into LDS, its first operands, stage 1's coordinates ready
     stage_offsets();
@@ -428,7 +422,7 @@ void k_wgw(WwGeom g, const float *__restrict__ x, const float *__restrict__ gy, 
     if constexpr (TS) {
 #pragma unroll
         for (int m = 0; m < 3; ++m) b_micro(m, 0, 0, B0, xb0);
-        WW_LDS_BARRIER();
+        WACC_LDS_BARRIER();
 #pragma unroll
         for (int m = 3; m < 7; ++m) b_micro(m, 0, 0, B0, xb0);
         t_micro(4, 0, A0, B0, xb0), t_micro(11, 0, A0, B0, xb0), t_micro(12, 0, A0, B0, xb0), t_micro(13, 0, A0, B0, xb0);
@@ -463,7 +457,7 @@ void k_wgw(WwGeom g, const float *__restrict__ x, const float *__restrict__ gy, 
         }
     }
     // ---- epilogue: dg = G^T M G per (k, c); M[i][j] = sigma_i sigma_j acc[4 i + j], sigma = (1, 1, 1, -1) ----
-    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+    WACC_DRAIN();
     float *pout = part + ((int64_t)split * 9 * g.K + k0) * g.C + c0 + li;
     const int64_t tap_plane = (int64_t)g.K * g.C;
     auto out_e = [&](int e, float (&m)[16]) {
@@ -485,7 +479,9 @@ void k_wgw(WwGeom g, const float *__restrict__ x, const float *__restrict__ gy, 
     };
     {
         float m[16];
-@@OUT@@
+#define WW_OUT(e) WACC_RD16_##e(m); out_e(e, m);
+        WACC_EACH16(WW_OUT)
+#undef WW_OUT
     }
     WW_STAMP(4);
 }
