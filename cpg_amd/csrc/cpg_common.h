@@ -51,6 +51,8 @@ enum Opt {
     OPT_WINO_TAIL,        // CPG_WINO_TAIL=0: no channel-split tail launch for the leftover units of k_wg3's last round (round 4 behaviour)
     OPT_FC_SMALL,         // CPG_FC_SMALL=0: linear layers at <= 64 rows on the batch-256 tiles / the generic split-K kernel (round 4 behaviour)
     OPT_NO_WW_RIDER,      // CPG_NO_WW_RIDER=1: cpg_conv2d_wgrad_rider_supported answers 0 (the BatchNorm backward apply stays a pass of its own)
+    OPT_NO_GROUPED,       // CPG_NO_GROUPED=1: descriptors with groups > 1 are reported as unsupported (callers run one groups == 1 launch per group)
+    OPT_GROUPED_WIDE_MIN, // CPG_GROUPED_WIDE_MIN=n: channels per group (both sides) from which groups > 1 run the MFMA implicit GEMM instead of the direct kernels (default 16)
     OPT_COUNT
 };
 constexpr int OPT_UNSET = INT32_MIN;

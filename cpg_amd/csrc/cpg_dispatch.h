@@ -100,6 +100,19 @@ size_t cpg_conv_stem2_wgrad_workspace(const cpg_conv_desc *d);
 int cpg_conv_stem2_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr, float *gw,
                          float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
 
+// ---- conv_grouped.hip: groups > 1 (depthwise / narrow groups on direct VALU kernels, wide groups on the fp32-MFMA implicit GEMM) ---------------
+// 1: descriptors with groups > 1 run the grouped kernels (CPG_NO_GROUPED: never -- such descriptors are then unsupported).  The entry points
+// below take a descriptor the caller has validated (groups > 1 dividing C and K) and non-null tensors.
+int cpg_conv_grouped_ok(const cpg_conv_desc *d);
+int cpg_conv_grouped_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y,
+                         hipStream_t stream);
+int cpg_conv_grouped_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx,
+                           hipStream_t stream);
+// the split partial sums of the weight gradient: [slices or splits][K][C/G][R][S] floats
+size_t cpg_conv_grouped_wgrad_workspace(const cpg_conv_desc *d);
+int cpg_conv_grouped_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr, float *gw,
+                           float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
+
 // ---- pointwise.hip: 1x1 convolutions ----------------------------------------------------------------------------------------------------
 // 1: the pointwise kernels take this shape's forward and input gradient (CPG_DISABLE_CONV1X1: never)
 extern "C" int cpg_conv1x1_supported(const cpg_conv_desc *d);

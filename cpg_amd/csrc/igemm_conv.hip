@@ -1,5 +1,5 @@
 // Generic masked conv2d on fp32 MFMA: forward, input-gradient and weight-gradient of
-// models/layers.py:108-109 for ANY kernel size / stride / padding / dilation (groups == 1).
+// models/layers.py:108-109 for ANY kernel size / stride / padding / dilation (groups == 1; groups > 1: conv_grouped.hip).
 // This is the shape-complete path (ResNet 1x1, 7x7 s2, 3x3 s2; SphereNet 3x3 s2) and the
 // fallback for the specialised 3x3 s1 p1 kernels of conv3x3.hip.
 //
@@ -476,7 +476,8 @@ int make_geom(const cpg_conv_desc *d, ConvGeom &g) {
     CPG_REQUIRE(d->N > 0 && d->C > 0 && d->H > 0 && d->W > 0 && d->K > 0 && d->R > 0 && d->S > 0, "conv: non-positive dimension");
     CPG_REQUIRE(d->stride_h > 0 && d->stride_w > 0 && d->dil_h > 0 && d->dil_w > 0 && d->pad_h >= 0 && d->pad_w >= 0,
                 "conv: bad stride/dilation/padding");
-    if (d->groups != 1) return fail(CPG_E_UNSUPPORTED, "conv: groups=%d not implemented (all CPG configs use 1)", d->groups);
+    CPG_REQUIRE(d->groups >= 1 && d->C % d->groups == 0 && d->K % d->groups == 0, "conv: groups must be >= 1 and divide C and K");
+    if (d->groups > 1 && !cpg_conv_grouped_ok(d)) return fail(CPG_E_UNSUPPORTED, "conv: groups=%d with CPG_NO_GROUPED set (run one groups == 1 launch per group)", d->groups);
     g = ConvGeom{d->N, d->C, d->H, d->W, d->K, d->R, d->S, d->stride_h, d->stride_w, d->pad_h, d->pad_w, d->dil_h, d->dil_w, 0, 0};
     g.OH = (d->H + 2 * d->pad_h - d->dil_h * (d->R - 1) - 1) / d->stride_h + 1;
     g.OW = (d->W + 2 * d->pad_w - d->dil_w * (d->S - 1) - 1) / d->stride_w + 1;
@@ -512,9 +513,10 @@ void conv_wgrad_tiles(const ConvGeom &g, int &tiles_m, int &tiles_n) {
 // The classes are mutually exclusive, so the order in which a route tests them decides nothing:
 //   - 3x3 s1 p1 (conv3x3.hip, conv3x3_wino*.hip), 1x1 (pointwise.hip) and the two stride-2 classes differ in kernel size or stride;
 //   - of the stride-2 classes, 3x3 s2 p1 (conv3x3.hip) needs >= 16 channels on both sides, the image stems (conv_stem_s2.hip:
-//     7x7 s2 p3, 3x3 s2 p1) need <= 3 input channels.
+//     7x7 s2 p3, 3x3 s2 p1) need <= 3 input channels;
+//   - groups > 1 (conv_grouped.hip) is ROUTE_GROUPED and nothing else: every other class requires groups == 1.
 // (wgrad_route tests the stems before 3x3 s2, fwd_route after it, as the entry points always did.)
-enum ConvRoute { ROUTE_C3, ROUTE_C1, ROUTE_C3S2, ROUTE_STEM2, ROUTE_GENERIC };
+enum ConvRoute { ROUTE_C3, ROUTE_C1, ROUTE_C3S2, ROUTE_STEM2, ROUTE_GROUPED, ROUTE_GENERIC };
 
 // the 3x3 weight-gradient kernel owns a 64-wide input-channel tile; <= 3 channels (the VGG stem) have their own
 // HBM-streaming kernel, 4..15 channels go to the generic kernel whose (ci, tap) column packing wastes less MFMA
@@ -523,6 +525,7 @@ static inline bool use_c3_wgrad(const cpg_conv_desc *d) { return cpg_conv3x3_sup
 // forward and input gradient (the stems have no input gradient of their own: cpg_conv2d_dgrad sends ROUTE_STEM2 to the generic kernel)
 static ConvRoute fwd_route(const cpg_conv_desc *d) {
     if (d == nullptr) return ROUTE_GENERIC;              // (the generic entry point reports it)
+    if (d->groups > 1) return ROUTE_GROUPED;
     if (cpg_conv3x3_supported(d)) return ROUTE_C3;
     if (cpg_conv1x1_supported(d)) return ROUTE_C1;
     if (cpg_conv3x3s2_supported(d)) return ROUTE_C3S2;
@@ -531,6 +534,7 @@ static ConvRoute fwd_route(const cpg_conv_desc *d) {
 }
 // weight gradient (d != nullptr)
 static ConvRoute wgrad_route(const cpg_conv_desc *d) {
+    if (d->groups > 1) return ROUTE_GROUPED;
     if (use_c3_wgrad(d)) return ROUTE_C3;
     if (cpg_conv_stem2_ok(d)) return ROUTE_STEM2;
     if (cpg_conv3x3s2_supported(d)) return ROUTE_C3S2;
@@ -553,6 +557,7 @@ extern "C" size_t cpg_conv2d_workspace_bytes(const cpg_conv_desc *d) {
         case ROUTE_STEM2: return std::max(need, cpg_conv_stem2_wgrad_workspace(d));
         case ROUTE_C3S2: return std::max(need, cpg_conv3x3s2_wgrad_workspace(d));
         case ROUTE_C1: return std::max(need, cpg_conv1x1_wgrad_workspace(d));
+        case ROUTE_GROUPED: return std::max(need, cpg_conv_grouped_wgrad_workspace(d));
         default: break;
     }
     int tm, tn, nsplit, per;
@@ -661,6 +666,13 @@ extern "C" int cpg_conv2d_fwd(const cpg_conv_desc *d, const float *x, const floa
     if (cpg::pack_query()) return CPG_OK;        // (only the two routes above have pack sites)
     if (route == ROUTE_C3S2) return cpg_conv3x3s2_fwd(d, x, w, pm, thr, bias, y, nullptr, ws, ws_bytes, (hipStream_t)stream);
     if (route == ROUTE_STEM2) return cpg_conv_stem2_fwd(d, x, w, pm, thr, bias, y, nullptr, (hipStream_t)stream);
+    if (route == ROUTE_GROUPED) {
+        ConvGeom g;
+        const int rc = make_geom(d, g);
+        if (rc) return rc;
+        CPG_REQUIRE(x && w && y, "cpg_conv2d_fwd: null pointer");
+        return cpg_conv_grouped_fwd(d, x, w, pm, thr, bias, y, (hipStream_t)stream);
+    }
     return cpg_conv2d_fwd_generic(d, x, w, pm, thr, bias, y, stream);
 }
 
@@ -747,6 +759,13 @@ extern "C" int cpg_conv2d_dgrad(const cpg_conv_desc *d, const float *gy, const f
     if (route == ROUTE_C1) return cpg_conv1x1_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream);
     if (cpg::pack_query()) return CPG_OK;        // (only the two routes above have pack sites)
     if (route == ROUTE_C3S2) return cpg_conv3x3s2_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream);
+    if (route == ROUTE_GROUPED) {
+        ConvGeom g;
+        const int rc = make_geom(d, g);
+        if (rc) return rc;
+        CPG_REQUIRE(gy && w && gx, "cpg_conv2d_dgrad: null pointer");
+        return cpg_conv_grouped_dgrad(d, gy, w, pm, thr, gx, (hipStream_t)stream);
+    }
     return cpg_conv2d_dgrad_generic(d, gy, w, pm, thr, gx, stream);
 }
 
@@ -894,6 +913,7 @@ extern "C" int cpg_conv2d_wgrad(const cpg_conv_desc *d, const float *x, const fl
         case ROUTE_STEM2: rc = cpg_conv_stem2_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream); break;
         case ROUTE_C3S2: rc = cpg_conv3x3s2_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream); break;
         case ROUTE_C1: rc = cpg_conv1x1_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream); break;
+        case ROUTE_GROUPED: rc = cpg_conv_grouped_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream); break;
         default: rc = wgrad_generic(g, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream); what = "cpg_conv2d_wgrad"; break;
     }
     if (rc) return rc;

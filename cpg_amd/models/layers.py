@@ -32,6 +32,17 @@ DEFAULT_THRESHOLD = 5e-3      # models/layers.py:9
 CONV_MATH = 'fp32'
 
 
+# groups > 1: channels per group (the smaller of C/G and K/G) from which two classes of layers run one groups == 1 launch per group
+# instead of the grouped kernels, because a pass of theirs measured slower there (profiles/grouped_conv.md, batch 256):
+#   * 3x3 / stride 1 / pad 1 / dilation 1: per group these are Winograd layers (16/36 of the products); forward and input gradient of
+#     the grouped implicit GEMM are 1.2 - 1.8 x slower at 16 and 24 channels per group and every pass 1.2 - 3.2 x slower from 32 (its
+#     weight gradient is 2 x FASTER at 16 and 24: given up, the dispatch is per layer, not per pass);
+#   * any stride > 1: the grouped MFMA input gradient runs one launch with a divisibility test per tap and is 2.5 - 4.6 x slower than
+#     the generic kernel's residue-class launches per group (forward and weight gradient are up to 3 x faster: given up likewise).
+# Below 16 channels per group every measured shape and pass is faster on the grouped kernels.  None: always the grouped kernels.
+GROUPED_PER_GROUP_MIN = 16
+
+
 def set_conv_math(math):
     """Select the arithmetic of every SharableConv2d that has no `.math` of its own: 'fp32' or 'bf16' (opt-in)."""
     global CONV_MATH
@@ -464,8 +475,9 @@ class SharableConv2d(_Sharable):
         if in_channels % groups or out_channels % groups:
             raise ValueError('in_channels and out_channels must be divisible by groups')
         # groups > 1 (the reference forwards `groups` to F.conv2d, models/layers.py:108-109; no CPG configuration uses it -- the resnext*
-        # factories and VGG(groups=...) exist in its model files): one launch of the groups == 1 kernels per group on a contiguous
-        # channel slice, see _grouped() -- correct and on the HIP path, not tuned
+        # factories and VGG(groups=...) exist in its model files): fp32 runs the library's grouped kernels, all groups in one launch per
+        # pass (csrc/conv_grouped.hip); the bf16 arithmetics, CPG_NO_GROUPED=1 and, from GROUPED_PER_GROUP_MIN channels per group, 3x3 s1 p1
+        # layers and strided layers (see there: a pass of theirs measured slower) run one groups == 1 launch per group, see _grouped()
         self.in_channels, self.out_channels, self.groups = in_channels, out_channels, groups
         self.kernel_size, self.stride = _pair(kernel_size), _pair(stride)
         self.padding, self.dilation = _pair(padding), _pair(dilation)
@@ -479,7 +491,8 @@ class SharableConv2d(_Sharable):
         self._init_mask_state(mask_init, mask_scale, threshold_fn, threshold)
 
     def _grouped(self, input):
-        """groups > 1: y = cat_g conv2d(x[:, g-th channel slice], W[g-th row block] * bin(pm[...]), b[...]) -- every group through the
+        """groups > 1 without the library's grouped kernels (the bf16 arithmetics, CPG_NO_GROUPED=1, the classes of _per_group):
+        y = cat_g conv2d(x[:, g-th channel slice], W[g-th row block] * bin(pm[...]), b[...]) -- every group through the
         groups == 1 kernels (autograd slices / concatenates; the row blocks of weight, piggymask and bias are contiguous views)."""
         G = self.groups
         if input.dim() != 4 or input.shape[1] != self.weight.shape[1] * G:
@@ -494,9 +507,25 @@ class SharableConv2d(_Sharable):
                                               self.padding, self.dilation, 1, False, self._math(), None, None))
         return torch.cat(outs, dim=1)
 
+    def _per_group(self):
+        """groups > 1 only: True when this call runs one groups == 1 launch per group (_grouped) instead of the grouped kernels."""
+        if self._math() != 'fp32' or bool(_lib.get_option('CPG_NO_GROUPED')):
+            return True
+        per = min(self.in_channels, self.out_channels) // self.groups
+        if GROUPED_PER_GROUP_MIN is None or per < GROUPED_PER_GROUP_MIN:
+            return False
+        wino = self.kernel_size == (3, 3) and self.stride == (1, 1) and self.padding == (1, 1) and self.dilation == (1, 1)
+        return wino or self.stride != (1, 1)
+
+    def _grouped_fused(self, input):
+        """groups > 1 on the grouped kernels: ONE application of the autograd Function, one launch per pass for all groups (no fused
+        statistics, BatchNorm-backward hint or bias sink on this route)."""
+        return _MaskedConv2dFn.apply(input, self.weight, self.piggymask, self.bias, self.info['threshold'],
+                                     self.stride, self.padding, self.dilation, self.groups, False, 'fp32', None, None)
+
     def forward(self, input, layer_info=None, name=None, bn_hint=None, bias_sink=None):
         if self.groups != 1:
-            return self._grouped(input)
+            return self._grouped(input) if self._per_group() else self._grouped_fused(input)
         return _MaskedConv2dFn.apply(input, self.weight, self.piggymask, self.bias, self.info['threshold'],
                                      self.stride, self.padding, self.dilation, self.groups, False, self._math(), bn_hint, bias_sink)
 
@@ -505,11 +534,11 @@ class SharableConv2d(_Sharable):
 
     def forward_with_bn_stats(self, input, bn_hint=None):
         """(y, stats): forward plus the BatchNorm partial sums of y from the same kernel; stats is None when this shape
-        has no fused-statistics kernel (groups > 1 among them: the per-group calls take no statistics epilogue, no BatchNorm-backward hint
-        and no bias sink -- callers get stats None and run the separate statistics pass).  Used by cpg_amd.models.fused_bn.FusedSequential
+        has no fused-statistics kernel (groups > 1 among them: neither the grouped kernels nor the per-group calls take a statistics
+        epilogue, a BatchNorm-backward hint or a bias sink -- callers get stats None and run the separate statistics pass).  Used by cpg_amd.models.fused_bn.FusedSequential
         for conv -> BatchNorm2d runs."""
         if self.groups != 1:
-            return self._grouped(input), None
+            return self.forward(input), None
         y, stats = _MaskedConv2dFn.apply(input, self.weight, self.piggymask, self.bias, self.info['threshold'],
                                          self.stride, self.padding, self.dilation, self.groups, True, self._math(), bn_hint)
         return y, (stats if stats.numel() else None)
@@ -518,7 +547,7 @@ class SharableConv2d(_Sharable):
         """(y, stats or None, skip): forward (+ BatchNorm partial sums where the shape has them) and the input handed back for the
         residual branch; the two gradients of the input are summed inside the input-gradient kernel (_MaskedConv2dSkipFn)."""
         if self.groups != 1:
-            return self._grouped(input), None, input
+            return self.forward(input), None, input
         y, stats, skip = _MaskedConv2dSkipFn.apply(input, self.weight, self.piggymask, self.bias, self.info['threshold'],
                                                    self.stride, self.padding, self.dilation, self.groups, self._math(), bias_sink, want_stats)
         return y, (stats if stats.numel() else None), skip

@@ -62,7 +62,7 @@ typedef struct cpg_conv_desc {
     int32_t stride_h, stride_w;
     int32_t pad_h, pad_w;
     int32_t dil_h, dil_w;
-    int32_t groups;           /* only 1 is implemented (all CPG configs)      */
+    int32_t groups;           /* >= 1, divides C and K; w is [K][C/groups][R][S] */
 } cpg_conv_desc;
 
 /* result record of cpg_rank_prune, written to DEVICE memory (one per call) */
@@ -101,7 +101,9 @@ int32_t cpg_get_shared_chip_hint(void);
  *   arithmetic (Winograd transforms vs direct taps: differences of 1e-6 of the output scale):
  *       CPG_NO_WINO, CPG_NO_WINO_WGRAD, CPG_NO_WINO_ODD, CPG_DISABLE_CONV3X3, CPG_C3_FORCE (tile shape of the direct kernel = its
  *       channel-split accumulation), CPG_NO_S2, CPG_NO_V14, CPG_W3_PICK, CPG_DISABLE_CONV1X1, CPG_DISABLE_CONV1X1_WGRAD,
- *       CPG_DISABLE_PW_GEMM, CPG_NO_STEM (stem kernel vs general kernel: other k order of the 27 taps);
+ *       CPG_DISABLE_PW_GEMM, CPG_NO_STEM (stem kernel vs general kernel: other k order of the 27 taps),
+ *       CPG_NO_GROUPED (groups > 1: the library reports the descriptor as unsupported and the caller runs one groups == 1 launch
+ *       per group: another kernel family per group = another summation order), CPG_GROUPED_WIDE_MIN (direct vs MFMA kernels);
  *   summation order only (how a reduction over pixels / tiles / channel blocks is split and added: last-bit differences, mostly in
  *   weight gradients and BatchNorm statistics):
  *       CPG_WW_UNITS, CPG_WW_SHARE, CPG_C3W_BPC, CPG_PWW_BPC, CPG_PW_TILE, CPG_WINO_KERNEL, CPG_WINO_NW, CPG_STEM_BLOCKS, CPG_WINO_TAIL,
@@ -136,7 +138,19 @@ int cpg_binarize_mask_weight(const float *w, const float *pm, float thr, float *
  * wgrad : gW_eff = conv2d_weight_grad(x, gy); then, as autograd of `bin(pm) * W`
  *         (models/layers.py:103): gw = gW_eff * bin(pm), gpm = gW_eff * W (gpm NULL when pm
  *         is NULL).  gb (may be NULL) = sum of gy over N,H,W.
- *         gw / gpm / gb are OVERWRITTEN (caller accumulates if it needs to). */
+ *         gw / gpm / gb are OVERWRITTEN (caller accumulates if it needs to).
+ * groups > 1 (desc->groups divides C and K, else CPG_E_INVALID): w, pm, gw and gpm are [K][C/groups][R][S]; group g reads input
+ *         channels [g C/groups, (g+1) C/groups) and writes output channels [g K/groups, (g+1) K/groups).  All groups of a pass run
+ *         in one launch on the NCHW tensors in place (direct kernels for narrow groups, fp32 MFMA from 16 channels per group on both
+ *         sides); the weight gradient sums split partials from the workspace in a fixed order (no atomics: bit-reproducible).  Such
+ *         descriptors have no packed operand, no fused BatchNorm statistics / inference epilogue, no addend, no rider: the queries
+ *         below answer 0 and cpg_conv2d_fwd_bnstats returns CPG_E_UNSUPPORTED.  With CPG_NO_GROUPED set every entry point reports
+ *         them as CPG_E_UNSUPPORTED (workspace 0).  Measured (profiles/grouped_conv.md, batch 256): faster in every pass than one
+ *         groups == 1 call per group on channel slices, EXCEPT from 16 channels per group for 3x3 / stride 1 / pad 1 layers (forward
+ *         and input gradient 1.2 - 3 x slower: per group those run the Winograd kernels) and for strided layers (input gradient
+ *         2.5 - 4.6 x slower).  The library does not reroute these; a caller with such layers is better served by per-group calls,
+ *         as cpg_amd's SharableConv2d does.
+ * Every entry point validates the descriptor first, then the pointers (NULL: CPG_E_INVALID), then launches. */
 size_t cpg_conv2d_workspace_bytes(const cpg_conv_desc *d);
 int cpg_conv2d_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm,
                    float thr, const float *bias, float *y, void *ws, size_t ws_bytes, void *stream);
