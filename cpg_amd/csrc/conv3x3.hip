@@ -1074,14 +1074,43 @@ inline size_t pack_floats(int c_read, int m) { return ((size_t)pad_to(c_read, 4)
 inline size_t live_words(int c_read, int m) { return (size_t)pad_to(m, 128) + 4 + pad_to(c_read, 4) / 4; }
 inline size_t pack_bytes(int c_read, int m) { return (pack_floats(c_read, m) + live_words(c_read, m)) * sizeof(float); }
 
-// What a forward / input-gradient launch does besides y = conv(x).  Filled field by field; everything is optional.
+// What a forward / input-gradient call does besides y = conv(x).  Filled field by field; everything is optional.
 struct C3Extra {
     float *stats = nullptr;         // forward: [m][tiles][2] BatchNorm partial sums of y; with bb: the BatchNorm-backward partial sums
-    int *tiles_out = nullptr;       // receives the number of pixel tiles (the rows of `stats`)
-    bool dry = false;               // only compute tiles_out: nothing is launched, no pointer is touched
-    const C3BnEval *bn = nullptr;   // forward: eval-mode BatchNorm (+ ReLU) epilogue, dead-channel skip
+    const C3BnEval *bn = nullptr;   // forward: eval-mode BatchNorm (+ ReLU) epilogue (its `live` is filled in from the workspace here)
+    bool live = false;              // ... with the dead-channel skip: the pack writes the workspace's liveness words, the kernel reads them
     const C3BnBwd *bb = nullptr;    // input gradient: BatchNorm-backward reduction of the layer below in the epilogue
 };
+
+// ... the same as far as the dispatch depends on it
+enum C3Want { C3_PLAIN, C3_STATS, C3_BN_EVAL, C3_BN_BWD };
+enum C3Route { C3_WINO, C3_WINO_EVAL, C3_STEM, C3_DIRECT };
+enum C3Tile {
+    TILE_M128, TILE_M64, TILE_S16, TILE_D128, TILE_D64, TILE_V14, TILE_P28, TILE_V7,      // the Cfg* aliases above
+    TILE_S2P28, TILE_S2M8, TILE_S2S16, TILE_S2G64, TILE_S2G128                            // the strided forward's S2* aliases below
+};
+// The launch a call makes -- decided from the shape and the option table alone, so that the *_tiles queries and the entry points read
+// ONE decision.
+struct C3Plan {
+    C3Route route;
+    C3Tile tile;                    // C3_DIRECT: the tile configuration ...
+    int ksplit;                     // ... and 1, or 2: the channel chunks of a tile are shared by two blocks (C3Geom::ksplit)
+    int64_t blocks;                 // C3_DIRECT: blocks of one channel split (the launch has blocks * ksplit)
+    int tiles;                      // pixel tiles = rows per channel of the statistics buffer; 0: this launch fuses no statistics
+};
+
+// blocks = pixel tiles x tiles_m output-channel tiles (tiles cover the OUTPUT map; = the input map for the stride-1 tiles)
+template <class Cfg>
+int64_t c3_blocks(int N, int M, int OH, int OW) {
+    const int tx = (OW + Cfg::TW - 1) / Cfg::TW, ty = (OH + Cfg::TH - 1) / Cfg::TH, tm = (M + Cfg::BM - 1) / Cfg::BM;
+    return Cfg::VROWS ? (int64_t)(((int64_t)N * Cfg::TH + Cfg::VROWS - 1) / Cfg::VROWS) * tm : (int64_t)((N + Cfg::NIMG - 1) / Cfg::NIMG) * tx * ty * tm;
+}
+// the direct route's plan from its tile: no statistics from a grid the launch refuses, none on split tiles
+template <class Cfg>
+C3Plan c3_direct(C3Tile tile, int ksplit, int N, int M, int OH, int OW) {
+    const int64_t blocks = c3_blocks<Cfg>(N, M, OH, OW);
+    return C3Plan{C3_DIRECT, tile, ksplit, blocks, blocks > 0x7FFFFFFFll || ksplit > 1 ? 0 : (int)(blocks / ((M + Cfg::BM - 1) / Cfg::BM))};
+}
 
 template <class Cfg>
 int launch_fwd(C3Geom g, const float *x, const float *wp, const float *bias, float *y, hipStream_t stream, const char *what, const C3Extra &ex) {
@@ -1090,14 +1119,11 @@ int launch_fwd(C3Geom g, const float *x, const float *wp, const float *bias, flo
     const C3BnBwd *const bbp = ex.bb;
     const C3BnEval bn = bnp ? *bnp : C3BnEval{nullptr, nullptr, nullptr, nullptr, 0.0f, 0, nullptr};
     const C3BnBwd bb = bbp ? *bbp : C3BnBwd{nullptr, nullptr, nullptr, nullptr, nullptr};
-    g.tiles_x = (g.OW + Cfg::TW - 1) / Cfg::TW;           // (tiles cover the OUTPUT map; = the input map for the stride-1 tiles)
+    g.tiles_x = (g.OW + Cfg::TW - 1) / Cfg::TW;
     g.tiles_y = (g.OH + Cfg::TH - 1) / Cfg::TH;
     g.tiles_m = (g.M + Cfg::BM - 1) / Cfg::BM;
-    const int64_t blocks = Cfg::VROWS ? (int64_t)(((int64_t)g.N * Cfg::TH + Cfg::VROWS - 1) / Cfg::VROWS) * g.tiles_m
-                                      : (int64_t)((g.N + Cfg::NIMG - 1) / Cfg::NIMG) * g.tiles_x * g.tiles_y * g.tiles_m;
+    const int64_t blocks = c3_blocks<Cfg>(g.N, g.M, g.OH, g.OW);
     if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "conv3x3: grid too large");
-    if (ex.tiles_out) *ex.tiles_out = g.ksplit > 1 ? 0 : (int)(blocks / g.tiles_m);      // no fused statistics on split tiles
-    if (ex.dry) return CPG_OK;
     if (g.ksplit > 1) {
         if (stats != nullptr || bnp != nullptr || bbp != nullptr) return fail(CPG_E_UNSUPPORTED, "conv3x3: no fused epilogue on channel-split tiles");
         hipError_t e = hipMemsetAsync(y, 0, (size_t)g.N * g.M * g.OH * g.OW * sizeof(float), stream);
@@ -1122,118 +1148,103 @@ int launch_fwd(C3Geom g, const float *x, const float *wp, const float *bias, flo
     return CPG_OK;
 }
 
-// c_read / m: channels contracted over / produced.  w is the layer's [K][C][3][3] weight.
-int run_fwd(bool dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
-            float thr, const float *bias, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const C3Extra &extra = C3Extra()) {
-    const char *what = dgrad ? "cpg_conv2d_dgrad(3x3)" : "cpg_conv2d_fwd(3x3)";
-    C3Extra ex = extra;             // (ex.bn is redirected to a copy with the workspace's liveness words below)
+// c_read / m: channels contracted over / produced.  Touches no pointer, no workspace and no thread state.
+C3Plan plan_fwd(bool dgrad, int N, int c_read, int m, int H, int W, C3Want want) {
+    const bool train = want == C3_PLAIN || want == C3_STATS;
     // Winograd F(2x2, 3x3) (conv3x3_wino.hip) takes the training forward (with or without the BatchNorm statistics) and the plain
     // input gradient of every even-sized map with >= 16 channels on both sides: 2.25x fewer MFMAs, 1.36-1.47x the speed of the
     // direct kernels below.  The inference epilogues (eval BatchNorm, dead-channel skip) and BRED stay on the direct kernels.
-    if (ex.bn == nullptr && ex.bb == nullptr && cpg_conv3x3_wino_ok(N, c_read, m, H, W)) {
-        if (ex.tiles_out) *ex.tiles_out = cpg_conv3x3_wino_tiles(N, c_read, m, H, W);
-        if (ex.dry) return CPG_OK;
-        return cpg_conv3x3_wino_run(dgrad ? 1 : 0, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, ex.stats, ws, ws_bytes, stream);
-    }
-    if (!ex.dry && cpg::pack_query()) return CPG_OK;       // (cpg_conv2d_pack's query: only the Winograd route above records a job)
-    // ... and the inference forward with the eval-mode BatchNorm epilogue and the dead-channel skip (k_wg1<.., BNE>).  Workspace layout:
-    // [the direct kernels' packed-weight region (unused) | liveness words, where cpg_conv3x3_fwd_bn_eval looks for them | U]
-    if (ex.bn != nullptr && ex.bb == nullptr && !dgrad && ex.stats == nullptr && !ex.dry && cpg_conv3x3_wino_eval_ok(N, c_read, m, H, W)) {
-        const size_t off = (pack_bytes(c_read, m) + 15) / 16 * 16;
-        if (ws == nullptr || ws_bytes < off) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, off);
-        int *live = ex.bn->live != nullptr ? reinterpret_cast<int *>((float *)ws + pack_floats(c_read, m)) : nullptr;
-        return cpg_conv3x3_wino_run_bn_eval(N, c_read, m, H, W, x, w, pm, thr, bias, ex.bn->gamma, ex.bn->beta, ex.bn->mean, ex.bn->var, ex.bn->eps, ex.bn->relu,
-                                            live, live_words(c_read, m), y, (char *)ws + off, ws_bytes - off, stream);
-    }
+    if (train && cpg_conv3x3_wino_ok(N, c_read, m, H, W)) return C3Plan{C3_WINO, TILE_M128, 1, 0, cpg_conv3x3_wino_tiles(N, c_read, m, H, W)};
+    // ... and the inference forward with the eval-mode BatchNorm epilogue and the dead-channel skip (k_wg1<.., BNE>)
+    if (want == C3_BN_EVAL && !dgrad && cpg_conv3x3_wino_eval_ok(N, c_read, m, H, W)) return C3Plan{C3_WINO_EVAL, TILE_M128, 1, 0, 0};
     // the <= 3-channel stem (conv3x3_stem.hip: one persistent wave per tile, weights in registers, HBM-bound)
-    if (!dgrad && ex.bn == nullptr && ex.bb == nullptr && cpg_conv3x3_stem_ok(N, c_read, m, H, W)) {
-        if (ex.tiles_out) *ex.tiles_out = cpg_conv3x3_stem_tiles(N, c_read, m, H, W);
-        if (ex.dry) return CPG_OK;
-        return cpg_conv3x3_stem_run(N, c_read, m, H, W, x, w, pm, thr, bias, y, ex.stats, stream);
-    }
-    float *wp = (float *)ws;
-    const int rows_c = pad_to(c_read, 4), Mp = pad_to(m, 128);
-    if (!ex.dry) {
-        const size_t need = pack_bytes(c_read, m);
-        if (ws == nullptr || ws_bytes < need) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
-        CPG_REQUIRE((((uintptr_t)ws) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
-        int *live = nullptr;
-        if (ex.bn != nullptr && ex.bn->live != nullptr) {          // (bn->live is only a request flag here; the words live in the workspace)
-            live = reinterpret_cast<int *>(wp + pack_floats(c_read, m));
-            hipError_t e = hipMemsetAsync(live, 0, live_words(c_read, m) * sizeof(int), stream);
-            if (e != hipSuccess) return hip_status(e, what);
-        }
-        hipLaunchKernelGGL(k_c3_pack, dim3(stream_grid((int64_t)rows_c * 9 * Mp, 256)), dim3(256), 0, stream, w, pm, thr, wp, K, C,
-                           rows_c, Mp, dgrad ? 1 : 0, live);
-    }
-    C3BnEval bn_local;
-    if (ex.bn != nullptr) {
-        bn_local = *ex.bn;
-        bn_local.live = (ex.bn->live != nullptr && !ex.dry) ? reinterpret_cast<int *>(wp + pack_floats(c_read, m)) : nullptr;
-        ex.bn = &bn_local;
-    }
-    C3Geom g{N, c_read, H, W, m, Mp, 0, 0, 0, H, W, dgrad ? 1 : 0, 1};
+    if (!dgrad && train && cpg_conv3x3_stem_ok(N, c_read, m, H, W)) return C3Plan{C3_STEM, TILE_M128, 1, 0, cpg_conv3x3_stem_tiles(N, c_read, m, H, W)};
     if (const int force = opt(OPT_C3_FORCE); force != OPT_UNSET) {        // A/B experiments only (tools/conv_bench.py --ab)
         switch (force) {
-            case 0: return launch_fwd<CfgM128>(g, x, wp, bias, y, stream, what, ex);
-            case 1: return launch_fwd<CfgM64>(g, x, wp, bias, y, stream, what, ex);
-            case 2: return launch_fwd<CfgS16>(g, x, wp, bias, y, stream, what, ex);
-            case 3: return launch_fwd<CfgD128>(g, x, wp, bias, y, stream, what, ex);
-            case 4: return launch_fwd<CfgD64>(g, x, wp, bias, y, stream, what, ex);
-            case 7: return launch_fwd<CfgV14>(g, x, wp, bias, y, stream, what, ex);
-            case 8: g.ksplit = 2; return launch_fwd<CfgV14>(g, x, wp, bias, y, stream, what, ex);
-            default: if (c_read % 4 == 0) return launch_fwd<CfgP28>(g, x, wp, bias, y, stream, what, ex);
+            case 0: return c3_direct<CfgM128>(TILE_M128, 1, N, m, H, W);
+            case 1: return c3_direct<CfgM64>(TILE_M64, 1, N, m, H, W);
+            case 2: return c3_direct<CfgS16>(TILE_S16, 1, N, m, H, W);
+            case 3: return c3_direct<CfgD128>(TILE_D128, 1, N, m, H, W);
+            case 4: return c3_direct<CfgD64>(TILE_D64, 1, N, m, H, W);
+            case 7: return c3_direct<CfgV14>(TILE_V14, 1, N, m, H, W);
+            case 8: return c3_direct<CfgV14>(TILE_V14, 2, N, m, H, W);
+            default: if (c_read % 4 == 0) return c3_direct<CfgP28>(TILE_P28, 1, N, m, H, W);
         }
     }
-    if (W == 7 && H == 7 && c_read % 4 == 0) return launch_fwd<CfgV7>(g, x, wp, bias, y, stream, what, ex);
+    if (W == 7 && H == 7 && c_read % 4 == 0) return c3_direct<CfgV7>(TILE_V7, 1, N, m, H, W);
     // 14 x 14 maps: the 14 x 16 single-image tile wastes 1/8 of its MFMAs on two padding columns; the zero-waste virtual-row
     // tile alone measured the same, because its N*14/16 tiles put 3.5 block-equivalents on each CU, which rounds up to 4
     // (at batch 256 the layer is too small for 256 CUs).  Halving the blocks (two per tile, each half of the channel chunks,
     // atomically added into a zeroed y) makes it 7 half-blocks per CU.
-    if (W == 14 && H == 14 && m > 64 && c_read % 8 == 0 && ex.bn == nullptr && !opt_on(OPT_NO_V14)) {
+    if (W == 14 && H == 14 && m > 64 && c_read % 8 == 0 && want != C3_BN_EVAL && !opt_on(OPT_NO_V14)) {
         // ... when that balances: per-CU MFMA time in block-equivalents of either tiling (the split pays a memset, atomics
         // and a second prologue; at 256 channels and batch 256 -- 3.5 half-blocks per CU -- it measured no gain)
         const int tm = (m + 127) / 128;
         const double t_single = std::ceil((double)N * tm / kCUs) * (16.0 / 14.0);
         const double t_split = std::ceil(2.0 * (((int64_t)N * 14 + 15) / 16) * tm / kCUs) * 0.5 * 1.04;
-        if (t_split < 0.9 * t_single) {
-            g.ksplit = 2;
-            return launch_fwd<CfgV14>(g, x, wp, bias, y, stream, what, ex);
-        }
+        if (t_split < 0.9 * t_single) return c3_direct<CfgV14>(TILE_V14, 2, N, m, H, W);
     }
-    if (W <= 16 && H <= 16 && m > 64) return launch_fwd<CfgS16>(g, x, wp, bias, y, stream, what, ex);
-    if (W == 28 && H % 4 == 0 && m > 64 && c_read % 4 == 0)
-        return launch_fwd<CfgP28>(g, x, wp, bias, y, stream, what, ex);
+    if (W <= 16 && H <= 16 && m > 64) return c3_direct<CfgS16>(TILE_S16, 1, N, m, H, W);
+    if (W == 28 && H % 4 == 0 && m > 64 && c_read % 4 == 0) return c3_direct<CfgP28>(TILE_P28, 1, N, m, H, W);
     // 56, 112, 168 ...: a 32-wide tile would waste 12.5 % of the MFMAs.  The 64-channel 8 x 56 tile (2 x 2 waves) measured
     // 1-2 % faster than the 128-channel 4 x 56 tile (4 x 1 waves) on every 56- and 112-wide VGG layer, also for m > 64
     // (interleaved in-process A/B, tools/conv_bench.py --ab CPG_C3_FORCE=3,4).
     // (224-wide maps divide by 32 too; the 8 x 56 tile measured 0.8 % faster there as well -- except for the HBM-bound 3-channel
     // stem, which prefers the 8 x 32 tile by 9 %)
-    if (W % 56 == 0 && (W % 32 != 0 || c_read >= 16)) return launch_fwd<CfgD64>(g, x, wp, bias, y, stream, what, ex);
-    if (m <= 64) return launch_fwd<CfgM64>(g, x, wp, bias, y, stream, what, ex);
-    return launch_fwd<CfgM128>(g, x, wp, bias, y, stream, what, ex);
+    if (W % 56 == 0 && (W % 32 != 0 || c_read >= 16)) return c3_direct<CfgD64>(TILE_D64, 1, N, m, H, W);
+    if (m <= 64) return c3_direct<CfgM64>(TILE_M64, 1, N, m, H, W);
+    return c3_direct<CfgM128>(TILE_M128, 1, N, m, H, W);
 }
 
-int run_fwd_s2(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y, void *ws,
-               size_t ws_bytes, hipStream_t stream, const C3Extra &ex);        // (the stride-2 class, below)
-
-// Pixel tiles of the launch a call would make, from a dry run of its dispatch; 0: there is no such launch.
-enum C3Probe { PROBE_FWD, PROBE_DGRAD_BNBWD, PROBE_FWD_S2 };
-int dry_run_tiles(const cpg_conv_desc *d, C3Probe which) {
-    int tiles = 0;
-    const C3BnBwd probe{nullptr, nullptr, nullptr, nullptr, nullptr};
-    C3Extra ex;
-    ex.tiles_out = &tiles;
-    ex.dry = true;
-    if (which == PROBE_DGRAD_BNBWD) ex.bb = &probe;
-    int rc;
-    if (which == PROBE_FWD_S2)
-        rc = run_fwd_s2(d, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, 0, nullptr, ex);
-    else if (which == PROBE_FWD)
-        rc = run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, 0, nullptr, ex);
-    else           // reads gy (K channels), produces gx (C channels)
-        rc = run_fwd(true, d->N, d->K, d->C, d->H, d->W, d->K, d->C, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, 0, nullptr, ex);
-    return rc == CPG_OK ? tiles : 0;
+// w is the layer's [K][C][3][3] weight.
+int run_fwd(bool dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
+            float thr, const float *bias, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const C3Extra &extra = C3Extra()) {
+    const char *what = dgrad ? "cpg_conv2d_dgrad(3x3)" : "cpg_conv2d_fwd(3x3)";
+    C3Extra ex = extra;             // (ex.bn is redirected to a copy with the workspace's liveness words below)
+    const C3Plan plan = plan_fwd(dgrad, N, c_read, m, H, W, ex.bb ? C3_BN_BWD : ex.bn ? C3_BN_EVAL : ex.stats ? C3_STATS : C3_PLAIN);
+    if (plan.route == C3_WINO)
+        return cpg_conv3x3_wino_run(dgrad ? 1 : 0, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, ex.stats, ws, ws_bytes, stream);
+    // Workspace layout of the Winograd inference forward:
+    // [the direct kernels' packed-weight region (unused) | liveness words, where cpg_conv3x3_fwd_bn_eval looks for them | U]
+    if (plan.route == C3_WINO_EVAL) {
+        const size_t off = (pack_bytes(c_read, m) + 15) / 16 * 16;
+        if (ws == nullptr || ws_bytes < off) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, off);
+        int *live = ex.live ? reinterpret_cast<int *>((float *)ws + pack_floats(c_read, m)) : nullptr;
+        return cpg_conv3x3_wino_run_bn_eval(N, c_read, m, H, W, x, w, pm, thr, bias, ex.bn->gamma, ex.bn->beta, ex.bn->mean, ex.bn->var, ex.bn->eps, ex.bn->relu,
+                                            live, live_words(c_read, m), y, (char *)ws + off, ws_bytes - off, stream);
+    }
+    if (plan.route == C3_STEM) return cpg_conv3x3_stem_run(N, c_read, m, H, W, x, w, pm, thr, bias, y, ex.stats, stream);
+    float *wp = (float *)ws;
+    const int rows_c = pad_to(c_read, 4), Mp = pad_to(m, 128);
+    const size_t need = pack_bytes(c_read, m);
+    if (ws == nullptr || ws_bytes < need) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
+    CPG_REQUIRE((((uintptr_t)ws) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
+    int *live = nullptr;
+    if (ex.bn != nullptr && ex.live) {          // (the liveness words live in the workspace, behind the packed weights)
+        live = reinterpret_cast<int *>(wp + pack_floats(c_read, m));
+        hipError_t e = hipMemsetAsync(live, 0, live_words(c_read, m) * sizeof(int), stream);
+        if (e != hipSuccess) return hip_status(e, what);
+    }
+    hipLaunchKernelGGL(k_c3_pack, dim3(stream_grid((int64_t)rows_c * 9 * Mp, 256)), dim3(256), 0, stream, w, pm, thr, wp, K, C,
+                       rows_c, Mp, dgrad ? 1 : 0, live);
+    C3BnEval bn_local;
+    if (ex.bn != nullptr) {
+        bn_local = *ex.bn;
+        bn_local.live = live;
+        ex.bn = &bn_local;
+    }
+    C3Geom g{N, c_read, H, W, m, Mp, 0, 0, 0, H, W, dgrad ? 1 : 0, plan.ksplit};
+    switch (plan.tile) {
+        case TILE_M128: return launch_fwd<CfgM128>(g, x, wp, bias, y, stream, what, ex);
+        case TILE_M64: return launch_fwd<CfgM64>(g, x, wp, bias, y, stream, what, ex);
+        case TILE_S16: return launch_fwd<CfgS16>(g, x, wp, bias, y, stream, what, ex);
+        case TILE_D128: return launch_fwd<CfgD128>(g, x, wp, bias, y, stream, what, ex);
+        case TILE_D64: return launch_fwd<CfgD64>(g, x, wp, bias, y, stream, what, ex);
+        case TILE_V14: return launch_fwd<CfgV14>(g, x, wp, bias, y, stream, what, ex);
+        case TILE_P28: return launch_fwd<CfgP28>(g, x, wp, bias, y, stream, what, ex);
+        case TILE_V7: return launch_fwd<CfgV7>(g, x, wp, bias, y, stream, what, ex);
+        default: return fail(CPG_E_INVALID, "%s: not a stride-1 tile", what);
+    }
 }
 
 }  // namespace
@@ -1261,7 +1272,7 @@ int cpg_conv3x3_fwd(const cpg_conv_desc *d, const float *x, const float *w, cons
 }
 
 // forward that also writes the per-(channel, pixel tile) BatchNorm partial sums; tiles = cpg_conv3x3_bnstats_tiles(d)
-int cpg_conv3x3_bnstats_tiles(const cpg_conv_desc *d) { return dry_run_tiles(d, PROBE_FWD); }
+int cpg_conv3x3_bnstats_tiles(const cpg_conv_desc *d) { return plan_fwd(false, d->N, d->C, d->K, d->H, d->W, C3_STATS).tiles; }
 int cpg_conv3x3_fwd_bnstats(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                             float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream) {
     CPG_REQUIRE(x && w && y && stats, "cpg_conv2d_fwd_bnstats: null pointer");
@@ -1275,11 +1286,11 @@ int cpg_conv3x3_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float 
                             const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu, float *y,
                             int32_t *skip_stats, void *ws, size_t ws_bytes, hipStream_t stream) {
     CPG_REQUIRE(x && w && y && gamma && beta && mean && var, "cpg_conv2d_fwd_bn_eval: null pointer");
-    static int dummy;
     const bool skip = !opt_on(OPT_NO_DEAD_SKIP);
-    const C3BnEval bn{gamma, beta, mean, var, eps, relu, skip ? &dummy : nullptr};
+    const C3BnEval bn{gamma, beta, mean, var, eps, relu, nullptr};
     C3Extra ex;
     ex.bn = &bn;
+    ex.live = skip;
     int rc = run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, x, w, pm, thr, bias, y, ws, ws_bytes, stream, ex);
     if (rc == CPG_OK && skip_stats != nullptr) {
         // {4 * (input chunks up to the last live one), output blocks skipped}: device-to-device copy of the two words behind live[Mp]
@@ -1295,6 +1306,13 @@ int cpg_conv3x3_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float 
     return rc;
 }
 
+// the packed operand a caller may hand to the forward (dgrad = 0) or the input gradient: the Winograd launch's, where the pass runs there
+bool cpg_conv3x3_pack_job(const cpg_conv_desc *d, int dgrad, cpg::PackJob *job) {
+    const int c_read = dgrad ? d->K : d->C, m = dgrad ? d->C : d->K;
+    return plan_fwd(dgrad != 0, d->N, c_read, m, d->H, d->W, C3_PLAIN).route == C3_WINO &&
+           cpg_conv3x3_wino_pack_job(dgrad, d->N, c_read, m, d->H, d->W, d->K, d->C, job);
+}
+
 int cpg_conv3x3_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                       size_t ws_bytes, hipStream_t stream) {
     CPG_REQUIRE(gy && w && gx, "cpg_conv2d_dgrad: null pointer");
@@ -1304,7 +1322,9 @@ int cpg_conv3x3_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, c
 
 // input gradient whose epilogue also does the BatchNorm-backward reduction of the layer below (see C3BnBwd).  tiles = 0: this
 // shape has no such path (channel-split 14 x 14 tiles).
-int cpg_conv3x3_dgrad_bnbwd_tiles(const cpg_conv_desc *d) { return dry_run_tiles(d, PROBE_DGRAD_BNBWD); }
+int cpg_conv3x3_dgrad_bnbwd_tiles(const cpg_conv_desc *d) {
+    return plan_fwd(true, d->N, d->K, d->C, d->H, d->W, C3_BN_BWD).tiles;       // reads gy (K channels), produces gx (C channels)
+}
 int cpg_conv3x3_dgrad_bnbwd(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, const float *ypre,
                             const float *gamma, const float *beta, const float *mean, const float *invstd, float *gx, float *partials,
                             void *ws, size_t ws_bytes, hipStream_t stream) {
@@ -1442,17 +1462,14 @@ using S2G128 = C3Cfg<128, 4, 32, 2, 2, 4, 2, 1, 0, 1>;  // anything else
 using S2G64 = C3Cfg<64, 8, 32, 1, 4, 4, 2, 1, 0, 1>;    // ... with <= 64 output channels
 
 template <class Cfg>
-int launch_fwd_s2(C3Geom g, const float *x, const float *wp, const float *bias, float *y, hipStream_t stream, const C3Extra &ex) {
-    float *const stats = ex.stats;
-    const C3BnEval bn = ex.bn ? *ex.bn : C3BnEval{nullptr, nullptr, nullptr, nullptr, 0.0f, 0, nullptr};
+int launch_fwd_s2(C3Geom g, const float *x, const float *wp, const float *bias, float *y, float *stats, hipStream_t stream) {
+    const C3BnEval bn{nullptr, nullptr, nullptr, nullptr, 0.0f, 0, nullptr};
     const C3BnBwd bb{nullptr, nullptr, nullptr, nullptr, nullptr};
     g.tiles_x = (g.OW + Cfg::TW - 1) / Cfg::TW;
     g.tiles_y = (g.OH + Cfg::TH - 1) / Cfg::TH;
     g.tiles_m = (g.M + Cfg::BM - 1) / Cfg::BM;
-    const int64_t blocks = (int64_t)((g.N + Cfg::NIMG - 1) / Cfg::NIMG) * g.tiles_x * g.tiles_y * g.tiles_m;
+    const int64_t blocks = c3_blocks<Cfg>(g.N, g.M, g.OH, g.OW);
     if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "conv3x3 s2: grid too large");
-    if (ex.tiles_out) *ex.tiles_out = (int)(blocks / g.tiles_m);
-    if (ex.dry) return CPG_OK;
     if (stats != nullptr)
         hipLaunchKernelGGL((k_c3_fwd<Cfg, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, stats, bn, bb);
     else
@@ -1463,26 +1480,35 @@ int launch_fwd_s2(C3Geom g, const float *x, const float *wp, const float *bias, 
 
 inline int s2_out(int v) { return (v - 1) / 2 + 1; }
 
-int run_fwd_s2(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y, void *ws,
-               size_t ws_bytes, hipStream_t stream, const C3Extra &ex) {
+// the strided forward's launch (one route: the direct kernel's strided tiles), decided from the descriptor alone
+C3Plan plan_fwd_s2(const cpg_conv_desc *d) {
+    const int N = d->N, K = d->K, OH = s2_out(d->H), OW = s2_out(d->W);
+    if (OW == 28 && OH % 4 == 0 && K > 64) return c3_direct<S2P28>(TILE_S2P28, 1, N, K, OH, OW);
+    if (OW <= 8 && OH <= 8 && K > 64) return c3_direct<S2M8>(TILE_S2M8, 1, N, K, OH, OW);
+    if (OW <= 16 && OH <= 16 && K > 64) return c3_direct<S2S16>(TILE_S2S16, 1, N, K, OH, OW);
+    if (K <= 64) return c3_direct<S2G64>(TILE_S2G64, 1, N, K, OH, OW);
+    return c3_direct<S2G128>(TILE_S2G128, 1, N, K, OH, OW);
+}
+
+int run_fwd_s2(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y, float *stats,
+               void *ws, size_t ws_bytes, hipStream_t stream) {
     const char *what = "cpg_conv2d_fwd(3x3 s2)";
-    const bool dry = ex.dry;
-    const int OH = s2_out(d->H), OW = s2_out(d->W);
     float *wp = (float *)ws;
     const int rows_c = pad_to(d->C, 4), Mp = pad_to(d->K, 128);
-    if (!dry) {
-        const size_t need = pack_bytes(d->C, d->K);
-        if (ws == nullptr || ws_bytes < need) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
-        CPG_REQUIRE((((uintptr_t)ws) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
-        hipLaunchKernelGGL(k_c3_pack, dim3(stream_grid((int64_t)rows_c * 9 * Mp, 256)), dim3(256), 0, stream, w, pm, thr, wp, d->K, d->C,
-                           rows_c, Mp, 0, (int *)nullptr);
+    const size_t need = pack_bytes(d->C, d->K);
+    if (ws == nullptr || ws_bytes < need) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
+    CPG_REQUIRE((((uintptr_t)ws) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
+    hipLaunchKernelGGL(k_c3_pack, dim3(stream_grid((int64_t)rows_c * 9 * Mp, 256)), dim3(256), 0, stream, w, pm, thr, wp, d->K, d->C,
+                       rows_c, Mp, 0, (int *)nullptr);
+    C3Geom g{d->N, d->C, d->H, d->W, d->K, Mp, 0, 0, 0, s2_out(d->H), s2_out(d->W), 0, 1};
+    switch (plan_fwd_s2(d).tile) {
+        case TILE_S2P28: return launch_fwd_s2<S2P28>(g, x, wp, bias, y, stats, stream);
+        case TILE_S2M8: return launch_fwd_s2<S2M8>(g, x, wp, bias, y, stats, stream);
+        case TILE_S2S16: return launch_fwd_s2<S2S16>(g, x, wp, bias, y, stats, stream);
+        case TILE_S2G64: return launch_fwd_s2<S2G64>(g, x, wp, bias, y, stats, stream);
+        case TILE_S2G128: return launch_fwd_s2<S2G128>(g, x, wp, bias, y, stats, stream);
+        default: return fail(CPG_E_INVALID, "%s: not a stride-2 tile", what);
     }
-    C3Geom g{d->N, d->C, d->H, d->W, d->K, Mp, 0, 0, 0, OH, OW, 0, 1};
-    if (OW == 28 && OH % 4 == 0 && d->K > 64) return launch_fwd_s2<S2P28>(g, x, wp, bias, y, stream, ex);
-    if (OW <= 8 && OH <= 8 && d->K > 64) return launch_fwd_s2<S2M8>(g, x, wp, bias, y, stream, ex);
-    if (OW <= 16 && OH <= 16 && d->K > 64) return launch_fwd_s2<S2S16>(g, x, wp, bias, y, stream, ex);
-    if (d->K <= 64) return launch_fwd_s2<S2G64>(g, x, wp, bias, y, stream, ex);
-    return launch_fwd_s2<S2G128>(g, x, wp, bias, y, stream, ex);
 }
 
 //                  BM  WM WN TH TW NIMG
@@ -1517,13 +1543,11 @@ extern "C" int cpg_conv3x3s2_supported(const cpg_conv_desc *d) {
            (int64_t)d->C * d->H * d->W < (1ll << 27) && (int64_t)d->K * d->H * d->W < (1ll << 27) && (int64_t)d->H * d->W <= (1ll << 22);
 }
 size_t cpg_conv3x3s2_pack_workspace(const cpg_conv_desc *d) { return std::max(pack_bytes(d->C, d->K), pack_bytes(d->K, d->C)) + 16; }
-int cpg_conv3x3s2_bnstats_tiles(const cpg_conv_desc *d) { return dry_run_tiles(d, PROBE_FWD_S2); }
+int cpg_conv3x3s2_bnstats_tiles(const cpg_conv_desc *d) { return plan_fwd_s2(d).tiles; }
 int cpg_conv3x3s2_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y,
                       float *stats, void *ws, size_t ws_bytes, hipStream_t stream) {
     CPG_REQUIRE(x && w && y, "cpg_conv2d_fwd: null pointer");
-    C3Extra ex;
-    ex.stats = stats;
-    return run_fwd_s2(d, x, w, pm, thr, bias, y, ws, ws_bytes, stream, ex);
+    return run_fwd_s2(d, x, w, pm, thr, bias, y, stats, ws, ws_bytes, stream);
 }
 int cpg_conv3x3s2_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                         size_t ws_bytes, hipStream_t stream) {

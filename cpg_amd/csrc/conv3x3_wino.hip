@@ -1954,6 +1954,21 @@ static inline int wino_variant(int c_read, int m, bool stats) {
     return p64 * 10 > p32 * 11 ? WV_WAVE : WV_PAIR64;
 }
 
+// The packed operand of a forward / input-gradient launch of the one- and two-wave kernels: the per-lane transformed filter U in
+// k_wg1_pack's layout, cpg_conv3x3_wino_pack_bytes(c_read, m) bytes.  w is the layer's [K][C][3][3] weight.
+static cpg::PackJob wino_pack_job(int dgrad, int c_read, int m, int K, int C) {
+    const int nch = pad_to(c_read, WG_CK) / WG_CK;
+    return cpg::PackJob{2, K, C, m, c_read, nch, dgrad ? 1 : 0, (long long)((m + 31) / 32) * nch * 32 * WG_CK, cpg_conv3x3_wino_pack_bytes(c_read, m)};
+}
+// ... of the launch cpg_conv3x3_wino_run would make; false: that launch streams no operand a caller could hand in -- a shape
+// cpg_conv3x3_wino_ok refuses, or the cooperative block kernel (CPG_WINO_KERNEL=block), which packs for itself
+bool cpg_conv3x3_wino_pack_job(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, cpg::PackJob *job) {
+    if (!cpg_conv3x3_wino_ok(N, c_read, m, H, W)) return false;
+    if (!((H | W) & 1) && wino_variant(c_read, m) == WV_BLOCK) return false;
+    *job = wino_pack_job(dgrad, c_read, m, K, C);
+    return true;
+}
+
 #ifdef WG_TIMING
 extern "C" int cpg_debug_wg_timing(unsigned long long *dst, int n) {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(wg_dbg), (size_t)n * 8 * sizeof(unsigned long long));
@@ -2089,19 +2104,17 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
         wino_geom(g, N, c_read, m, H, W);
         float *up = (float *)ws;
         const WgBnEval none{nullptr, nullptr, nullptr, nullptr, 0.0f, 0, nullptr, 0};
-        int ps = 0;
+        const float *pre = nullptr;
         if (bne == nullptr) {      // (the inference epilogue's pack also writes the liveness flags: never taken from a caller's operand)
-            const float *pre = nullptr;
-            ps = cpg::pack_site(cpg::PackJob{2, K, C, m, c_read, g.nch, dgrad ? 1 : 0, (long long)((m + 31) / 32) * g.nch * 32 * WG_CK, need}, &pre, what);
-            if (ps == 1) return CPG_OK;
-            if (ps < 0) return ps;
-            if (ps == 2) up = const_cast<float *>(pre);
-        } else if (cpg::pack_query()) {
-            return CPG_OK;
+            if (const int rc = cpg::take_packed(need, &pre, what)) return rc;
         }
-        if (ps != 2)
-            hipLaunchKernelGGL(k_wg1_pack, dim3(stream_grid((int64_t)g.nkb * g.nch * 32 * WG_CK, 256)), dim3(256), 0, stream, w, pm, thr, up,
-                               K, C, m, c_read, g.nch, dgrad ? 1 : 0, bne ? bne->live : nullptr, bne ? bne->Mp : 0);
+        if (pre != nullptr) {
+            up = const_cast<float *>(pre);
+        } else {
+            const cpg::PackJob job = wino_pack_job(dgrad, c_read, m, K, C);
+            hipLaunchKernelGGL(k_wg1_pack, dim3(stream_grid(job.total, 256)), dim3(256), 0, stream, w, pm, thr, up, K, C, m, c_read, job.c,
+                               job.d, bne ? bne->live : nullptr, bne ? bne->Mp : 0);
+        }
         const int64_t runs = (g.tiles_total + W1_T - 1) / W1_T;
         const bool persist = wino_persist();
         const WgMode mode = bne != nullptr ? WG_FWD_BNE : dgrad ? (addend != nullptr ? WG_DGRAD_ADD : WG_DGRAD) : stats != nullptr ? WG_FWD_STATS : WG_FWD;
@@ -2204,7 +2217,6 @@ static int wg1_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
 
 static int wino_run_block(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
                           float thr, const float *bias, float *y, float *stats, void *ws, hipStream_t stream, const char *what) {
-    if (cpg::pack_query()) return CPG_OK;        // (the block kernels pack for themselves: no job recorded)
     const int nw = wino_nw(c_read, m), BK = 8 * nw;
     WgGeom g;
     g.N = N, g.C = c_read, g.H = H, g.W = W, g.M = m;

@@ -23,22 +23,16 @@ PackCtx &pack_ctx() { return g_pack; }
 static thread_local WgradRider g_rider = {};
 WgradRider &wgrad_rider() { return g_rider; }
 
-int pack_site(const PackJob &job, const float **pre, const char *what) {
+int take_packed(size_t bytes, const float **pre, const char *what) {
     PackCtx &c = g_pack;
-    if (c.mode == PACK_QUERY) {
-        c.job = job;
-        c.hit = true;
-        return 1;
-    }
-    if (c.mode == PACK_USE && !c.hit) {
-        if (c.use == nullptr || c.use_bytes != job.bytes || (((uintptr_t)c.use) & 15) != 0)
-            return fail(CPG_E_INVALID, "%s: the packed operand handed in (%zu bytes) is not the one this launch streams (%zu bytes, 16-byte aligned)",
-                        what, c.use_bytes, job.bytes);
-        *pre = c.use;
-        c.hit = true;
-        return 2;
-    }
-    return 0;
+    *pre = nullptr;
+    if (!c.armed) return CPG_OK;
+    if (c.use == nullptr || c.use_bytes != bytes || (((uintptr_t)c.use) & 15) != 0)
+        return fail(CPG_E_INVALID, "%s: the packed operand handed in (%zu bytes) is not the one this launch streams (%zu bytes, 16-byte aligned)",
+                    what, c.use_bytes, bytes);
+    *pre = c.use;
+    c.armed = false;
+    return CPG_OK;
 }
 
 // Process-wide: the weight-gradient planners that read it run inside autograd's backward, i.e. on the engine's per-device worker

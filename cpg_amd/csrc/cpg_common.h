@@ -64,8 +64,8 @@ inline int opt_or(Opt o, int dflt) { const int v = opt(o); return v == OPT_UNSET
 // The pointwise and the one-/two-wave Winograd kernels stream the effective weight W * bin(pm) from a packed copy that every call used
 // to produce into its own workspace first.  A caller may now produce it ONCE (and the forward's and the input gradient's in one launch)
 // and hand it to the calls that need it.  The plumbing is a per-THREAD one-shot context: cpg_conv2d_use_packed arms it, the next conv
-// entry point on that thread consumes (or drops) it; the same context in QUERY mode is how cpg_conv2d_pack finds out what a call of
-// this shape would pack -- the call runs to its pack site, records the job and returns before anything is launched.
+// entry point on that thread consumes (or drops) it.  What a call of a shape would pack is a pure function of the descriptor and the
+// option table (the *_pack_job planners of cpg_dispatch.h): cpg_conv2d_pack and cpg_conv2d_pack_bytes ask them and touch no context.
 struct PackJob {
     int family;               // 0 none, 1 pointwise (k_pw_pack's layout), 2 Winograd per-lane U (k_wg1_pack's layout)
     int K, C;                 // the layer's weight is [K][C][R][S]
@@ -73,19 +73,15 @@ struct PackJob {
     long long total;          // work items of the pack pass
     size_t bytes;             // size of the packed operand
 };
-enum { PACK_NONE = 0, PACK_QUERY = 1, PACK_USE = 2 };
 struct PackCtx {
-    int mode;
-    bool hit;                 // QUERY: a job was recorded;  USE: the operand was consumed
-    PackJob job;
+    bool armed;               // cpg_conv2d_use_packed handed `use` in and no launch has taken it yet
     const float *use;
     size_t use_bytes;
 };
 PackCtx &pack_ctx();          // thread-local
-inline bool pack_query() { return pack_ctx().mode == PACK_QUERY; }
-// At a pack site: 0 = pack into the workspace as always; 1 = QUERY (job recorded: return CPG_OK now); 2 = *pre is the caller's operand
-// (skip the pack); < 0 = the caller's operand does not fit this launch (status to return).
-int pack_site(const PackJob &job, const float **pre, const char *what);
+// Where a launch is about to pack `bytes` of operand into its workspace: *pre = the operand the caller armed (skip the pack), or null
+// (pack as always).  < 0: the caller's operand does not fit this launch (status to return).
+int take_packed(size_t bytes, const float **pre, const char *what);
 // one launch that carries out up to two jobs (conv3x3_wino.hip)
 int pack_jobs_launch(const PackJob *ja, float *dst_a, const PackJob *jb, float *dst_b, const float *w, const float *pm, float thr,
                      hipStream_t stream);

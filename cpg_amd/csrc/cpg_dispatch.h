@@ -23,6 +23,9 @@ int cpg_conv3x3_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float 
                             int32_t *skip_stats, void *ws, size_t ws_bytes, hipStream_t stream);
 int cpg_conv3x3_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                       size_t ws_bytes, hipStream_t stream);
+// the packed operand cpg_conv3x3_fwd / _fwd_bnstats (dgrad = 0) or cpg_conv3x3_dgrad streams and a caller may hand in (cpg_conv2d_use_packed);
+// false: none (the pass runs a direct kernel, or a Winograd kernel that packs for itself)
+bool cpg_conv3x3_pack_job(const cpg_conv_desc *d, int dgrad, cpg::PackJob *job);
 // input gradient whose epilogue also does the BatchNorm-backward reduction of the layer below; tiles = 0: this shape has no such path
 int cpg_conv3x3_dgrad_bnbwd_tiles(const cpg_conv_desc *d);
 int cpg_conv3x3_dgrad_bnbwd(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, const float *ypre,
@@ -56,6 +59,9 @@ extern "C" size_t cpg_conv3x3_wino_pack_bytes(int c_read, int m);
 extern "C" size_t cpg_conv3x3_wino_tail_bytes(int N, int c_read, int m, int H, int W);
 // BatchNorm-statistics tiles per channel of a forward launch (stats[m][tiles][2])
 extern "C" int cpg_conv3x3_wino_tiles(int N, int c_read, int m, int H, int W);
+// the packed operand of the launch cpg_conv3x3_wino_run would make; false: none a caller could hand in (a shape cpg_conv3x3_wino_ok
+// refuses; the cooperative block kernel, which packs for itself)
+bool cpg_conv3x3_wino_pack_job(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, cpg::PackJob *job);
 // y[N][m][H][W] = conv3x3(x[N][c_read][H][W], W .* bin(pm)) (+ bias); dgrad: x = gy, the filter transposed and flipped.
 // w is the layer's [K][C][3][3] weight.  stats (forward only, may be null): [m][tiles][2]
 extern "C" int cpg_conv3x3_wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w,
@@ -117,6 +123,8 @@ int cpg_conv_grouped_wgrad(const cpg_conv_desc *d, const float *x, const float *
 // 1: the pointwise kernels take this shape's forward and input gradient (CPG_DISABLE_CONV1X1: never)
 extern "C" int cpg_conv1x1_supported(const cpg_conv_desc *d);
 size_t cpg_conv1x1_pack_workspace(const cpg_conv_desc *d);
+// the packed operand of cpg_conv1x1_fwd (dgrad = 0) / cpg_conv1x1_dgrad
+cpg::PackJob cpg_conv1x1_pack_job(const cpg_conv_desc *d, int dgrad);
 // stats (may be null): [K][tiles][2] BatchNorm partial sums, tiles = cpg_conv1x1_bnstats_tiles(d)
 int cpg_conv1x1_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                     float *y, void *ws, size_t ws_bytes, hipStream_t stream, float *stats = nullptr);

@@ -647,13 +647,10 @@ extern "C" int cpg_conv2d_dgrad_generic(const cpg_conv_desc *d, const float *gy,
 }
 
 // Drops the calling thread's packed-operand context when a conv entry point returns, whether or not the launch consumed it
-// (cpg_conv2d_use_packed is one-shot).  QUERY mode is cpg_conv2d_pack's own and is cleared by it.
+// (cpg_conv2d_use_packed is one-shot).
 namespace {
 struct PackScope {
-    ~PackScope() {
-        cpg::PackCtx &c = cpg::pack_ctx();
-        if (c.mode == cpg::PACK_USE) c = cpg::PackCtx{};
-    }
+    ~PackScope() { cpg::pack_ctx() = cpg::PackCtx{}; }
 };
 }  // namespace
 
@@ -663,7 +660,6 @@ extern "C" int cpg_conv2d_fwd(const cpg_conv_desc *d, const float *x, const floa
     const ConvRoute route = fwd_route(d);
     if (route == ROUTE_C3) return cpg_conv3x3_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream);
     if (route == ROUTE_C1) return cpg_conv1x1_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream);
-    if (cpg::pack_query()) return CPG_OK;        // (only the two routes above have pack sites)
     if (route == ROUTE_C3S2) return cpg_conv3x3s2_fwd(d, x, w, pm, thr, bias, y, nullptr, ws, ws_bytes, (hipStream_t)stream);
     if (route == ROUTE_STEM2) return cpg_conv_stem2_fwd(d, x, w, pm, thr, bias, y, nullptr, (hipStream_t)stream);
     if (route == ROUTE_GROUPED) {
@@ -702,7 +698,6 @@ extern "C" int cpg_conv2d_fwd_bnstats(const cpg_conv_desc *d, const float *x, co
         case ROUTE_C1: return cpg_conv1x1_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream, stats);
         default: break;
     }
-    if (cpg::pack_query()) return CPG_OK;        // (only the two routes above have pack sites)
     if (route == ROUTE_C3S2) return cpg_conv3x3s2_fwd(d, x, w, pm, thr, bias, y, stats, ws, ws_bytes, (hipStream_t)stream);
     return cpg_conv_stem2_fwd(d, x, w, pm, thr, bias, y, stats, (hipStream_t)stream);
 }
@@ -711,7 +706,7 @@ extern "C" int32_t cpg_conv2d_winograd(const cpg_conv_desc *d, int32_t dgrad) {
     ConvGeom g;
     if (d == nullptr || make_geom(d, g) != CPG_OK || !cpg_conv3x3_supported(d)) return 0;
     if (dgrad == 2) return use_c3_wgrad(d) ? cpg_conv3x3_wino_wgrad_ok(d) : 0;
-    if (dgrad == 3) return cpg_conv3x3_wino_eval_ok(d->N, d->C, d->K, d->H, d->W);      // the dispatch rule of run_fwd(bn != nullptr)
+    if (dgrad == 3) return cpg_conv3x3_wino_eval_ok(d->N, d->C, d->K, d->H, d->W);      // the rule of conv3x3.hip's plan_fwd(C3_BN_EVAL)
     return dgrad ? cpg_conv3x3_wino_ok(d->N, d->K, d->C, d->H, d->W) : cpg_conv3x3_wino_ok(d->N, d->C, d->K, d->H, d->W);
 }
 
@@ -757,7 +752,6 @@ extern "C" int cpg_conv2d_dgrad(const cpg_conv_desc *d, const float *gy, const f
     const ConvRoute route = fwd_route(d);
     if (route == ROUTE_C3) return cpg_conv3x3_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream);
     if (route == ROUTE_C1) return cpg_conv1x1_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream);
-    if (cpg::pack_query()) return CPG_OK;        // (only the two routes above have pack sites)
     if (route == ROUTE_C3S2) return cpg_conv3x3s2_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream);
     if (route == ROUTE_GROUPED) {
         ConvGeom g;
@@ -789,33 +783,18 @@ extern "C" int cpg_conv2d_dgrad_add(const cpg_conv_desc *d, const float *gy, con
 
 // ---- caller-owned packed weight operands (include/cpg_hip.h, ABI 3) ------------------------------------------------------------------
 namespace {
-// What a call of this pass would pack: run the REAL dispatch in query mode -- it stops at the pack site.  Only shape classes whose every
-// route ends at a hooked site may enter (3x3 s1 p1 layers on the Winograd kernels, pointwise layers): the pointers below are never
-// dereferenced, but a route without a site would launch on them.
+// What a call of this pass (0 forward, 1 input gradient, 2 forward with the BatchNorm statistics) would pack: the route of the pass, then
+// that route's planner.  Reads the descriptor and the option table only.
 bool query_pack_job(const cpg_conv_desc *d, int pass, cpg::PackJob *out) {
     ConvGeom g;
     if (d == nullptr || pass < 0 || pass > 2 || make_geom(d, g) != CPG_OK) return false;
-    if (d->N <= 0 || d->K <= 0 || d->C <= 0) return false;
-    bool eligible = false;
-    if (cpg_conv3x3_supported(d))
-        eligible = cpg_conv2d_winograd(d, pass == 1 ? 1 : 0) != 0;
-    else if (cpg_conv1x1_supported(d))
-        eligible = true;
-    if (!eligible || (pass == 2 && cpg_conv2d_bnstats_tiles(d) <= 0)) return false;
-    float *const fake = reinterpret_cast<float *>((uintptr_t)1 << 20);
-    const size_t big = (size_t)1 << 46;
-    cpg::PackCtx &c = cpg::pack_ctx();
-    c = cpg::PackCtx{};
-    c.mode = cpg::PACK_QUERY;
-    const int rc = pass == 1   ? cpg_conv2d_dgrad(d, fake, fake, nullptr, 0.0f, fake, fake, big, nullptr)
-                   : pass == 2 ? cpg_conv2d_fwd_bnstats(d, fake, fake, nullptr, 0.0f, nullptr, fake, fake, big, fake, big, nullptr)
-                               : cpg_conv2d_fwd(d, fake, fake, nullptr, 0.0f, nullptr, fake, fake, big, nullptr);
-    const bool hit = c.hit;
-    const cpg::PackJob job = c.job;
-    c = cpg::PackCtx{};
-    if (rc != CPG_OK || !hit || job.family == 0) return false;
-    *out = job;
-    return true;
+    const ConvRoute route = fwd_route(d);
+    if (pass == 2 && bnstats_tiles(d, route) <= 0) return false;
+    switch (route) {
+        case ROUTE_C3: return cpg_conv3x3_pack_job(d, pass == 1 ? 1 : 0, out);
+        case ROUTE_C1: *out = cpg_conv1x1_pack_job(d, pass == 1 ? 1 : 0); return true;
+        default: return false;                    // (the other routes stream no packed operand a caller could supply)
+    }
 }
 }  // namespace
 
@@ -839,12 +818,7 @@ extern "C" int cpg_conv2d_pack(const cpg_conv_desc *d, const float *w, const flo
 }
 
 extern "C" int cpg_conv2d_use_packed(const void *packed, size_t bytes) {
-    cpg::PackCtx &c = cpg::pack_ctx();
-    c = cpg::PackCtx{};
-    if (packed == nullptr) return CPG_OK;        // (disarms)
-    c.mode = cpg::PACK_USE;
-    c.use = (const float *)packed;
-    c.use_bytes = bytes;
+    cpg::pack_ctx() = cpg::PackCtx{packed != nullptr, (const float *)packed, bytes};       // (null disarms)
     return CPG_OK;
 }
 

@@ -780,69 +780,81 @@ extern "C" int cpg_conv1x1_supported(const cpg_conv_desc *d) {
 
 size_t cpg_conv1x1_pack_workspace(const cpg_conv_desc *d) { return std::max(pack_bytes(d->C, d->K), pack_bytes(d->K, d->C)); }
 
-// pixel tiles of the forward launch = rows of the [K][tiles][2] statistics buffer of cpg_conv2d_fwd_bnstats.  The launch below derives
-// the same tile from the same inputs (K, stride, plane size, CPG_PW_TILE); where the wide tile additionally needs a 16-byte aligned input
-// it REFUSES a fused-statistics launch on an unaligned one instead of falling back to another tile size.  CPG_PW_TILE is A/B tooling:
-// like every planner switch it must not change between a query and the launch it sized (include/cpg_hip.h).
+// The forward's tile: <= 64 output channels, the wide tile (CPG_PW_TILE), or the 224-pixel tile; float4 staging (dense reads of planes
+// that are multiples of 4 pixels, from a 16-byte aligned x) or per-pixel staging.  The wide tile has no per-pixel flavour.
+namespace {
+enum PwTile { PW_V64, PW_S64, PW_V2, PW_V, PW_S };
+PwTile pw_fwd_tile(const cpg_conv_desc *d, bool x_aligned) {
+    const int OH = (d->H - 1) / d->stride_h + 1, OW = (d->W - 1) / d->stride_w + 1;
+    const bool vec = d->stride_h == 1 && d->stride_w == 1 && (OH * OW) % 4 == 0 && x_aligned;
+    if (d->K <= 64) return vec ? PW_V64 : PW_S64;
+    if (vec) return pw_wide() ? PW_V2 : PW_V;
+    return PW_S;
+}
+constexpr int pw_tile_pixels(PwTile t) { return t == PW_V64 || t == PW_S64 ? PwV64::BN : t == PW_V2 ? PwV2::BN : PwV::BN; }
+static_assert(PwV::BN == PwS::BN && PwV64::BN == PwS64::BN, "only the wide tile's pixel count depends on the input's alignment");
+}  // namespace
+
+// pixel tiles of the forward launch = rows of the [K][tiles][2] statistics buffer of cpg_conv2d_fwd_bnstats: those of the tile an aligned
+// input gets.  Where that is the wide tile, the launch REFUSES fused statistics on an unaligned input instead of falling back to another
+// tile size.  CPG_PW_TILE is A/B tooling: like every planner switch it must not change between a query and the launch it sized
+// (include/cpg_hip.h).
 int cpg_conv1x1_bnstats_tiles(const cpg_conv_desc *d) {
     const int OH = (d->H - 1) / d->stride_h + 1, OW = (d->W - 1) / d->stride_w + 1;
-    const bool wide = pw_wide() && d->stride_h == 1 && d->stride_w == 1 && (OH * OW) % 4 == 0;
-    const int bn = d->K <= 64 ? PwV64::BN : (wide ? PwV2::BN : PwV::BN);
+    const int bn = pw_tile_pixels(pw_fwd_tile(d, true));
     return (int)(((int64_t)d->N * OH * OW + bn - 1) / bn);
 }
+
+// the packed operand of cpg_conv1x1_fwd / cpg_conv1x1_dgrad: the effective weight K-major, [channels read, padded to 16 (+ 16 rows of
+// slack)][channels produced, padded to 128]
+cpg::PackJob cpg_conv1x1_pack_job(const cpg_conv_desc *d, int dgrad) {
+    const int c_read = dgrad ? d->K : d->C, m = dgrad ? d->C : d->K;
+    const int rows = pad_to(c_read, 16), Mp = pad_to(m, 128);
+    return cpg::PackJob{1, d->K, d->C, rows, Mp, dgrad, 0, (long long)rows * Mp, pack_bytes(c_read, m)};
+}
+
+namespace {
+// *wp = the operand the launch streams: the caller's (cpg_conv2d_use_packed), or the one packed here into the workspace
+int pw_packed_operand(const cpg_conv_desc *d, int dgrad, const float *w, const float *pm, float thr, void *ws, size_t ws_bytes, hipStream_t stream,
+                      const char *what, const float **wp) {
+    const cpg::PackJob job = cpg_conv1x1_pack_job(d, dgrad);
+    if (ws == nullptr || ws_bytes < job.bytes) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, job.bytes);
+    CPG_REQUIRE((((uintptr_t)ws) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
+    const int rc = cpg::take_packed(job.bytes, wp, what);
+    if (rc != CPG_OK || *wp != nullptr) return rc;
+    hipLaunchKernelGGL(k_pw_pack, dim3(stream_grid(job.total, 256)), dim3(256), 0, stream, w, pm, thr, (float *)ws, d->K, d->C, job.a, job.b, dgrad);
+    *wp = (const float *)ws;
+    return CPG_OK;
+}
+}  // namespace
 
 int cpg_conv1x1_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                     float *y, void *ws, size_t ws_bytes, hipStream_t stream, float *stats) {
     const char *what = "cpg_conv2d_fwd(1x1)";
     CPG_REQUIRE(x && w && y, "%s: null pointer", what);
-    const size_t need = pack_bytes(d->C, d->K);
-    if (ws == nullptr || ws_bytes < need) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
-    CPG_REQUIRE((((uintptr_t)ws) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
-    float *wp = (float *)ws;
-    const int rows = pad_to(d->C, 16), Mp = pad_to(d->K, 128);
-    {
-        const float *pre = nullptr;
-        const int ps = cpg::pack_site(cpg::PackJob{1, d->K, d->C, rows, Mp, 0, 0, (long long)rows * Mp, need}, &pre, what);
-        if (ps == 1) return CPG_OK;
-        if (ps < 0) return ps;
-        if (ps == 2)
-            wp = const_cast<float *>(pre);
-        else
-            hipLaunchKernelGGL(k_pw_pack, dim3(stream_grid((int64_t)rows * Mp, 256)), dim3(256), 0, stream, w, pm, thr, wp, d->K, d->C, rows, Mp, 0);
-    }
+    const float *wp = nullptr;
+    if (const int rc = pw_packed_operand(d, 0, w, pm, thr, ws, ws_bytes, stream, what, &wp)) return rc;
     const int OH = (d->H - 1) / d->stride_h + 1, OW = (d->W - 1) / d->stride_w + 1;
-    PwGeom g{d->N, d->C, d->K, Mp, OW, OH * OW, d->H * d->W, d->stride_h * d->W, d->stride_w, OH * OW, OW, 1, 0, (long long)d->N * OH * OW};
-    const bool dense = d->stride_h == 1 && d->stride_w == 1;
-    static_assert(PwV::BN == PwS::BN && PwV64::BN == PwS64::BN, "cpg_conv1x1_bnstats_tiles counts tiles of either staging flavour");
-    const bool vec = dense && (OH * OW) % 4 == 0 && (((uintptr_t)x) & 15) == 0;
-    if (d->K <= 64) return vec ? launch<PwV64, false>(g, x, wp, bias, y, stream, what, stats) : launch<PwS64, false>(g, x, wp, bias, y, stream, what, stats);
-    if (pw_wide() && dense && (OH * OW) % 4 == 0) {
-        CPG_REQUIRE(vec || stats == nullptr, "%s: the fused-statistics launch needs a 16-byte aligned input", what);
-        if (vec) return launch<PwV2, false>(g, x, wp, bias, y, stream, what, stats);
+    PwGeom g{d->N, d->C, d->K, pad_to(d->K, 128), OW, OH * OW, d->H * d->W, d->stride_h * d->W, d->stride_w, OH * OW, OW, 1, 0, (long long)d->N * OH * OW};
+    const PwTile tile = pw_fwd_tile(d, (((uintptr_t)x) & 15) == 0);
+    // (the statistics buffer was sized by cpg_conv1x1_bnstats_tiles: only an unaligned input under the wide tile gets another tile size)
+    CPG_REQUIRE(stats == nullptr || pw_tile_pixels(tile) == pw_tile_pixels(pw_fwd_tile(d, true)),
+                "%s: the fused-statistics launch needs a 16-byte aligned input", what);
+    switch (tile) {
+        case PW_V64: return launch<PwV64, false>(g, x, wp, bias, y, stream, what, stats);
+        case PW_S64: return launch<PwS64, false>(g, x, wp, bias, y, stream, what, stats);
+        case PW_V2: return launch<PwV2, false>(g, x, wp, bias, y, stream, what, stats);
+        case PW_V: return launch<PwV, false>(g, x, wp, bias, y, stream, what, stats);
+        default: return launch<PwS, false>(g, x, wp, bias, y, stream, what, stats);
     }
-    if (vec) return launch<PwV, false>(g, x, wp, bias, y, stream, what, stats);
-    return launch<PwS, false>(g, x, wp, bias, y, stream, what, stats);
 }
 
 int cpg_conv1x1_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                       size_t ws_bytes, hipStream_t stream, const float *addend) {
     const char *what = "cpg_conv2d_dgrad(1x1)";
     CPG_REQUIRE(gy && w && gx, "%s: null pointer", what);
-    const size_t need = pack_bytes(d->K, d->C);
-    if (ws == nullptr || ws_bytes < need) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
-    CPG_REQUIRE((((uintptr_t)ws) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
-    float *wp = (float *)ws;
-    const int rows = pad_to(d->K, 16), Mp = pad_to(d->C, 128);
-    {
-        const float *pre = nullptr;
-        const int ps = cpg::pack_site(cpg::PackJob{1, d->K, d->C, rows, Mp, 1, 0, (long long)rows * Mp, need}, &pre, what);
-        if (ps == 1) return CPG_OK;
-        if (ps < 0) return ps;
-        if (ps == 2)
-            wp = const_cast<float *>(pre);
-        else
-            hipLaunchKernelGGL(k_pw_pack, dim3(stream_grid((int64_t)rows * Mp, 256)), dim3(256), 0, stream, w, pm, thr, wp, d->K, d->C, rows, Mp, 1);
-    }
+    const float *wp = nullptr;
+    if (const int rc = pw_packed_operand(d, 1, w, pm, thr, ws, ws_bytes, stream, what, &wp)) return rc;
     const int OH = (d->H - 1) / d->stride_h + 1, OW = (d->W - 1) / d->stride_w + 1;
     const bool dense = d->stride_h == 1 && d->stride_w == 1;
     if (!dense) {       // positions the strided conv never read receive no gradient
@@ -850,7 +862,7 @@ int cpg_conv1x1_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, c
         if (e != hipSuccess) return hip_status(e, what);
     }
     // reads gy (K channels, dense over the output grid), produces gx (C channels) at the strided positions
-    PwGeom g{d->N, d->K, d->C, Mp, OW, OH * OW, OH * OW, OW, 1, d->H * d->W, d->stride_h * d->W, d->stride_w, 0, (long long)d->N * OH * OW};
+    PwGeom g{d->N, d->K, d->C, pad_to(d->C, 128), OW, OH * OW, OH * OW, OW, 1, d->H * d->W, d->stride_h * d->W, d->stride_w, 0, (long long)d->N * OH * OW};
     if (addend != nullptr && !dense) return fail(CPG_E_UNSUPPORTED, "%s: the fused addend needs a dense (stride 1) layer", what);
     const bool vec = (OH * OW) % 4 == 0 && (((uintptr_t)gy) & 15) == 0;
     if (d->C <= 64) return vec ? launch<PwV64, true>(g, gy, wp, nullptr, gx, stream, what, nullptr, addend) : launch<PwS64, true>(g, gy, wp, nullptr, gx, stream, what, nullptr, addend);

@@ -182,6 +182,8 @@ int cpg_conv2d_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, co
  *       _dgrad_bnbwd call on this thread streams `packed` instead of packing w / pm (which it still takes: a launch of another kernel
  *       family ignores the operand and packs for itself).  One-shot: that call disarms the thread whether it used the operand or
  *       not; a size that does not match what the launch streams is CPG_E_INVALID.  NULL disarms.
+ * cpg_conv2d_pack_bytes, cpg_conv2d_pack and the *_tiles / *_supported queries read no thread state and write none: they answer from the
+ * descriptor and the library options alone, launch nothing (the queries) and leave an armed operand armed.
  * Results are bit-equal to the self-packing calls.  Reference: the `W_eff` the reference materialises in every forward
  * (models/layers.py:99-105) and autograd keeps for the backward. */
 size_t cpg_conv2d_pack_bytes(const cpg_conv_desc *desc, int32_t pass);

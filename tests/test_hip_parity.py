@@ -3373,7 +3373,7 @@ def test_bn_stats_finalize_count_bumps_num_batches_tracked_and_changes_nothing_e
 def test_caller_packed_operands_are_bit_equal_to_self_packing_calls(shape, with_pm):
     """cpg_conv2d_pack (forward + input-gradient operand in ONE launch) + cpg_conv2d_use_packed against the self-packing entry points on
     the same inputs: y, the BatchNorm partial sums, gx and gx + addend BIT-equal; the context is one-shot (the call after an armed call
-    packs for itself again) and a wrong-sized operand is refused."""
+    packs for itself again), a wrong-sized operand is refused, and the size / tile queries leave an armed operand armed."""
     import ctypes
     L = __import__('cpg_amd._lib', fromlist=['x'])
     lib = L.lib()
@@ -3390,6 +3390,7 @@ def test_caller_packed_operands_are_bit_equal_to_self_packing_calls(shape, with_
     assert nb[0] > 0 and nb[1] > 0, nb
     ws, wsb = L.workspace(lib.cpg_conv2d_workspace_bytes(ctypes.byref(d)), DEV)
     tiles = lib.cpg_conv2d_bnstats_tiles(ctypes.byref(d))
+    bnbwd_tiles = lib.cpg_conv2d_dgrad_bnbwd_tiles(ctypes.byref(d))
 
     def run(packed):
         out = {}
@@ -3439,6 +3440,10 @@ def test_caller_packed_operands_are_bit_equal_to_self_packing_calls(shape, with_
     # a wrong-sized operand is refused and leaves the thread disarmed
     junk = torch.zeros(64, device=DEV)
     L.check('use', lib.cpg_conv2d_use_packed(L.dptr(junk), 256))
+    # (the host-only queries answer as before and touch no thread state: the refusal below proves that the operand stayed armed)
+    assert [lib.cpg_conv2d_pack_bytes(ctypes.byref(d), p) for p in (0, 1, 2)] == nb
+    assert lib.cpg_conv2d_bnstats_tiles(ctypes.byref(d)) == tiles
+    assert lib.cpg_conv2d_dgrad_bnbwd_tiles(ctypes.byref(d)) == bnbwd_tiles
     y = torch.empty(N, K, H, W, device=DEV)
     assert lib.cpg_conv2d_fwd(ctypes.byref(d), L.dptr(x), L.dptr(w), L.dptr(pm), 0.005, None, L.dptr(y), L.dptr(ws), wsb, s) < 0
     L.check('fwd', lib.cpg_conv2d_fwd(ctypes.byref(d), L.dptr(x), L.dptr(w), L.dptr(pm), 0.005, None, L.dptr(y), L.dptr(ws), wsb, s))
