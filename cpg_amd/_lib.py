@@ -153,6 +153,11 @@ _SIGNATURES = {
                                            _i64, _vp]),
     'cpg_pair_distance': (_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     'cpg_pair_sweep': (_int, [_vp, _vp, _i64, ctypes.POINTER(_f64), _i32, _i32, _vp, _vp, _vp]),
+    'cpg_loss_heads_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    'cpg_softmax_xent_fwd': (_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    'cpg_softmax_xent_fwd_bwd': (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'cpg_angle_head_fwd': (_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f64] + [_vp] * 7 + [_sz, _vp]),
+    'cpg_angle_head_bwd': (_int, [_vp] * 7 + [_i32, _i32, _i32, _i32, _f32, _f64, _vp, _vp, _vp, _sz, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

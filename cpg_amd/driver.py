@@ -47,7 +47,8 @@ def default_args(**over):
     """The flags the hot path reads (utils/prune.py, utils/manager.py), with experiment1's values."""
     a = dict(mode='finetune', dataset='task1', finetune_again=False, target_sparsity=0.1, initial_sparsity=0.0,
              pruning_frequency=10, pruning_interval=4, weight_decay=4e-5, network_width_multiplier=1.0, cuda=True,
-             log_path=None, progress=False, lr=1e-2, lr_mask=5e-4, checkpoint_format='{save_folder}/checkpoint-{epoch}.pth.tar')
+             log_path=None, progress=False, lr=1e-2, lr_mask=5e-4, checkpoint_format='{save_folder}/checkpoint-{epoch}.pth.tar',
+             fused_loss=False)
     a.update(over)
     return types.SimpleNamespace(**a)
 
@@ -99,7 +100,7 @@ class CPGSession(object):
     """Holds everything the reference passes between processes through checkpoint files."""
 
     def __init__(self, arch='custom_vgg_cifar100', width=None, device='cuda', cfg=VGG16_CFG, data_parallel=True,
-                 fused_optimizers=True, seed=None, freeze_gc=False, width_multiplier=None):
+                 fused_optimizers=True, seed=None, freeze_gc=False, width_multiplier=None, fused_loss=False):
         """width_multiplier: the RAW multiplier of the reference's command line (--network_width_multiplier, before main() takes its
         square root); `width`: the rooted, model-space value the constructors see.  Give one of them (neither: 1.0)."""
         assert width is None or width_multiplier is None, 'give the rooted width OR the raw width_multiplier'
@@ -116,6 +117,9 @@ class CPGSession(object):
         # collector's permanent generation (cpg_amd.utils.settle_host_gc) -- removes the ~80 ms generation-2 pauses from the step loop,
         # but also freezes the embedding application's objects and undoes a freeze it did itself; off unless asked for
         self.freeze_gc = bool(freeze_gc)
+        # OPT-IN: every Manager of this session takes loss, accuracy and the first gradient from the loss-head kernels (args.fused_loss of
+        # utils/manager.py; an `args` that sets the flag itself does the same for its own phases)
+        self.fused_loss = bool(fused_loss)
         self.shared_layer_info = {}
         self.masks = {}
         self.model = None
@@ -280,6 +284,9 @@ class CPGSession(object):
 
     # -- phases ------------------------------------------------------------------------------------------------
     def _manager(self, args, train_loader, val_loader, begin, end):
+        if self.fused_loss:
+            args = copy.copy(args)
+            args.fused_loss = True
         return Manager(args, self.model, self.shared_layer_info, self.masks, train_loader, val_loader, begin, end)
 
     def _validate(self, mgr, epoch):
@@ -386,7 +393,7 @@ class CPGSession(object):
         ckpt.attach_task_layers(model, saved_info, dataset, piggymasks=True)
         masks = {k: v.clone() for k, v in self.masks.items()}
         ckpt.resize_masks(model, masks, 'inference')
-        args = default_args(mode='inference', dataset=dataset, network_width_multiplier=width)
+        args = default_args(mode='inference', dataset=dataset, network_width_multiplier=width, fused_loss=self.fused_loss)
         mgr = Manager(args, model, saved_info, masks, None, val_loader, 0, 0)
         if dataset == 'face_verification':
             acc = self._validate(mgr, 0)

@@ -1,7 +1,8 @@
 """SphereNet-20 + A-Softmax head of CPG on the HIP masked layers (counterpart of models/spherenet.py).
 
 20 x SharableConv2d(3x3, bias=True) with PReLU residual units (four stride-2 stages); the small
-dense/elementwise AngleLinear / AngleLoss ops stay in stock torch.
+dense/elementwise AngleLinear / AngleLoss ops stay in stock torch unless args.fused_loss
+selects their fused restatement (models/losses.py: FusedAngleLoss.head_loss on the same AngleLinear parameter).
 Input is 112x112 (flatten expects 512*m*7*7).
 """
 

@@ -47,6 +47,23 @@ class _NullBar(object):
         pass
 
 
+def make_criterion(args):
+    """The task's loss (utils/manager.py:29-36).  OPT-IN (args.fused_loss; default off): loss, accuracy and the first gradient from the
+    library's loss-head kernels (cpg_amd/models/losses.py) instead of stock torch; same values to rounding, same criterion state."""
+    if getattr(args, 'fused_loss', False):
+        from ..models.losses import FusedAngleLoss as AngleLoss, FusedCrossEntropyLoss as CrossEntropyLoss
+    else:
+        from ..models.spherenet import AngleLoss
+        CrossEntropyLoss = nn.CrossEntropyLoss
+    if args.dataset == 'face_verification':
+        return AngleLoss()
+    if args.dataset == 'emotion':
+        counts = torch.from_numpy(np.array([74874, 134415, 25459, 14090, 6378, 3803, 24882]).astype(np.float32))
+        weights = (torch.sum(counts) - counts) / counts
+        return CrossEntropyLoss(weight=weights.cuda() if getattr(args, 'cuda', True) else weights)
+    return CrossEntropyLoss()
+
+
 class Manager(object):
     """Handles training and pruning (utils/manager.py:16-37)."""
 
@@ -72,18 +89,29 @@ class Manager(object):
         self.last_stats = {}
         self.last_lfw = None
         self.postfix_interval = float(getattr(args, 'postfix_interval', 0.5))
-        if args.dataset == 'face_verification':
-            from ..models.spherenet import AngleLoss
-            self.criterion = AngleLoss()
-        elif args.dataset == 'emotion':
-            counts = torch.from_numpy(np.array([74874, 134415, 25459, 14090, 6378, 3803, 24882]).astype(np.float32))
-            weights = (torch.sum(counts) - counts) / counts
-            self.criterion = nn.CrossEntropyLoss(weight=weights.cuda() if getattr(args, 'cuda', True) else weights)
-        else:
-            self.criterion = nn.CrossEntropyLoss()
+        self.fused_loss = bool(getattr(args, 'fused_loss', False))
+        self.criterion = make_criterion(args)
 
     def _bar(self, total, desc):
         return tqdm(total=total, desc=desc, ascii=True) if self.progress else _NullBar()
+
+    def _loss_and_accuracy(self, data, target, train):
+        """(loss, accuracy of the batch or None), in the reference's order of calls: train computes the accuracy before the loss (and none
+        for the face task), validate the loss before the accuracy.  Fused: the accuracy comes out of the loss kernel, and in train the face
+        task's head takes the embeddings -- the trunk and the 512-wide linear layer in front of AngleLinear are the calls `model(data)` makes."""
+        face = self.args.dataset == 'face_verification'
+        if self.fused_loss and face and train:
+            root = self.model.module if hasattr(self.model, 'module') else self.model
+            return self.criterion.head_loss(root.forward_to_embeddings(data), root.classifier[1], target), None
+        output = self.model(data)
+        if self.fused_loss and not face:
+            loss = self.criterion(output, target)
+            return loss, self.criterion.accuracy
+        if train:
+            accuracy = None if face else classification_accuracy(output, target)
+            return self.criterion(output, target), accuracy
+        loss = self.criterion(output, target)
+        return loss, classification_accuracy(output, target)
 
     def _to_device(self, data, target):
         if getattr(self.args, 'cuda', True):
@@ -101,11 +129,10 @@ class Manager(object):
             for batch_idx, (data, target) in enumerate(self.train_loader):
                 data, target = self._to_device(data, target)
                 optimizers.zero_grad()
-                output = self.model(data)
                 num = data.size(0)
-                if self.args.dataset != 'face_verification':
-                    train_accuracy.update(classification_accuracy(output, target), num)
-                loss = self.criterion(output, target)
+                loss, accuracy = self._loss_and_accuracy(data, target, train=True)
+                if accuracy is not None:
+                    train_accuracy.update(accuracy, num)
                 train_loss.update(loss, num)
                 loss.backward()
                 # Set fixed param grads to 0 (after the data-parallel all-reduce hooks have filled .grad)
@@ -158,10 +185,10 @@ class Manager(object):
             with torch.no_grad():
                 for bi, (data, target) in enumerate(self.val_loader):
                     data, target = self._to_device(data, target)
-                    output = self.model(data)
                     num = data.size(0)
-                    val_loss.update(self.criterion(output, target), num)
-                    val_accuracy.update(classification_accuracy(output, target), num)
+                    loss, accuracy = self._loss_and_accuracy(data, target, train=False)
+                    val_loss.update(loss, num)
+                    val_accuracy.update(accuracy, num)
                     # statistics per validation batch, as the reference (utils/manager.py:126-136); cached histogram
                     stats = {'sparsity': self.pruner.calculate_sparsity(),
                              'task{} ratio'.format(idx): self.pruner.calculate_curr_task_ratio(),

@@ -592,6 +592,52 @@ int cpg_pair_distance(const float *a, int64_t lda, const float *b, int64_t ldb, 
 int cpg_pair_sweep(const float *dist, const uint8_t *issame, int64_t n, const double *thr_host, int32_t n_thr, int32_t nfolds, int64_t *counts,
                    int64_t *best, void *stream);
 
+/* ---- loss heads: from the network's output to the loss, the accuracy and the gradient that starts the backward pass.  Compatible
+ * additions: the ABI version stays 3 (probe with dlsym, as for the rider entries above).  Every reduction has a fixed order (no
+ * floating-point atomics): two calls on the same inputs give the same bytes.  loss and correct are ONE float each in device memory;
+ * nothing is synchronised.  target: int64 [B].
+ *
+ * cpg_loss_heads_workspace_bytes: the workspace of the four calls below for B rows, C classes and D embedding features (D == 0: the
+ * two cross-entropy calls alone).  16-byte aligned.
+ *
+ * cpg_softmax_xent_fwd / _fwd_bwd: nn.CrossEntropyLoss(weight=class_weight) with its mean reduction plus classification_accuracy
+ * (utils/manager.py:29-36,58-62,120-121; utils/__init__.py:46-49) on logits [B][C], any B >= 1 and C >= 1:
+ *   nll_i = logsumexp(z_i) - z_i[t_i] (the row maximum subtracted before the exponentials), W = sum_i class_weight[t_i] (NULL: the
+ *   number of counted rows), loss = sum_i class_weight[t_i] nll_i / W, correct = the number of rows whose FIRST maximum index is t_i.
+ *   _fwd_bwd also writes dlogits[i][j] = g class_weight[t_i] (softmax_ij - [j == t_i]) / W, g = gscale[0] (a DEVICE scalar: the
+ *   upstream gradient of the loss; NULL: 1); there loss and correct may both be NULL (gradient only: the launch that adds the rows'
+ *   results up is skipped -- what a backward pass wants after _fwd gave the two numbers).  Rows of up to 8 192 classes are read from
+ *   memory once (they live in registers); wider rows are streamed two (forward) or three (with the gradient) times.
+ * A row whose target is outside [0, C) -- torch's ignore_index = -100 included -- counts with weight 0, is never correct, gets an
+ * exactly zero gradient row and indexes no memory.  A NaN logit in a counted row gives a NaN loss; no counted row gives 0 / 0.
+ *
+ * cpg_angle_head_fwd / _bwd: AngleLinear followed by AngleLoss (models/spherenet.py:24-61 and :64-98; CPG_face_main.py selects them
+ * for face_verification) for m = 4 and gamma = 0 ONLY -- anything else is refused with CPG_E_INVALID before a pointer is looked at.
+ * x [B][D] embeddings, w [D][C] (AngleLinear's own layout), lamb = max(LambdaMin, LambdaMax / (1 + 0.1 it)) of THIS call (the caller
+ * keeps `it`), s = 1 / (1 + lamb).  With n_j = |w[:, j]|, what = w / n_j, z = x . what, y = t_i, c_i = clamp(z_iy / |x_i|, -1, 1),
+ * k_i = floor(4 acos(c_i) / 3.14159265), phi_i = (-1)^k (8 c^4 - 8 c^2 + 1) - 2 k:
+ *   f = z except f_iy = (1 - s) z_iy + s |x_i| phi_i;  loss, correct = the cross-entropy above on (f, target), no class weights.
+ * That is the reference's result restated: its renorm(2, 1, 1e-5).mul(1e5) cancels against the division by the column norm, and
+ * phi(theta) only ever reaches the loss through the target column.  _fwd writes what [D][C], colnorm [C], f [B][C] and
+ * saved [B][4] = {|x_i|, c_i, phi_i, phi'_i}, which the caller keeps for _bwd:
+ *   phi'_i = (-1)^k (32 c^3 - 16 c) (0 where the clamp bit), dz = df except dz_iy = df_iy ((1 - s) + s phi'_i),
+ *   gx_i = dz_i . what^T + df_iy s (phi_i - c_i phi'_i) x_i / |x_i|,  G = x^T . dz,  gw_j = (G_j - what_j (what_j . G_j)) / n_j
+ * (the gradient through the renorm included), df being _fwd_bwd's dlogits on f with the same gscale.  The three products run on the
+ * fp32-MFMA kernels of the linear layers.  Preconditions, as in the reference, which divides by both: no zero column in w, no zero row
+ * in x.  A row whose target is outside [0, C) takes no margin and no part in the loss. */
+size_t cpg_loss_heads_workspace_bytes(int32_t B, int32_t D, int32_t C);
+int cpg_softmax_xent_fwd(const float *logits, const int64_t *target, const float *class_weight, int32_t B, int32_t C, float *loss,
+                         float *correct, void *workspace, size_t workspace_bytes, void *stream);
+int cpg_softmax_xent_fwd_bwd(const float *logits, const int64_t *target, const float *class_weight, const float *gscale, int32_t B,
+                             int32_t C, float *loss, float *correct, float *dlogits, void *workspace, size_t workspace_bytes,
+                             void *stream);
+int cpg_angle_head_fwd(const float *x, const float *w, const int64_t *target, int32_t B, int32_t D, int32_t C, int32_t m, float gamma,
+                       double lamb, float *what, float *colnorm, float *f, float *saved, float *loss, float *correct, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int cpg_angle_head_bwd(const float *x, const float *what, const float *colnorm, const float *f, const float *saved,
+                       const int64_t *target, const float *gscale, int32_t B, int32_t D, int32_t C, int32_t m, float gamma, double lamb,
+                       float *gx, float *gw, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
