@@ -89,6 +89,7 @@ _SIGNATURES = {
     'cpg_route_grads': (_int, [_vp, _vp, _vp, _i32, _f32, _vp, _i32, _i64, _vp]),
     'cpg_rank_prune_workspace_bytes': (_sz, []),
     'cpg_rank_prune': (_int, [_vp, _vp, _i32, _f64, _i64, _vp, _vp, _sz, _vp]),
+    'cpg_rank_prune_zero': (_int, [_vp, _vp, _i32, _f64, _i64, _vp, _vp, _sz, _vp]),
     'cpg_mask_hist': (_int, [_vp, _vp, _i32, _i64, _vp, _vp]),
     'cpg_apply_mask': (_int, [_vp, _vp, _i32, _i64, _vp]),
     'cpg_zero_pruned': (_int, [_vp, _vp, _i64, _vp]),
@@ -101,6 +102,8 @@ _SIGNATURES = {
     'cpg_multi_tensor_max': (_i32, []),
     'cpg_sgd_route_step_multi': (_int, [ctypes.POINTER(SgdItem), _i32, _i32, _f32, _f32, _f32, _i32, _i32, _vp]),
     'cpg_adam_route_step_multi': (_int, [ctypes.POINTER(AdamItem), _i32, _i32, _i32, _f64, _f64, _f64, _f64, _i32, _vp]),
+    'cpg_sgd_route_zero_step': (_int, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _i32, _i32, _i64, _vp]),
+    'cpg_sgd_route_zero_step_multi': (_int, [ctypes.POINTER(SgdItem), _i32, _i32, _f32, _f32, _f32, _i32, _i32, _vp]),
     'cpg_adam_route_step': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _f64, _f64, _i32, _i64, _vp]),
     'cpg_bn_workspace_bytes': (_sz, [_i32, _i32, _i32]),
     'cpg_bn_relu_fwd_train': (_int, [_vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),

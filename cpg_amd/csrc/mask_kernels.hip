@@ -226,7 +226,11 @@ __global__ __launch_bounds__(kThreads) void k_claim_free(uint8_t *__restrict__ o
 //   buf = first ? g : momentum * buf + g            (two roundings, as torch's _foreach_mul_ / _foreach_add_)
 //   d   = nesterov ? g + momentum * buf : buf
 //   w  -= lr * d
-// 17 B read + 12 B written per element instead of the 13 + 36 B of the routing pass plus torch's three foreach passes.
+// 13 B read + 12 B written per element instead of the 13 + 36 B of the routing pass plus torch's three foreach passes.
+// ZERO (the PackNet step, utils/packnet_prune.py:146-171 + utils/packnet_manager.py:69): the weight of a slot nobody owns is pinned to
+// +0.0f in the same store (make_pruned_zero after every step); its gradient and momentum are written as above -- the reference's
+// momentum keeps decaying on pruned slots.
+template <bool ZERO>
 __global__ __launch_bounds__(kThreads) void k_sgd_route(float *__restrict__ w, float *__restrict__ gw, float *__restrict__ buf,
                                                         const uint8_t *__restrict__ owner, int cur, float wd, float lr,
                                                         float momentum, int nesterov, int first, int64_t n, int vec_ok) {
@@ -236,7 +240,7 @@ __global__ __launch_bounds__(kThreads) void k_sgd_route(float *__restrict__ w, f
         const float g = (o == cur) ? fmaf(wd, wv, gv) : 0.0f;
         const float b = first ? g : __fadd_rn(__fmul_rn(momentum, bv), g);
         const float d = nesterov ? fmaf(momentum, b, g) : b;
-        wv = fmaf(-lr, d, wv);
+        wv = (ZERO && o == 0) ? 0.0f : fmaf(-lr, d, wv);
         gv = g;
         bv = b;
     };
@@ -342,6 +346,7 @@ __device__ __forceinline__ int find_item(const Items &it, int block) {
     return i;
 }
 
+template <bool ZERO>
 __global__ __launch_bounds__(kThreads) void k_sgd_route_multi(const SgdItems it, int cur, float wd, float lr, float momentum, int nesterov,
                                                               int first) {
     const int item = find_item(it, (int)blockIdx.x);
@@ -354,7 +359,7 @@ __global__ __launch_bounds__(kThreads) void k_sgd_route_multi(const SgdItems it,
         const float g = (o == cur) ? fmaf(wd, wv, gv) : 0.0f;
         const float b = first ? g : __fadd_rn(__fmul_rn(momentum, bv), g);
         const float d = nesterov ? fmaf(momentum, b, g) : b;
-        wv = fmaf(-lr, d, wv);
+        wv = (ZERO && o == 0) ? 0.0f : fmaf(-lr, d, wv);
         gv = g;
         bv = b;
     };
@@ -428,20 +433,30 @@ __global__ __launch_bounds__(kThreads) void k_adam_route_multi(const AdamItems i
 
 extern "C" int32_t cpg_multi_tensor_max(void) { return kMultiMax; }
 
-extern "C" int cpg_sgd_route_step_multi(const cpg_sgd_item *items_host, int32_t n_items, int32_t cur, float wd, float lr, float momentum,
+template <bool ZERO>
+static int sgd_route_multi(const char *fn, const cpg_sgd_item *items_host, int32_t n_items, int32_t cur, float wd, float lr, float momentum,
                                         int32_t nesterov, int32_t first_step, void *stream) {
-    CPG_REQUIRE(n_items >= 0 && (n_items == 0 || items_host), "cpg_sgd_route_step_multi: null item table or negative count");
-    CPG_REQUIRE(cur >= 0 && cur <= 255, "cpg_sgd_route_step_multi: owner id %d out of uint8 range", cur);
+    CPG_REQUIRE(n_items >= 0 && (n_items == 0 || items_host), "%s: null item table or negative count", fn);
+    CPG_REQUIRE(cur >= 0 && cur <= 255, "%s: owner id %d out of uint8 range", fn, cur);
+    // every row is checked before the first launch (pointers, sizes, and the grid of the launch it will fall into, cut as below):
+    // a bad table changes nothing
+    for (int32_t at = 0, count = 0, blocks = 0; at < n_items; ++at) {
+        const cpg_sgd_item &s = items_host[at];
+        CPG_REQUIRE(s.n >= 0 && (s.n == 0 || (s.w && s.gw && s.momentum_buf && s.owner)), "%s: item %d: null pointer or negative n", fn, at);
+        if (s.n == 0) continue;
+        if (count == kMultiMax) count = 0, blocks = 0;
+        const int64_t pieces = (s.n + kChunk - 1) / kChunk;
+        CPG_REQUIRE(blocks + pieces < (1ll << 30), "%s: item %d is too large for one launch", fn, at);
+        blocks += (int)pieces, ++count;
+    }
     for (int32_t at = 0; at < n_items;) {
         SgdItems it;
         int blocks = 0;
         it.count = 0;
         for (; at < n_items && it.count < kMultiMax; ++at) {
             const cpg_sgd_item &s = items_host[at];
-            CPG_REQUIRE(s.n >= 0 && (s.n == 0 || (s.w && s.gw && s.momentum_buf && s.owner)), "cpg_sgd_route_step_multi: item %d: null pointer or negative n", at);
             if (s.n == 0) continue;
             const int64_t pieces = (s.n + kChunk - 1) / kChunk;
-            CPG_REQUIRE(blocks + pieces < (1ll << 30), "cpg_sgd_route_step_multi: item %d is too large for one launch", at);
             const int i = it.count++;
             it.w[i] = s.w, it.gw[i] = s.gw, it.buf[i] = s.momentum_buf, it.owner[i] = s.owner, it.n[i] = s.n;
             it.vec[i] = is16(s.w) && is16(s.gw) && is16(s.momentum_buf) && (((uintptr_t)s.owner) & 3) == 0;
@@ -450,10 +465,20 @@ extern "C" int cpg_sgd_route_step_multi(const cpg_sgd_item *items_host, int32_t 
         }
         if (it.count == 0) continue;
         it.first_block[it.count] = blocks;
-        hipLaunchKernelGGL(k_sgd_route_multi, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, it, cur, wd, lr, momentum, nesterov, first_step);
-        CPG_CHECK_LAUNCH("cpg_sgd_route_step_multi");
+        hipLaunchKernelGGL(k_sgd_route_multi<ZERO>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, it, cur, wd, lr, momentum, nesterov, first_step);
+        CPG_CHECK_LAUNCH(fn);
     }
     return CPG_OK;
+}
+
+extern "C" int cpg_sgd_route_step_multi(const cpg_sgd_item *items_host, int32_t n_items, int32_t cur, float wd, float lr, float momentum,
+                                        int32_t nesterov, int32_t first_step, void *stream) {
+    return sgd_route_multi<false>("cpg_sgd_route_step_multi", items_host, n_items, cur, wd, lr, momentum, nesterov, first_step, stream);
+}
+
+extern "C" int cpg_sgd_route_zero_step_multi(const cpg_sgd_item *items_host, int32_t n_items, int32_t cur, float wd, float lr, float momentum,
+                                             int32_t nesterov, int32_t first_step, void *stream) {
+    return sgd_route_multi<true>("cpg_sgd_route_zero_step_multi", items_host, n_items, cur, wd, lr, momentum, nesterov, first_step, stream);
 }
 
 extern "C" int cpg_adam_route_step_multi(const cpg_adam_item *items_host, int32_t n_items, int32_t cur, int32_t mode, double lr, double beta1,
@@ -510,9 +535,21 @@ extern "C" int cpg_sgd_route_step(float *w, float *gw, float *momentum_buf, cons
     CPG_REQUIRE(cur >= 0 && cur <= 255, "cpg_sgd_route_step: owner id %d out of uint8 range", cur);
     if (n == 0) return CPG_OK;
     const int vec = is16(w) && is16(gw) && is16(momentum_buf) && (((uintptr_t)owner) & 3) == 0;
-    hipLaunchKernelGGL(k_sgd_route, dim3(stream_grid(n, kThreads * 4)), dim3(kThreads), 0, (hipStream_t)stream, w, gw, momentum_buf,
+    hipLaunchKernelGGL(k_sgd_route<false>, dim3(stream_grid(n, kThreads * 4)), dim3(kThreads), 0, (hipStream_t)stream, w, gw, momentum_buf,
                        owner, cur, wd, lr, momentum, nesterov, first_step, n, vec);
     CPG_CHECK_LAUNCH("cpg_sgd_route_step");
+    return CPG_OK;
+}
+
+extern "C" int cpg_sgd_route_zero_step(float *w, float *gw, float *momentum_buf, const uint8_t *owner, int32_t cur, float wd, float lr,
+                                       float momentum, int32_t nesterov, int32_t first_step, int64_t n, void *stream) {
+    CPG_REQUIRE(n >= 0 && (n == 0 || (w && gw && momentum_buf && owner)), "cpg_sgd_route_zero_step: null pointer or negative n");
+    CPG_REQUIRE(cur >= 0 && cur <= 255, "cpg_sgd_route_zero_step: owner id %d out of uint8 range", cur);
+    if (n == 0) return CPG_OK;
+    const int vec = is16(w) && is16(gw) && is16(momentum_buf) && (((uintptr_t)owner) & 3) == 0;
+    hipLaunchKernelGGL(k_sgd_route<true>, dim3(stream_grid(n, kThreads * 4)), dim3(kThreads), 0, (hipStream_t)stream, w, gw, momentum_buf,
+                       owner, cur, wd, lr, momentum, nesterov, first_step, n, vec);
+    CPG_CHECK_LAUNCH("cpg_sgd_route_zero_step");
     return CPG_OK;
 }
 

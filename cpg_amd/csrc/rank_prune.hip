@@ -9,6 +9,7 @@
 // k = round-half-even(ratio * n_cand) is formed on device in fp64 exactly as python's round().
 //
 // HBM traffic per element: 3 x (4 B w + 1 B owner) + final (4 + 1 r, 1 w) = 21 B.
+#include <type_traits>
 #include "cpg_common.h"
 
 using namespace cpg;
@@ -165,35 +166,59 @@ __global__ __launch_bounds__(kThreads) void k_rp_scan(RpWs *__restrict__ ws, dou
     for (int j = 0; j < PER; ++j) ws->hist[t * PER + j] = 0;
 }
 
-// final pass: owner[(|w| <= cutoff) & (owner == cur)] = 0, in the integer domain (NaN never <=)
-__global__ __launch_bounds__(kThreads) void k_rp_apply(const float *__restrict__ w, uint8_t *__restrict__ owner, int cur,
-                                                       int64_t n, RpWs *__restrict__ ws, int vec_ok) {
+// final pass: owner[(|w| <= cutoff) & (owner == cur)] = 0, in the integer domain (NaN never <=).
+// ZERO (cpg_rank_prune_zero; utils/packnet_prune.py:77,98 `weight[mask.eq(0)] = 0.0`): additionally w = +0.0f at every slot whose owner
+// is 0 after the update, newly released or not, in the same pass.
+template <bool ZERO>
+__global__ __launch_bounds__(kThreads) void k_rp_apply(typename std::conditional<ZERO, float, const float>::type *__restrict__ w,
+                                                       uint8_t *__restrict__ owner, int cur, int64_t n, RpWs *__restrict__ ws, int vec_ok) {
     if (ws->st.status != CPG_OK) return;
     const unsigned cut = ws->st.prefix;          // full 31-bit key of the k-th smallest |w|
-    if (cut > 0x7F800000u) return;               // cutoff is NaN: `abs(w) <= nan` is false everywhere
+    const bool nan_cut = cut > 0x7F800000u;      // cutoff is NaN: `abs(w) <= nan` is false everywhere
+    if (!ZERO && nan_cut) return;
     const int64_t tid = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     const int64_t nthreads = (int64_t)gridDim.x * kThreads;
     unsigned cnt = 0;
+    auto one = [&](int64_t i) {
+        int o = owner[i];
+        if (o == cur && !nan_cut && key_of(w[i]) <= cut) { owner[i] = 0; o = 0; cnt++; }
+        if constexpr (ZERO) {
+            if (o == 0) w[i] = 0.0f;
+        }
+    };
     if (vec_ok) {
         const int64_t n4 = n >> 2;
         for (int64_t i = tid; i < n4; i += nthreads) {
             uint32_t o4 = reinterpret_cast<const uint32_t *>(owner)[i];
             const int o0 = o4 & 255, o1 = (o4 >> 8) & 255, o2 = (o4 >> 16) & 255, o3 = o4 >> 24;
-            if (o0 == cur || o1 == cur || o2 == cur || o3 == cur) {
-                const float4 v = reinterpret_cast<const float4 *>(w)[i];
+            const bool any_cur = !nan_cut && (o0 == cur || o1 == cur || o2 == cur || o3 == cur);
+            const bool any_free = ZERO && (o0 == 0 || o1 == 0 || o2 == 0 || o3 == 0);
+            if (any_cur || any_free) {
+                float4 v = reinterpret_cast<const float4 *>(w)[i];
                 uint32_t keep = 0xFFFFFFFFu;
-                if (o0 == cur && key_of(v.x) <= cut) { keep &= 0xFFFFFF00u; cnt++; }
-                if (o1 == cur && key_of(v.y) <= cut) { keep &= 0xFFFF00FFu; cnt++; }
-                if (o2 == cur && key_of(v.z) <= cut) { keep &= 0xFF00FFFFu; cnt++; }
-                if (o3 == cur && key_of(v.w) <= cut) { keep &= 0x00FFFFFFu; cnt++; }
-                if (keep != 0xFFFFFFFFu) reinterpret_cast<uint32_t *>(owner)[i] = o4 & keep;
+                if (any_cur) {
+                    if (o0 == cur && key_of(v.x) <= cut) { keep &= 0xFFFFFF00u; cnt++; }
+                    if (o1 == cur && key_of(v.y) <= cut) { keep &= 0xFFFF00FFu; cnt++; }
+                    if (o2 == cur && key_of(v.z) <= cut) { keep &= 0xFF00FFFFu; cnt++; }
+                    if (o3 == cur && key_of(v.w) <= cut) { keep &= 0x00FFFFFFu; cnt++; }
+                    if (keep != 0xFFFFFFFFu) reinterpret_cast<uint32_t *>(owner)[i] = o4 & keep;
+                }
+                if constexpr (ZERO) {
+                    const uint32_t r4 = o4 & keep;
+                    const bool z0 = (r4 & 255) == 0, z1 = ((r4 >> 8) & 255) == 0, z2 = ((r4 >> 16) & 255) == 0, z3 = (r4 >> 24) == 0;
+                    if (z0 || z1 || z2 || z3) {
+                        if (z0) v.x = 0.f;
+                        if (z1) v.y = 0.f;
+                        if (z2) v.z = 0.f;
+                        if (z3) v.w = 0.f;
+                        reinterpret_cast<float4 *>(w)[i] = v;
+                    }
+                }
             }
         }
-        for (int64_t i = (n4 << 2) + tid; i < n; i += nthreads)
-            if (owner[i] == cur && key_of(w[i]) <= cut) { owner[i] = 0; cnt++; }
+        for (int64_t i = (n4 << 2) + tid; i < n; i += nthreads) one(i);
     } else {
-        for (int64_t i = tid; i < n; i += nthreads)
-            if (owner[i] == cur && key_of(w[i]) <= cut) { owner[i] = 0; cnt++; }
+        for (int64_t i = tid; i < n; i += nthreads) one(i);
     }
     // wave reduce, one atomic per wave
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
@@ -225,13 +250,14 @@ __global__ void k_rp_finish(const RpWs *ws, cpg_prune_result *res) {
 
 extern "C" size_t cpg_rank_prune_workspace_bytes(void) { return sizeof(RpWs); }
 
-extern "C" int cpg_rank_prune(const float *w, uint8_t *owner, int32_t cur, double ratio, int64_t n,
-                              cpg_prune_result *result, void *ws_v, size_t ws_bytes, void *stream_v) {
-    CPG_REQUIRE(w && owner && result && ws_v, "cpg_rank_prune: null pointer");
-    CPG_REQUIRE(n >= 0 && n < (int64_t)0xFFFFFFFFll, "cpg_rank_prune: n=%lld outside [0, 2^32)", (long long)n);
-    CPG_REQUIRE(cur >= 0 && cur <= 255, "cpg_rank_prune: owner id %d out of uint8 range", cur);
-    if (ws_bytes < sizeof(RpWs)) return fail(CPG_E_WORKSPACE, "cpg_rank_prune: workspace %zu < %zu", ws_bytes, sizeof(RpWs));
-    CPG_REQUIRE((((uintptr_t)ws_v) & 7) == 0, "cpg_rank_prune: workspace must be 8-byte aligned");
+template <bool ZERO>
+static int rank_prune(const char *fn, typename std::conditional<ZERO, float, const float>::type *w, uint8_t *owner, int32_t cur, double ratio,
+                      int64_t n, cpg_prune_result *result, void *ws_v, size_t ws_bytes, void *stream_v) {
+    CPG_REQUIRE(w && owner && result && ws_v, "%s: null pointer", fn);
+    CPG_REQUIRE(n >= 0 && n < (int64_t)0xFFFFFFFFll, "%s: n=%lld outside [0, 2^32)", fn, (long long)n);
+    CPG_REQUIRE(cur >= 0 && cur <= 255, "%s: owner id %d out of uint8 range", fn, cur);
+    if (ws_bytes < sizeof(RpWs)) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu", fn, ws_bytes, sizeof(RpWs));
+    CPG_REQUIRE((((uintptr_t)ws_v) & 7) == 0, "%s: workspace must be 8-byte aligned", fn);
     hipStream_t stream = (hipStream_t)stream_v;
     RpWs *ws = (RpWs *)ws_v;
     const int vec = (((uintptr_t)w) & 15) == 0 && (((uintptr_t)owner) & 3) == 0;
@@ -244,8 +270,18 @@ extern "C" int cpg_rank_prune(const float *w, uint8_t *owner, int32_t cur, doubl
     hipLaunchKernelGGL(k_rp_scan<1>, dim3(1), block, 0, stream, ws, ratio);
     hipLaunchKernelGGL(k_rp_hist<2>, grid, block, 0, stream, w, owner, cur, n, ws, vec);
     hipLaunchKernelGGL(k_rp_scan<2>, dim3(1), block, 0, stream, ws, ratio);
-    hipLaunchKernelGGL(k_rp_apply, grid, block, 0, stream, w, owner, cur, n, ws, vec);
+    hipLaunchKernelGGL(k_rp_apply<ZERO>, grid, block, 0, stream, w, owner, cur, n, ws, vec);
     hipLaunchKernelGGL(k_rp_finish, dim3(1), dim3(1), 0, stream, ws, result);
-    CPG_CHECK_LAUNCH("cpg_rank_prune");
+    CPG_CHECK_LAUNCH(fn);
     return CPG_OK;
+}
+
+extern "C" int cpg_rank_prune(const float *w, uint8_t *owner, int32_t cur, double ratio, int64_t n,
+                              cpg_prune_result *result, void *ws_v, size_t ws_bytes, void *stream_v) {
+    return rank_prune<false>("cpg_rank_prune", w, owner, cur, ratio, n, result, ws_v, ws_bytes, stream_v);
+}
+
+extern "C" int cpg_rank_prune_zero(float *w, uint8_t *owner, int32_t cur, double ratio, int64_t n,
+                                   cpg_prune_result *result, void *ws_v, size_t ws_bytes, void *stream_v) {
+    return rank_prune<true>("cpg_rank_prune_zero", w, owner, cur, ratio, n, result, ws_v, ws_bytes, stream_v);
 }

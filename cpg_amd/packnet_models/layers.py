@@ -1,0 +1,42 @@
+"""Plain (unmasked) operators of the PackNet baseline stack on the C-ABI kernels.
+
+The reference's packnet_models build their trunks from stock nn.Conv2d / nn.Linear and tell prunable layers apart with
+`isinstance(module, nn.Conv2d) or isinstance(module, nn.Linear)` (utils/packnet_prune.py:72,90,...).  These classes ARE nn.Conv2d /
+nn.Linear -- constructor, parameters, state_dict keys and seeded initialisation are torch's -- and only their forward / backward run the
+library's convolution and GEMM kernels, with no piggymask (the kernels' `pm == NULL` form, as models.layers.HeadLinear for one layer).
+They offer the hooks FusedSequential looks for (`forward_with_bn_stats`, `forward_bn_eval`), so the baselines get the fused BatchNorm,
+stem and inference paths of the CPG models.  fp32, HIP tensors only: no CPU fallback.
+"""
+import types
+
+import torch.nn as nn
+
+from ..models import layers as nl
+
+
+class PlainConv2d(nn.Conv2d):
+    # what SharableConv2d's two methods below and fused_bn read besides nn.Conv2d's own attributes: no mask, threshold unused (read-only)
+    piggymask = None
+    info = types.MappingProxyType({'threshold': 0.0})
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if self.padding_mode != 'zeros' or isinstance(self.padding, str):
+            raise NotImplementedError('PlainConv2d: only zero padding given as numbers')
+
+    def _math(self):
+        return 'fp32'
+
+    def forward(self, input, bn_hint=None, bias_sink=None):
+        if self.groups != 1:             # all groups in one launch per pass (no statistics epilogue, hint or sink on that route)
+            bn_hint = bias_sink = None
+        return nl._MaskedConv2dFn.apply(input, self.weight, None, self.bias, 0.0, self.stride, self.padding, self.dilation, self.groups,
+                                        False, 'fp32', bn_hint, bias_sink)
+
+    forward_with_bn_stats = nl.SharableConv2d.forward_with_bn_stats
+    forward_bn_eval = nl.SharableConv2d.forward_bn_eval
+
+
+class PlainLinear(nn.Linear):
+    def forward(self, input):
+        return nl._MaskedLinearFn.apply(input, self.weight, None, self.bias, 0.0)

@@ -162,3 +162,78 @@ class MaskedAdam(torch.optim.Adam):
         for p, g in held:
             p.grad = g
         return loss
+
+
+class PackNetSGD(torch.optim.SGD):
+    """MaskedSGD's counterpart for the PackNet baseline stack (packnet_cifar100_main_normal.py:229-230 + utils/packnet_manager.py:63-69):
+    a torch.optim.SGD whose step() sends every weight the PackNet pruner covers (utils.packnet_prune.SparsePruner: each nn.Conv2d /
+    nn.Linear outside `classifiers`) through ONE multi-tensor pass that adds the weight decay, routes the gradient, takes the
+    momentum step and pins the weights nobody owns to zero -- cpg_sgd_route_zero_step_multi.  BatchNorm, biases and the active head take
+    torch's own SGD path.  `.grad` is left routed as the reference leaves it.
+
+    mode:
+        'fused'      (default) the pass above; the pruner's do_weight_decay_and_make_grads_zero() and make_pruned_zero() skip the
+                     covered weights while this optimizer is attached.  The default by measurement: profiles/packnet.md.
+        'step+zero'  cpg_sgd_route_step_multi, then one cpg_zero_pruned per layer: the best composition of the entry points that
+                     existed before the fused pass (bit-equal results, one more pass and one launch per layer).
+        'unfused'    the reference's op sequence on the library's kernels: the pruner routes (cpg_route_grads), torch's SGD steps, the
+                     pruner zeroes (cpg_zero_pruned); this class then is a plain torch.optim.SGD.  Equal to 'fused' to the rounding of
+                     the fused multiply-adds (tests/test_packnet_gpu.py).
+    """
+    MODES = ('fused', 'step+zero', 'unfused')
+
+    def __init__(self, params, pruner, lr, momentum=0.9, nesterov=True, mode='fused', **kw):
+        if kw.get('weight_decay', 0.0) != 0.0 or kw.get('dampening', 0.0) != 0.0:
+            raise ValueError('PackNetSGD mirrors the reference optimizer: weight_decay = dampening = 0 '
+                             '(the decay is applied with the gradient routing)')
+        if mode not in self.MODES:
+            raise ValueError('PackNetSGD mode must be one of %s, got %r' % (', '.join(self.MODES), mode))
+        super().__init__(params, lr=lr, momentum=momentum, nesterov=nesterov, weight_decay=0.0, dampening=0.0)
+        self.pruner, self.mode = pruner, mode
+        pruner.fused_weight_step = mode != 'unfused'
+        self._masked = {}                        # id(param) -> mask name
+
+    def detach(self):
+        """Hand decay, routing and zeroing back to the pruner's own methods (another optimizer takes over)."""
+        self.pruner.fused_weight_step = False
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if self.mode == 'unfused':
+            return super().step(closure)
+        pr = self.pruner
+        if not self._masked:
+            self._masked = {id(module.weight): name for name, module in pr._layers()}
+        s = _lib.stream_ptr()
+        entry = 'cpg_sgd_route_zero_step_multi' if self.mode == 'fused' else 'cpg_sgd_route_step_multi'
+        held, zero_after = [], []
+        for group in self.param_groups:
+            batches = {True: [], False: []}      # rows that share first_step go into one launch, as in MaskedSGD
+            for p in group['params']:
+                name = self._masked.get(id(p))
+                if name is None or p.grad is None:
+                    continue
+                state = self.state[p]
+                first = state.get('momentum_buffer') is None
+                if first:
+                    state['momentum_buffer'] = torch.empty_like(p, memory_format=torch.contiguous_format)
+                owner = pr._owner(name, p.data)
+                batches[first].append((_lib.dptr(p.data, name='weight').value, _lib.dptr(p.grad, name='weight.grad').value,
+                                       _lib.dptr(state['momentum_buffer'], name='momentum').value,
+                                       _lib.dptr(owner, torch.uint8, 'mask').value, p.numel()))
+                held.append((p, p.grad))
+                p.grad = None                    # hide from torch's SGD for the rest of this step
+            for first, rows in batches.items():
+                if not rows:
+                    continue
+                items = (_lib.SgdItem * len(rows))(*rows)
+                _lib.call(entry, items, len(rows), int(pr.current_dataset_idx), float(pr.args.weight_decay), float(group['lr']),
+                          float(group['momentum']), int(bool(group['nesterov'])), int(first), s)
+                if self.mode == 'step+zero':
+                    zero_after += rows
+        for w_, _, _, o_, n_ in zero_after:
+            _lib.call('cpg_zero_pruned', w_, o_, n_, s)
+        loss = super().step(closure)
+        for p, g in held:
+            p.grad = g
+        return loss

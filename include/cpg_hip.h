@@ -243,6 +243,13 @@ int cpg_route_grads(float *gw, const float *w, const uint8_t *owner, int32_t cur
 size_t cpg_rank_prune_workspace_bytes(void);
 int cpg_rank_prune(const float *w, uint8_t *owner, int32_t cur, double ratio, int64_t n,
                    cpg_prune_result *result, void *ws, size_t ws_bytes, void *stream);
+/* The PackNet prunes (utils/packnet_prune.py:64-99, one_shot_prune / gradually_prune): cpg_rank_prune's three select passes unchanged, and a
+ * final pass that releases owners AND writes +0.0f to w at every slot whose owner is 0 after the update, newly released or not
+ * (`module.weight.data[mask.eq(0)] = 0.0`, :77 and :98) -- bit-equal to cpg_rank_prune followed by cpg_zero_pruned, without the second
+ * pass over w.  Same result record, same workspace query.  On CPG_E_KRANGE neither owner nor w is touched.  Callers probe for the symbol
+ * (CPG_ABI_VERSION stays 3). */
+int cpg_rank_prune_zero(float *w, uint8_t *owner, int32_t cur, double ratio, int64_t n,
+                        cpg_prune_result *result, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- K7: utils/prune.py:111-193 (the four mask statistics), one layer ----
  * hist[0..255] += #(owner == id); hist[256] += #(0 < owner < inference_idx && pm > 0.005f)
@@ -314,6 +321,18 @@ int cpg_sgd_route_step_multi(const cpg_sgd_item *items_host, int32_t n_items, in
                              int32_t nesterov, int32_t first_step, void *stream);
 int cpg_adam_route_step_multi(const cpg_adam_item *items_host, int32_t n_items, int32_t cur, int32_t mode, double lr, double beta1,
                               double beta2, double eps, int32_t step, void *stream);
+
+/* The PackNet step in one pass: do_weight_decay_and_make_grads_zero (utils/packnet_prune.py:146-159), optim.SGD(momentum, nesterov)
+ * (packnet_cifar100_main_normal.py:229-230) and make_pruned_zero (utils/packnet_prune.py:161-171, called after every step at
+ * utils/packnet_manager.py:69).  g, buf and the step direction d are cpg_sgd_route_step's; w = (owner == 0) ? +0.0f : w - lr * d.  The routed
+ * gradient and the momentum buffer are written as by cpg_sgd_route_step: the reference's momentum keeps decaying on pruned slots and
+ * only the weight is pinned to zero.  Bit-equal to cpg_sgd_route_step followed by cpg_zero_pruned at the traffic of the former (w is
+ * written anyway).  The multi form takes cpg_sgd_route_step_multi's item rows and follows its conventions.  Callers probe
+ * for the symbols (CPG_ABI_VERSION stays 3). */
+int cpg_sgd_route_zero_step(float *w, float *gw, float *momentum_buf, const uint8_t *owner, int32_t cur, float wd,
+                            float lr, float momentum, int32_t nesterov, int32_t first_step, int64_t n, void *stream);
+int cpg_sgd_route_zero_step_multi(const cpg_sgd_item *items_host, int32_t n_items, int32_t cur, float wd, float lr, float momentum,
+                                  int32_t nesterov, int32_t first_step, void *stream);
 
 /* ---- nn.BatchNorm2d -> nn.ReLU(inplace) after each masked conv ----
  * (models/vgg.py:137-141: `layers += [conv2d, nn.BatchNorm2d(c), nn.ReLU(inplace=True)]`).
