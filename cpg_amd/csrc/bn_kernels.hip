@@ -36,7 +36,7 @@ __device__ __forceinline__ double block_sum(double v, double *red) {
 }
 
 // Visit item j < P of every image plane n in [n0, n1): f(n, j), with flush() at least every 64 visits of a thread (the
-// callers keep fp32 running sums and fold them into fp64 there).  No per-element division: large planes are walked
+// backward reductions keep fp32 running sums and fold them into fp64 there; k_bn_stats sums in fp64 and passes a no-op).  No per-element division: large planes are walked
 // image by image (4 independent visits per loop trip, so 4 loads are in flight per thread -- the one-visit-per-trip
 // version with a 64-bit (i / P, i % P) per element ran k_bn_stats at 4.9 TB/s and k_bnp_bwd_reduce at 3.3 TB/s);
 // small planes are walked flattened.
@@ -81,23 +81,24 @@ __global__ __launch_bounds__(kThreads) void k_bn_stats(const float *__restrict__
     __shared__ double red[4];
     const int c = blockIdx.x, s = blockIdx.y;
     const int n0 = s * d.imgs_per_slice, n1 = min(d.N, n0 + d.imgs_per_slice);
+    // Both sums in fp64 from the first term on: var = E[x^2] - mean^2 loses (mean / std)^2 of whatever precision the sums have.  With
+    // fp32 products and fp32 running sums folded into fp64 every <= 256 terms invstd was off by 1.4e-3 at |mean| / std = 800
+    // (tests/test_autograd_contract_gpu.py); a dozen fp64 operations per 16 bytes stay far below the memory time.
     double ds = 0.0, dss = 0.0;
-    float fs = 0.f, fss = 0.f;
     const bool vec = (d.HW & 3) == 0 && (((uintptr_t)x) & 15) == 0;
-    auto flush = [&]() {          // bounds the fp32 partials to <= 256 terms
-        ds += (double)fs; dss += (double)fss; fs = 0.f; fss = 0.f;
-    };
+    auto flush = []() {};
     if (vec)
         walk_planes(d.HW >> 2, n0, n1, [&](int n, int j) {
             const float4 v = *reinterpret_cast<const float4 *>(x + ((int64_t)n * d.C + c) * d.HW + 4 * j);
-            fs += (v.x + v.y) + (v.z + v.w);
-            fss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+            const double a = v.x, b = v.y, e = v.z, f = v.w;
+            ds += (a + b) + (e + f);
+            dss += (a * a + b * b) + (e * e + f * f);
         }, flush);
     else
         walk_planes(d.HW, n0, n1, [&](int n, int j) {
-            const float v = x[((int64_t)n * d.C + c) * d.HW + j];
-            fs += v;
-            fss += v * v;
+            const double v = x[((int64_t)n * d.C + c) * d.HW + j];
+            ds += v;
+            dss += v * v;
         }, flush);
     const double ts = block_sum(ds, red);
     const double tss = block_sum(dss, red);

@@ -513,9 +513,9 @@ def conv_bn_act_skip(conv, bn, act, x):
     if (ENABLED and FUSE_SKIP_ADD and hasattr(conv, 'forward_with_skip') and x.is_cuda and torch.is_grad_enabled() and x.requires_grad
             and conv._math() == 'fp32' and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.in_channels % 16 == 0
             and conv.out_channels % 16 == 0):
-        y, stats, skip = conv.forward_with_skip(x)
-        if (stats is not None and _stats_from_conv(bn, FusedSequential.fuse_stats) and (act is None or type(act) is nn.ReLU)
-                and fusable(bn, y)):
+        # (partial sums only for a BatchNorm that takes them: an eval-mode one normalises with its running statistics)
+        y, stats, skip = conv.forward_with_skip(x, want_stats=bool(_stats_from_conv(bn, FusedSequential.fuse_stats)))
+        if stats is not None and (act is None or type(act) is nn.ReLU) and fusable(bn, y):
             return bn_relu(y, bn, relu=act is not None, stats=stats), skip
         return bn_act(bn, act, y), skip
     return conv_bn_act(conv, bn, act, x), x
