@@ -36,6 +36,34 @@ def _snap(t):
     return Parameter(c, requires_grad=t.requires_grad) if isinstance(t, Parameter) else c
 
 
+# the per-task tensors of the unmasked layer kinds, (shared_layer_info key, attribute); the first key decides whether a task stored the module
+_NORM_FIELDS = ((nn.BatchNorm2d, (('bn_layer_weight', 'weight'), ('bn_layer_bias', 'bias'), ('bn_layer_running_mean', 'running_mean'),
+                                  ('bn_layer_running_var', 'running_var'))),
+                (nn.PReLU, (('prelu_layer_weight', 'weight'),)))
+
+
+def _norm_fields(module):
+    return next((fields for cls, fields in _NORM_FIELDS if isinstance(module, cls)), ())
+
+
+def _stored(info, name, module):
+    fields = _norm_fields(module)
+    return bool(fields) and name in info.get(fields[0][0], {})
+
+
+def stash_norm(info, name, module):
+    """Store a BatchNorm2d's statistics and affine, or a PReLU's slopes, of one task; any other module has none.  KeyError where `info`
+    lacks the key, as in the reference."""
+    for key, attr in _norm_fields(module):
+        info[key][name] = _snap(getattr(module, attr))
+
+
+def restore_norm(info, name, module):
+    """stash_norm's inverse, into the live tensors; KeyError on a module the task did not store."""
+    for key, attr in _norm_fields(module):
+        _put(getattr(module, attr), info[key][name])
+
+
 def collect_task_layers(model, shared_layer_info, dataset):
     """Refresh shared_layer_info[dataset] from the live modules (utils/manager.py:202-221).
 
@@ -55,13 +83,8 @@ def collect_task_layers(model, shared_layer_info, dataset):
                 info['bias'][name] = _snap(module.bias)
             if module.piggymask is not None:
                 info['piggymask'][name] = _snap(module.piggymask)
-        elif isinstance(module, nn.BatchNorm2d):
-            info['bn_layer_running_mean'][name] = _snap(module.running_mean)
-            info['bn_layer_running_var'][name] = _snap(module.running_var)
-            info['bn_layer_weight'][name] = _snap(module.weight)
-            info['bn_layer_bias'][name] = _snap(module.bias)
-        elif isinstance(module, nn.PReLU):
-            info['prelu_layer_weight'][name] = _snap(module.weight)
+        else:
+            stash_norm(info, name, module)
     return info
 
 
@@ -136,13 +159,8 @@ def attach_task_layers(model, shared_layer_info, dataset, piggymasks=False):
                     new = torch.full_like(module.weight.detach(), 0.0)
                     _put(new, pm.detach())
                     module.piggymask = Parameter(new)
-        elif isinstance(module, nn.BatchNorm2d) and name in info.get('bn_layer_weight', {}):
-            _put(module.running_mean, info['bn_layer_running_mean'][name])
-            _put(module.running_var, info['bn_layer_running_var'][name])
-            _put(module.weight, info['bn_layer_weight'][name])
-            _put(module.bias, info['bn_layer_bias'][name])
-        elif isinstance(module, nn.PReLU) and name in info.get('prelu_layer_weight', {}):
-            _put(module.weight, info['prelu_layer_weight'][name])
+        elif _stored(info, name, module):
+            restore_norm(info, name, module)
 
 
 def resize_masks(model, masks, mode):

@@ -24,34 +24,33 @@ from .. import _lib
 
 # CPG_MULTI_TENSOR=0: one cpg_sgd_route_step / cpg_adam_route_step launch per layer (the behaviour up to round 5; A/B switch)
 MULTI_TENSOR = os.environ.get('CPG_MULTI_TENSOR', '1') not in ('0', '')
-from ..models import layers as nl
 
 
-class MaskedSGD(torch.optim.SGD):
-    def __init__(self, params, pruner, lr, momentum=0.9, nesterov=True, **kw):
+class _RoutedSGD(torch.optim.SGD):
+    """What MaskedSGD and PackNetSGD share: a torch.optim.SGD whose step() sends every weight its pruner covers (`pruner._layers()`)
+    through `_launch` -- decay, routing and the momentum step in the library's one pass -- and leaves the rest to torch's own SGD."""
+
+    def __init__(self, params, pruner, lr, momentum, nesterov, kw):
         if kw.get('weight_decay', 0.0) != 0.0 or kw.get('dampening', 0.0) != 0.0:
-            raise ValueError('MaskedSGD mirrors the reference optimizer: weight_decay = dampening = 0 '
-                             '(the decay is applied by the gradient routing)')
+            raise ValueError('%s mirrors the reference optimizer: weight_decay = dampening = 0 '
+                             '(the decay is applied with the gradient routing)' % type(self).__name__)
         super().__init__(params, lr=lr, momentum=momentum, nesterov=nesterov, weight_decay=0.0, dampening=0.0)
         self.pruner = pruner
-        pruner.fused_weight_step = True          # tells the pruner to leave masked-weight grads to us
         self._masked = {}                        # id(param) -> mask name
 
-    def _refresh(self):
-        self._masked = {}
-        for name, module in self.pruner.model.named_modules():
-            if isinstance(module, (nl.SharableConv2d, nl.SharableLinear)):
-                self._masked[id(module.weight)] = name
+    def _launch(self, rows, hyper, s):
+        """Step the (w, grad, momentum, owner, n) rows of one launch; hyper = (cur, wd, lr, momentum, nesterov, first_step)."""
+        raise NotImplementedError
 
     @torch.no_grad()
     def step(self, closure=None):
-        if not self._masked:
-            self._refresh()
-        s = _lib.stream_ptr()
         pr = self.pruner
+        if not self._masked:
+            self._masked = {id(module.weight): name for name, module in pr._layers()}
+        s = _lib.stream_ptr()
         held = []
         for group in self.param_groups:
-            # every masked weight of the group that shares `first` (no momentum buffer yet / has one) goes into ONE multi-tensor launch
+            # every covered weight of the group that shares `first` (no momentum buffer yet / has one) goes into ONE multi-tensor launch
             # (cpg_sgd_route_step_multi: 53 layers of ResNet-50 = 2 launches instead of 53)
             batches = {True: [], False: []}
             for p in group['params']:
@@ -59,7 +58,7 @@ class MaskedSGD(torch.optim.SGD):
                 if name is None or p.grad is None:
                     continue
                 state = self.state[p]
-                first = 'momentum_buffer' not in state or state['momentum_buffer'] is None
+                first = state.get('momentum_buffer') is None
                 if first:
                     state['momentum_buffer'] = torch.empty_like(p, memory_format=torch.contiguous_format)
                 owner = pr._owner(name, p.data)
@@ -69,20 +68,31 @@ class MaskedSGD(torch.optim.SGD):
                 held.append((p, p.grad))
                 p.grad = None                    # hide from torch's SGD for the rest of this step
             for first, rows in batches.items():
-                if not rows:
-                    continue
-                if not MULTI_TENSOR:
-                    for w_, g_, b_, o_, n_ in rows:
-                        _lib.call('cpg_sgd_route_step', w_, g_, b_, o_, int(pr.current_dataset_idx), float(pr.args.weight_decay), float(group['lr']),
-                                  float(group['momentum']), int(bool(group['nesterov'])), int(first), n_, s)
-                    continue
-                items = (_lib.SgdItem * len(rows))(*rows)
-                _lib.call('cpg_sgd_route_step_multi', items, len(rows), int(pr.current_dataset_idx), float(pr.args.weight_decay), float(group['lr']),
-                          float(group['momentum']), int(bool(group['nesterov'])), int(first), s)
+                if rows:
+                    self._launch(rows, (int(pr.current_dataset_idx), float(pr.args.weight_decay), float(group['lr']), float(group['momentum']),
+                                        int(bool(group['nesterov'])), int(first)), s)
         loss = super().step(closure)
         for p, g in held:
             p.grad = g
         return loss
+
+
+def _launch_multi(entry, rows, hyper, s):
+    _lib.call(entry, (_lib.SgdItem * len(rows))(*rows), len(rows), *hyper, s)
+
+
+class MaskedSGD(_RoutedSGD):
+    """The CPG step: every SharableConv2d / SharableLinear `.weight` through cpg_sgd_route_step_multi."""
+
+    def __init__(self, params, pruner, lr, momentum=0.9, nesterov=True, **kw):
+        super().__init__(params, pruner, lr, momentum, nesterov, kw)
+        pruner.fused_weight_step = True          # tells the pruner to leave masked-weight grads to us
+
+    def _launch(self, rows, hyper, s):
+        if MULTI_TENSOR:
+            return _launch_multi('cpg_sgd_route_step_multi', rows, hyper, s)
+        for w_, g_, b_, o_, n_ in rows:
+            _lib.call('cpg_sgd_route_step', w_, g_, b_, o_, *hyper, n_, s)
 
 
 class MaskedAdam(torch.optim.Adam):
@@ -101,10 +111,7 @@ class MaskedAdam(torch.optim.Adam):
         self._masked = {}
 
     def _refresh(self):
-        self._masked = {}
-        for name, module in self.pruner.model.named_modules():
-            if isinstance(module, (nl.SharableConv2d, nl.SharableLinear)) and module.piggymask is not None:
-                self._masked[id(module.piggymask)] = name
+        self._masked = {id(module.piggymask): name for name, module in self.pruner._layers() if module.piggymask is not None}
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -164,7 +171,7 @@ class MaskedAdam(torch.optim.Adam):
         return loss
 
 
-class PackNetSGD(torch.optim.SGD):
+class PackNetSGD(_RoutedSGD):
     """MaskedSGD's counterpart for the PackNet baseline stack (packnet_cifar100_main_normal.py:229-230 + utils/packnet_manager.py:63-69):
     a torch.optim.SGD whose step() sends every weight the PackNet pruner covers (utils.packnet_prune.SparsePruner: each nn.Conv2d /
     nn.Linear outside `classifiers`) through ONE multi-tensor pass that adds the weight decay, routes the gradient, takes the
@@ -183,57 +190,24 @@ class PackNetSGD(torch.optim.SGD):
     MODES = ('fused', 'step+zero', 'unfused')
 
     def __init__(self, params, pruner, lr, momentum=0.9, nesterov=True, mode='fused', **kw):
-        if kw.get('weight_decay', 0.0) != 0.0 or kw.get('dampening', 0.0) != 0.0:
-            raise ValueError('PackNetSGD mirrors the reference optimizer: weight_decay = dampening = 0 '
-                             '(the decay is applied with the gradient routing)')
         if mode not in self.MODES:
             raise ValueError('PackNetSGD mode must be one of %s, got %r' % (', '.join(self.MODES), mode))
-        super().__init__(params, lr=lr, momentum=momentum, nesterov=nesterov, weight_decay=0.0, dampening=0.0)
-        self.pruner, self.mode = pruner, mode
+        super().__init__(params, pruner, lr, momentum, nesterov, kw)
+        self.mode = mode
         pruner.fused_weight_step = mode != 'unfused'
-        self._masked = {}                        # id(param) -> mask name
 
     def detach(self):
         """Hand decay, routing and zeroing back to the pruner's own methods (another optimizer takes over)."""
         self.pruner.fused_weight_step = False
 
-    @torch.no_grad()
+    def _launch(self, rows, hyper, s):
+        if self.mode == 'fused':
+            return _launch_multi('cpg_sgd_route_zero_step_multi', rows, hyper, s)
+        _launch_multi('cpg_sgd_route_step_multi', rows, hyper, s)
+        for w_, _, _, o_, n_ in rows:
+            _lib.call('cpg_zero_pruned', w_, o_, n_, s)
+
     def step(self, closure=None):
         if self.mode == 'unfused':
-            return super().step(closure)
-        pr = self.pruner
-        if not self._masked:
-            self._masked = {id(module.weight): name for name, module in pr._layers()}
-        s = _lib.stream_ptr()
-        entry = 'cpg_sgd_route_zero_step_multi' if self.mode == 'fused' else 'cpg_sgd_route_step_multi'
-        held, zero_after = [], []
-        for group in self.param_groups:
-            batches = {True: [], False: []}      # rows that share first_step go into one launch, as in MaskedSGD
-            for p in group['params']:
-                name = self._masked.get(id(p))
-                if name is None or p.grad is None:
-                    continue
-                state = self.state[p]
-                first = state.get('momentum_buffer') is None
-                if first:
-                    state['momentum_buffer'] = torch.empty_like(p, memory_format=torch.contiguous_format)
-                owner = pr._owner(name, p.data)
-                batches[first].append((_lib.dptr(p.data, name='weight').value, _lib.dptr(p.grad, name='weight.grad').value,
-                                       _lib.dptr(state['momentum_buffer'], name='momentum').value,
-                                       _lib.dptr(owner, torch.uint8, 'mask').value, p.numel()))
-                held.append((p, p.grad))
-                p.grad = None                    # hide from torch's SGD for the rest of this step
-            for first, rows in batches.items():
-                if not rows:
-                    continue
-                items = (_lib.SgdItem * len(rows))(*rows)
-                _lib.call(entry, items, len(rows), int(pr.current_dataset_idx), float(pr.args.weight_decay), float(group['lr']),
-                          float(group['momentum']), int(bool(group['nesterov'])), int(first), s)
-                if self.mode == 'step+zero':
-                    zero_after += rows
-        for w_, _, _, o_, n_ in zero_after:
-            _lib.call('cpg_zero_pruned', w_, o_, n_, s)
-        loss = super().step(closure)
-        for p, g in held:
-            p.grad = g
-        return loss
+            return torch.optim.SGD.step(self, closure)
+        return super().step(closure)

@@ -64,36 +64,58 @@ def make_criterion(args):
     return CrossEntropyLoss()
 
 
-class Manager(object):
-    """Handles training and pruning (utils/manager.py:16-37)."""
+class ManagerBase(object):
+    """What the CPG and PackNet Managers share outside their train / validate loops: the fields both set, the progress line and
+    the checkpoint path."""
 
-    def __init__(self, args, model, shared_layer_info, masks, train_loader, val_loader, begin_prune_step, end_prune_step):
+    def __init__(self, args, model, shared_layer_info, train_loader, val_loader):
         self.args = args
         self.model = model
         self.shared_layer_info = shared_layer_info
-        root = model.module if hasattr(model, 'module') else model
-        self.inference_dataset_idx = root.datasets.index(args.dataset) + 1
+        self.inference_dataset_idx = self._root().datasets.index(args.dataset) + 1
+        self.train_loader = train_loader
+        self.val_loader = val_loader
+        self.progress = bool(getattr(args, 'progress', True)) and tqdm is not None
+        self.postfix_interval = float(getattr(args, 'postfix_interval', 0.5))
+        self.last_stats = {}
+
+    def _root(self):
+        return ckpt._root(self.model)
+
+    def _bar(self, total, desc):
+        return tqdm(total=total, desc=desc, ascii=True) if self.progress else _NullBar()
+
+    def _postfix_due(self, last_post, batch_idx, nbatches):
+        """Refresh the progress line now?  On a wall-clock interval since `last_post`, and at the last batch."""
+        return self.progress and (time.time() - last_post >= self.postfix_interval or batch_idx + 1 == nbatches)
+
+    def _to_device(self, data, target):
+        if getattr(self.args, 'cuda', True):
+            data, target = data.cuda(non_blocking=True), target.cuda(non_blocking=True)
+        return data, target
+
+    def _path(self, folder, epoch):
+        return self.args.checkpoint_format.format(save_folder=folder, epoch=epoch)
+
+
+class Manager(ManagerBase):
+    """Handles training and pruning (utils/manager.py:16-37)."""
+
+    def __init__(self, args, model, shared_layer_info, masks, train_loader, val_loader, begin_prune_step, end_prune_step):
+        super().__init__(args, model, shared_layer_info, train_loader, val_loader)
         self.pruner = SparsePruner(self.model, masks, self.args, begin_prune_step, end_prune_step,
                                    self.inference_dataset_idx)
         if hasattr(model, 'set_gradient_filter'):
             # data parallel: exchange only the gradient slots that survive the routing below (it runs right after the sync)
             model.set_gradient_filter(self.pruner)
-        self.train_loader = train_loader
-        self.val_loader = val_loader
         if getattr(args, 'freeze_gc', False):
             # OPT-IN (args.freeze_gc; no counterpart in the reference): the model, its masks and the pruner exist now -- one full collection,
             # then gc.freeze(): removes the 80 ms generation-2 collector pauses from the step loop (cpg_amd.utils.settle_host_gc: process-wide)
             from . import settle_host_gc
             settle_host_gc()
-        self.progress = bool(getattr(args, 'progress', True)) and tqdm is not None
-        self.last_stats = {}
         self.last_lfw = None
-        self.postfix_interval = float(getattr(args, 'postfix_interval', 0.5))
         self.fused_loss = bool(getattr(args, 'fused_loss', False))
         self.criterion = make_criterion(args)
-
-    def _bar(self, total, desc):
-        return tqdm(total=total, desc=desc, ascii=True) if self.progress else _NullBar()
 
     def _loss_and_accuracy(self, data, target, train):
         """(loss, accuracy of the batch or None), in the reference's order of calls: train computes the accuracy before the loss (and none
@@ -101,7 +123,7 @@ class Manager(object):
         task's head takes the embeddings -- the trunk and the 512-wide linear layer in front of AngleLinear are the calls `model(data)` makes."""
         face = self.args.dataset == 'face_verification'
         if self.fused_loss and face and train:
-            root = self.model.module if hasattr(self.model, 'module') else self.model
+            root = self._root()
             return self.criterion.head_loss(root.forward_to_embeddings(data), root.classifier[1], target), None
         output = self.model(data)
         if self.fused_loss and not face:
@@ -112,11 +134,6 @@ class Manager(object):
             return self.criterion(output, target), accuracy
         loss = self.criterion(output, target)
         return loss, classification_accuracy(output, target)
-
-    def _to_device(self, data, target):
-        if getattr(self.args, 'cuda', True):
-            data, target = data.cuda(non_blocking=True), target.cuda(non_blocking=True)
-        return data, target
 
     def train(self, optimizers, epoch_idx, curr_lrs, curr_prune_step):
         """One epoch of the hot loop (utils/manager.py:39-100). Returns (avg_train_acc, curr_prune_step)."""
@@ -146,9 +163,8 @@ class Manager(object):
                 # the mask statistic of the progress line is computed EVERY step, as the reference does
                 # (utils/manager.py:77-88); it is one histogram pass that is cached until a mask mutates
                 self.last_stats = {'sparsity': self.pruner.calculate_sparsity()}
-                now = time.time()
-                if self.progress and (now - last_post >= self.postfix_interval or batch_idx + 1 == nbatches):
-                    last_post = now
+                if self._postfix_due(last_post, batch_idx, nbatches):
+                    last_post = time.time()
                     t.set_postfix({'loss': train_loss.avg.item(),
                                    'accuracy': '{:.2f}'.format(100. * train_accuracy.avg.item()),
                                    'lr': curr_lrs[0],
@@ -196,9 +212,8 @@ class Manager(object):
                     if idx != 1:
                         stats['shared_ratio'] = self.pruner.calculate_shared_part_ratio()
                     self.last_stats = stats
-                    now = time.time()
-                    if self.progress and (now - last_post >= self.postfix_interval or bi + 1 == nbatches):
-                        last_post = now
+                    if self._postfix_due(last_post, bi, nbatches):
+                        last_post = time.time()
                         post = {'loss': val_loss.avg.item(),
                                 'accuracy': '{:.2f}'.format(100. * val_accuracy.avg.item())}
                         post.update(stats)
@@ -232,7 +247,7 @@ class Manager(object):
         if hasattr(self.model, 'sync_buffers'):
             self.model.sync_buffers()
         self.model.eval()
-        root = self.model.module if hasattr(self.model, 'module') else self.model
+        root = self._root()
         out = []
         with torch.no_grad():
             for batch in self.val_loader:
@@ -278,9 +293,6 @@ class Manager(object):
         return mean
 
     # ------------------------------------------------------------------ checkpoints (utils/manager.py:198-320)
-    def _path(self, folder, epoch):
-        return self.args.checkpoint_format.format(save_folder=folder, epoch=epoch)
-
     def save_checkpoint(self, optimizers, epoch_idx, save_folder):
         """Same dict layout as the reference; optimizer state is not saved (momentum restarts each phase)."""
         ckpt.save_checkpoint(self.model, self.pruner.masks, self.shared_layer_info, self.args.dataset,

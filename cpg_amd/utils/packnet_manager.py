@@ -21,8 +21,8 @@ import torch
 import torch.nn as nn
 
 from . import Metric, classification_accuracy
-from .checkpoint import _HEAD_ALIAS, _put, _snap
-from .manager import _NullBar, make_criterion, tqdm
+from .checkpoint import _HEAD_ALIAS, _put, _snap, restore_norm, stash_norm
+from .manager import ManagerBase, make_criterion
 from .packnet_prune import SparsePruner
 
 TASK_KEYS = ('conv_bias', 'bn_layer_running_mean', 'bn_layer_running_var', 'bn_layer_weight', 'bn_layer_bias', 'fc_bias')
@@ -39,33 +39,14 @@ def make_masks(model):
             if isinstance(m, (nn.Conv2d, nn.Linear)) and 'classifiers' not in name}
 
 
-class Manager(object):
+class Manager(ManagerBase):
     """Handles training and pruning (utils/packnet_manager.py:13-33)."""
 
     def __init__(self, args, model, shared_layer_info, masks, train_loader, val_loader):
-        self.args = args
-        self.model = model
-        self.shared_layer_info = shared_layer_info
-        self.inference_dataset_idx = self._root().datasets.index(args.dataset) + 1
+        super().__init__(args, model, shared_layer_info, train_loader, val_loader)
         self.pruner = SparsePruner(self.model, masks, self.args, None, None, self.inference_dataset_idx)
-        self.train_loader = train_loader
-        self.val_loader = val_loader
         # AngleLoss / class-weighted / plain cross-entropy (:25-32), stock torch
         self.criterion = make_criterion(types.SimpleNamespace(dataset=args.dataset, cuda=getattr(args, 'cuda', True), fused_loss=False))
-        self.progress = bool(getattr(args, 'progress', True)) and tqdm is not None
-        self.postfix_interval = float(getattr(args, 'postfix_interval', 0.5))
-        self.last_stats = {}
-
-    def _root(self):
-        return self.model.module if hasattr(self.model, 'module') else self.model
-
-    def _bar(self, total, desc):
-        return tqdm(total=total, desc=desc, ascii=True) if self.progress else _NullBar()
-
-    def _to_device(self, data, target):
-        if getattr(self.args, 'cuda', True):
-            data, target = data.cuda(non_blocking=True), target.cuda(non_blocking=True)
-        return data, target
 
     def train(self, optimizers, epoch_idx, curr_lrs):
         """One epoch (utils/packnet_manager.py:35-76).  Returns the average train accuracy."""
@@ -87,9 +68,8 @@ class Manager(object):
                 optimizers.step()
                 self.pruner.make_pruned_zero()
                 self.last_stats = {'sparsity': self.pruner.calculate_sparsity()}
-                now = time.time()
-                if self.progress and (now - last_post >= self.postfix_interval or batch_idx + 1 == nbatches):
-                    last_post = now
+                if self._postfix_due(last_post, batch_idx, nbatches):
+                    last_post = time.time()
                     t.set_postfix({'loss': train_loss.avg.item(), 'accuracy': '{:.2f}'.format(100. * train_accuracy.avg.item()),
                                    'lr': curr_lrs[0], 'sparsity': self.last_stats['sparsity']})
                 t.update(1)
@@ -117,9 +97,8 @@ class Manager(object):
                     self.last_stats = {'sparsity': self.pruner.calculate_sparsity(),
                                        'task{} ratio'.format(idx): self.pruner.calculate_curr_task_ratio(),
                                        'zero ratio': self.pruner.calculate_zero_ratio()}
-                    now = time.time()
-                    if self.progress and (now - last_post >= self.postfix_interval or bi + 1 == nbatches):
-                        last_post = now
+                    if self._postfix_due(last_post, bi, nbatches):
+                        last_post = time.time()
                         t.set_postfix(dict({'loss': val_loss.avg.item(), 'accuracy': '{:.2f}'.format(100. * val_accuracy.avg.item())},
                                            **self.last_stats))
                     t.update(1)
@@ -133,9 +112,6 @@ class Manager(object):
         self.pruner.one_shot_prune(one_shot_prune_perc)
 
     # ------------------------------------------------------------------ checkpoints (utils/packnet_manager.py:151-239)
-    def _path(self, folder, epoch):
-        return self.args.checkpoint_format.format(save_folder=folder, epoch=epoch)
-
     def collect_task_layers(self):
         """Refresh shared_layer_info[dataset] from the live modules (:155-173)."""
         info = self.shared_layer_info.setdefault(self.args.dataset, new_task_info())
@@ -143,15 +119,11 @@ class Manager(object):
             if isinstance(module, nn.Conv2d):
                 if module.bias is not None:
                     info['conv_bias'][name] = _snap(module.bias)
-            elif isinstance(module, nn.BatchNorm2d):
-                info['bn_layer_running_mean'][name] = _snap(module.running_mean)
-                info['bn_layer_running_var'][name] = _snap(module.running_var)
-                info['bn_layer_weight'][name] = _snap(module.weight)
-                info['bn_layer_bias'][name] = _snap(module.bias)
-            elif isinstance(module, nn.Linear) and 'features' in name:
-                info['fc_bias'][name] = _snap(module.bias)
-            elif isinstance(module, nn.PReLU):
-                info['prelu_layer_weight'][name] = _snap(module.weight)       # KeyError without the key, as in the reference
+            elif isinstance(module, nn.Linear):
+                if 'features' in name:
+                    info['fc_bias'][name] = _snap(module.bias)
+            else:
+                stash_norm(info, name, module)       # (prelu_layer_weight: KeyError without the key, as in the reference)
         return info
 
     def attach_task_layers(self):
@@ -161,15 +133,11 @@ class Manager(object):
             if isinstance(module, nn.Conv2d):
                 if module.bias is not None:
                     _put(module.bias, info['conv_bias'][name])
-            elif isinstance(module, nn.BatchNorm2d):
-                _put(module.running_mean, info['bn_layer_running_mean'][name])
-                _put(module.running_var, info['bn_layer_running_var'][name])
-                _put(module.weight, info['bn_layer_weight'][name])
-                _put(module.bias, info['bn_layer_bias'][name])
-            elif isinstance(module, nn.Linear) and 'features' in name:
-                _put(module.bias, info['fc_bias'][name])
-            elif isinstance(module, nn.PReLU):
-                _put(module.weight, info['prelu_layer_weight'][name])
+            elif isinstance(module, nn.Linear):
+                if 'features' in name:
+                    _put(module.bias, info['fc_bias'][name])
+            else:
+                restore_norm(info, name, module)
 
     def checkpoint_dict(self):
         self.collect_task_layers()

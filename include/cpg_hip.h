@@ -305,6 +305,9 @@ int cpg_adam_route_step(float *pm, float *gpm, float *exp_avg, float *exp_avg_sq
  * launch, so nothing is copied to the device and the array may be freed or reused when the call returns.  All items share the scalar
  * arguments -- callers group parameters by (lr, momentum, nesterov, first_step) / (lr, betas, eps, step) as torch's own foreach path
  * does.  Element for element the arithmetic is cpg_sgd_route_step's / cpg_adam_route_step's: results are bit-equal to per-layer calls.
+ * Every row is checked before the first launch -- null pointers, a negative n, and the 2^30-block limit of the launch the row falls
+ * into: a bad table returns CPG_E_INVALID and changes nothing, however many launches' worth of good rows precede the bad one.  This
+ * holds for cpg_sgd_route_step_multi, cpg_sgd_route_zero_step_multi and cpg_adam_route_step_multi alike.
  * Replaces the same reference lines: utils/prune.py:195-211 + CPG_cifar100_main_normal.py:339-346. */
 typedef struct cpg_sgd_item {
     float *w, *gw, *momentum_buf;

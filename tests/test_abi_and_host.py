@@ -153,6 +153,19 @@ def test_pinned_accumulator_macros_are_defined_once():
         assert not [n for n in names if re.match(r'W\w+?_(ONE_\d+|RD_)', n)], path
 
 
+def test_routed_optimizer_arithmetic_is_written_once():
+    """mask_kernels.hip holds ONE definition of the fused SGD update and ONE of the fused Adam update (sgd_route_one, adam_route_one);
+    the per-layer and the multi-tensor kernels call them, so the two forms cannot drift apart."""
+    src = open(os.path.join(ROOT, 'cpg_amd', 'csrc', 'mask_kernels.hip')).read()
+    code = re.sub(r'//[^\n]*', '', src)
+    for update in (r'__fmul_rn\((\w+\.)?momentum,', r'fmaf\(-(\w+\.)?lr,', r'fmaf\((\w+\.)?omb1,', r'fmaf\((\w+\.)?omb2,', r'sqrtf\('):
+        assert len(re.findall(update, code)) == 1, update
+    for name in ('sgd_route_one', 'adam_route_one'):
+        assert len(re.findall(r'__device__ __forceinline__ void %s\(' % name, code)) == 1, name
+    for retired in ('auto one =', 'is16('):
+        assert retired not in code, retired
+
+
 def test_struct_layouts_match_header():
     import ctypes
     assert ctypes.sizeof(L.ConvDesc) == 14 * 4

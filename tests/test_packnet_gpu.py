@@ -105,22 +105,28 @@ def test_route_zero_step_bit_equals_step_then_zero(ragged, cur, first, nesterov)
         assert w_out[frozen].tobytes() == w_in[frozen].tobytes()
 
 
-def test_route_zero_step_multi_rejects_a_bad_table_before_any_launch(ragged):
+@pytest.mark.parametrize('entry', ['cpg_sgd_route_zero_step_multi', 'cpg_sgd_route_step_multi', 'cpg_adam_route_step_multi'])
+def test_route_zero_step_multi_rejects_a_bad_table_before_any_launch(ragged, entry):
+    """All three multi-tensor entry points check every row before their first launch: a null pointer in the last of 69 rows, past the
+    first launch's 48, returns CPG_E_INVALID and leaves every tensor bytewise as it was.  (Adam's two moments: buf and |buf|.)"""
     L = _lib()
     sizes, offs, flats = ragged
-    w, gw, buf, owner = (t.clone() for t in flats)
-    ws, gs, bs, os_ = (_views(t, sizes, offs) for t in (w, gw, buf, owner))
-    rows = [(a.data_ptr(), b.data_ptr(), c.data_ptr(), d.data_ptr(), a.numel()) for a, b, c, d in zip(ws, gs, bs, os_) if a.numel()]
-    rows[-1] = (rows[-1][0], None, rows[-1][2], rows[-1][3], rows[-1][4])          # the 69th row: after the first launch's worth of layers
+    adam = entry == 'cpg_adam_route_step_multi'
+    before = list(flats[:3]) + ([flats[2].abs()] if adam else [])
+    tensors = [t.clone() for t in before]
+    views = [_views(t, sizes, offs) for t in tensors + [flats[3]]]
+    rows = [tuple(v.data_ptr() for v in row) + (row[0].numel(),) for row in zip(*views) if row[0].numel()]
+    rows[-1] = (rows[-1][0], None) + rows[-1][2:]                                  # the 69th row: after the first launch's worth of layers
     assert len(rows) > L.lib().cpg_multi_tensor_max()
-    items = (L.SgdItem * len(rows))(*rows)
+    items = (L.AdamItem if adam else L.SgdItem) * len(rows)
+    hyper = (2, L.MODE_FINETUNE, 5e-4, 0.9, 0.999, 1e-8, 3) if adam else (2, 4e-5, 1e-2, 0.9, 1, 0)
     with pytest.raises(L.CpgHipError) as e:
-        L.call('cpg_sgd_route_zero_step_multi', items, len(rows), 2, 4e-5, 1e-2, 0.9, 1, 0, L.stream_ptr())
+        L.call(entry, items(*rows), len(rows), *hyper, L.stream_ptr())
     assert e.value.code == L.CPG_E_INVALID
     with pytest.raises(L.CpgHipError):
         L.call('cpg_sgd_route_zero_step', None, None, None, None, 2, 4e-5, 1e-2, 0.9, 1, 0, 8, L.stream_ptr())
     torch.cuda.synchronize()
-    assert torch.equal(w, flats[0]) and torch.equal(gw, flats[1]) and torch.equal(buf, flats[2])
+    assert all(torch.equal(t, t0) for t, t0 in zip(tensors, before))
 
 
 # ================================================================ raw ABI: the zeroing prune
