@@ -35,6 +35,55 @@ __device__ __forceinline__ double block_sum(double v, double *red) {
     return red[0] + red[1] + red[2] + red[3];       // fixed order
 }
 
+// The four per-channel scalars of a plane (or slice) in registers, and the formulas of cpg_common.h on them.
+struct BnChan {
+    float m, is, ga, be;
+    __device__ __forceinline__ BnChan(const float *mean, const float *invstd, const float *gamma, const float *beta, int c)
+        : m(mean[c]), is(invstd[c]), ga(gamma[c]), be(beta[c]) {}
+    __device__ __forceinline__ float xhat(float x) const { return bn_xhat(x, m, is); }
+    __device__ __forceinline__ float affine(float x) const { return bn_affine(x, m, is, ga, be); }
+    __device__ __forceinline__ float relu(float x) const { return bn_relu_affine(x, m, is, ga, be); }
+};
+// ... and what the backward apply passes add: the two means of the reduction (TRAIN) and scale = invstd * gamma.
+// dx<RELU>(x, g): TRAIN: (g - mean(g) - xhat * mean(g xhat)) * invstd * gamma ; EVAL (fixed statistics): g * invstd * gamma
+template <bool TRAIN>
+struct BnBwdChan : BnChan {
+    float mg, mgx, scale;
+    __device__ __forceinline__ BnBwdChan(const float *mean, const float *invstd, const float *gamma, const float *beta, const float *coef, int c)
+        : BnChan(mean, invstd, gamma, beta, c), mg(TRAIN ? coef[2 * c] : 0.f), mgx(TRAIN ? coef[2 * c + 1] : 0.f), scale(is * ga) {}
+    template <bool RELU>
+    __device__ __forceinline__ float dx(float xv, float gv) const {
+        return bn_bwd_apply_one<RELU, TRAIN>(xv, gv, m, is, ga, be, mg, mgx, scale);
+    }
+};
+
+// The (channel, image-slice) reduction block, grid (C, slices): channel c, images [n0, n1), NS fp32 running sums that flush() folds
+// into their fp64 partners, and store(): the block's fp64 totals, merged in a fixed order, as partial[c][slice][0 .. NS) (two slots
+// per (c, slice) whatever NS is).  Two-stage and without float atomics: results do not depend on block scheduling.
+template <int NS>
+struct SliceSums {
+    const BnDims &d;
+    const int c, s, n0, n1;
+    float run[NS] = {};
+    double sum[NS] = {};
+    __device__ __forceinline__ explicit SliceSums(const BnDims &dims)
+        : d(dims), c(blockIdx.x), s(blockIdx.y), n0(s * d.imgs_per_slice), n1(min(d.N, n0 + d.imgs_per_slice)) {}
+    __device__ __forceinline__ int64_t plane(int n) const { return (int64_t)n * d.C + c; }
+    __device__ __forceinline__ void flush() {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) sum[k] += (double)run[k], run[k] = 0.f;
+    }
+    __device__ __forceinline__ void store(double *partial) {
+        __shared__ double red[4];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) sum[k] = block_sum(sum[k], red);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < NS; ++k) partial[((int64_t)c * d.slices + s) * 2 + k] = sum[k];
+        }
+    }
+};
+
 // Visit item j < P of every image plane n in [n0, n1): f(n, j), with flush() at least every 64 visits of a thread (the
 // backward reductions keep fp32 running sums and fold them into fp64 there; k_bn_stats sums in fp64 and passes a no-op).  No per-element division: large planes are walked
 // image by image (4 independent visits per loop trip, so 4 loads are in flight per thread -- the one-visit-per-trip
@@ -78,48 +127,32 @@ __device__ __forceinline__ void walk_planes(int P, int n0, int n1, F &&f, FL &&f
 
 // grid (C, slices): partial[c][slice] = {sum, sumsq} over images [s*ips, (s+1)*ips)
 __global__ __launch_bounds__(kThreads) void k_bn_stats(const float *__restrict__ x, BnDims d, double *__restrict__ partial) {
-    __shared__ double red[4];
-    const int c = blockIdx.x, s = blockIdx.y;
-    const int n0 = s * d.imgs_per_slice, n1 = min(d.N, n0 + d.imgs_per_slice);
     // Both sums in fp64 from the first term on: var = E[x^2] - mean^2 loses (mean / std)^2 of whatever precision the sums have.  With
     // fp32 products and fp32 running sums folded into fp64 every <= 256 terms invstd was off by 1.4e-3 at |mean| / std = 800
     // (tests/test_autograd_contract_gpu.py); a dozen fp64 operations per 16 bytes stay far below the memory time.
-    double ds = 0.0, dss = 0.0;
+    SliceSums<2> acc(d);
     const bool vec = (d.HW & 3) == 0 && (((uintptr_t)x) & 15) == 0;
     auto flush = []() {};
     if (vec)
-        walk_planes(d.HW >> 2, n0, n1, [&](int n, int j) {
-            const float4 v = *reinterpret_cast<const float4 *>(x + ((int64_t)n * d.C + c) * d.HW + 4 * j);
+        walk_planes(d.HW >> 2, acc.n0, acc.n1, [&](int n, int j) {
+            const float4 v = *reinterpret_cast<const float4 *>(x + acc.plane(n) * d.HW + 4 * j);
             const double a = v.x, b = v.y, e = v.z, f = v.w;
-            ds += (a + b) + (e + f);
-            dss += (a * a + b * b) + (e * e + f * f);
+            acc.sum[0] += (a + b) + (e + f);
+            acc.sum[1] += (a * a + b * b) + (e * e + f * f);
         }, flush);
     else
-        walk_planes(d.HW, n0, n1, [&](int n, int j) {
-            const double v = x[((int64_t)n * d.C + c) * d.HW + j];
-            ds += v;
-            dss += v * v;
+        walk_planes(d.HW, acc.n0, acc.n1, [&](int n, int j) {
+            const double v = x[acc.plane(n) * d.HW + j];
+            acc.sum[0] += v;
+            acc.sum[1] += v * v;
         }, flush);
-    const double ts = block_sum(ds, red);
-    const double tss = block_sum(dss, red);
-    if (threadIdx.x == 0) {
-        partial[((int64_t)c * d.slices + s) * 2 + 0] = ts;
-        partial[((int64_t)c * d.slices + s) * 2 + 1] = tss;
-    }
+    acc.store(partial);
 }
 
-// one thread per channel: fixed-order merge, mean / biased var / invstd, running statistics
-// (torch.nn.BatchNorm2d semantics: running_var uses the unbiased variance, momentum m)
-__global__ void k_bn_finalize(const double *__restrict__ partial, BnDims d, float eps, float momentum, float *__restrict__ mean,
-                              float *__restrict__ invstd, float *__restrict__ running_mean, float *__restrict__ running_var) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= d.C) return;
-    double s = 0.0, ss = 0.0;
-    for (int k = 0; k < d.slices; ++k) {
-        s += partial[((int64_t)c * d.slices + k) * 2 + 0];
-        ss += partial[((int64_t)c * d.slices + k) * 2 + 1];
-    }
-    const double n = (double)d.N * d.HW;
+// what both statistics kernels end in, for channel c with sum s and sum of squares ss over n elements: mean / clamped biased variance /
+// invstd, and the running statistics (torch.nn.BatchNorm2d semantics: running_var uses the unbiased variance, momentum m)
+__device__ __forceinline__ void bn_stats_tail(int c, double s, double ss, double n, float eps, float momentum, float *mean, float *invstd,
+                                              float *running_mean, float *running_var) {
     const double m = s / n;
     double var = ss / n - m * m;
     if (var < 0.0) var = 0.0;
@@ -132,8 +165,30 @@ __global__ void k_bn_finalize(const double *__restrict__ partial, BnDims d, floa
     }
 }
 
+// one thread per channel: fixed-order merge of the slices
+__global__ void k_bn_finalize(const double *__restrict__ partial, BnDims d, float eps, float momentum, float *__restrict__ mean,
+                              float *__restrict__ invstd, float *__restrict__ running_mean, float *__restrict__ running_var) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= d.C) return;
+    double s = 0.0, ss = 0.0;
+    for (int k = 0; k < d.slices; ++k) {
+        s += partial[((int64_t)c * d.slices + k) * 2 + 0];
+        ss += partial[((int64_t)c * d.slices + k) * 2 + 1];
+    }
+    bn_stats_tail(c, s, ss, (double)d.N * d.HW, eps, momentum, mean, invstd, running_mean, running_var);
+}
+
 // GROUP threads (a whole block, or one wave for small feature maps) own one (n, c) plane at a time, so the
-// four per-channel scalars sit in registers and every access is a contiguous 16 B per lane.
+// four per-channel scalars sit in registers and every access is a contiguous 16 B per lane: body(plane, channel, lane in the group)
+template <int GROUP, class F>
+__device__ __forceinline__ void walk_plane_groups(const BnDims &d, F body) {
+    const int64_t planes = (int64_t)d.N * d.C;
+    const int gl = threadIdx.x % GROUP;
+    const int64_t g0 = (int64_t)blockIdx.x * (kThreads / GROUP) + threadIdx.x / GROUP;
+    const int64_t gstride = (int64_t)gridDim.x * (kThreads / GROUP);
+    for (int64_t pl = g0; pl < planes; pl += gstride) body(pl, (int)(pl % d.C), gl);
+}
+
 // `res` (may be null): a residual added before the ReLU -- the tail of a ResNet block, relu(bn3(conv3) + identity).
 // `mask` (may be null; needs 4 | HW and 16-byte aligned tensors): one byte per float4 of y whose bits 0-3 say which of its four
 // elements are > 0 -- the ReLU mask the backward of relu(bn(x) + res) needs (it cannot be recomputed from x alone), at 1/16 of the
@@ -143,23 +198,18 @@ __global__ __launch_bounds__(kThreads) void k_bn_apply(const float *__restrict__
                                                        float *__restrict__ y, BnDims d, const float *__restrict__ mean,
                                                        const float *__restrict__ invstd, const float *__restrict__ gamma,
                                                        const float *__restrict__ beta, uint8_t *__restrict__ mask = nullptr) {
-    const int64_t planes = (int64_t)d.N * d.C;
     const bool vec = (d.HW & 3) == 0 && (((uintptr_t)x) & 15) == 0 && (((uintptr_t)y) & 15) == 0 && (((uintptr_t)res) & 15) == 0;
-    const int gl = threadIdx.x % GROUP;
-    const int64_t g0 = (int64_t)blockIdx.x * (kThreads / GROUP) + threadIdx.x / GROUP;
-    const int64_t gstride = (int64_t)gridDim.x * (kThreads / GROUP);
-    for (int64_t pl = g0; pl < planes; pl += gstride) {
-        const int c = (int)(pl % d.C);
-        const float m = mean[c], is = invstd[c], g = gamma[c], b = beta[c];
+    walk_plane_groups<GROUP>(d, [&](int64_t pl, int c, int gl) {
+        const BnChan ch(mean, invstd, gamma, beta, c);
         const float *p = x + pl * d.HW;
         float *q = y + pl * d.HW;
         if (vec) {
             for (int i = gl; i < d.HW / 4; i += GROUP) {
                 float4 v = reinterpret_cast<const float4 *>(p)[i];
-                v.x = bn_affine(v.x, m, is, g, b);
-                v.y = bn_affine(v.y, m, is, g, b);
-                v.z = bn_affine(v.z, m, is, g, b);
-                v.w = bn_affine(v.w, m, is, g, b);
+                v.x = ch.affine(v.x);
+                v.y = ch.affine(v.y);
+                v.z = ch.affine(v.z);
+                v.w = ch.affine(v.w);
                 if (res != nullptr) {
                     const float4 r = reinterpret_cast<const float4 *>(res + pl * d.HW)[i];
                     v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
@@ -173,12 +223,12 @@ __global__ __launch_bounds__(kThreads) void k_bn_apply(const float *__restrict__
             }
         } else {
             for (int i = gl; i < d.HW; i += GROUP) {
-                float v = bn_affine(p[i], m, is, g, b);
+                float v = ch.affine(p[i]);
                 if (res != nullptr) v += res[pl * d.HW + i];
                 q[i] = RELU ? fmaxf(v, 0.f) : v;
             }
         }
-    }
+    });
 }
 
 // grid (C, slices): partial[c][slice] = {sum g, sum g*xhat}
@@ -191,27 +241,22 @@ __global__ __launch_bounds__(kThreads) void k_bn_bwd_reduce(const float *__restr
                                                             const float *__restrict__ gamma, const float *__restrict__ beta,
                                                             double *__restrict__ partial, const float *__restrict__ out = nullptr,
                                                             float *__restrict__ gz = nullptr, const uint8_t *__restrict__ mask = nullptr) {
-    __shared__ double red[4];
-    const int c = blockIdx.x, s = blockIdx.y;
-    const int n0 = s * d.imgs_per_slice, n1 = min(d.N, n0 + d.imgs_per_slice);
-    const float m = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
-    double dsg = 0.0, dsgx = 0.0;
-    float sg = 0.f, sgx = 0.f;
+    SliceSums<2> acc(d);
+    const BnChan ch(mean, invstd, gamma, beta, acc.c);
+    const int n0 = acc.n0, n1 = acc.n1;
     const bool vec = (d.HW & 3) == 0 && (((uintptr_t)x) & 15) == 0 && (((uintptr_t)gy) & 15) == 0;
     auto visit = [&](float xv, float gv) {
-        if (RELU && !(bn_affine(xv, m, is, ga, be) > 0.f)) gv = 0.f;
-        sg += gv;
-        sgx += gv * ((xv - m) * is);
+        if (RELU && !(ch.affine(xv) > 0.f)) gv = 0.f;
+        acc.run[0] += gv;
+        acc.run[1] += gv * ch.xhat(xv);
     };
-    auto flush = [&]() {
-        dsg += (double)sg; dsgx += (double)sgx; sg = 0.f; sgx = 0.f;
-    };
+    auto flush = [&]() { acc.flush(); };
     if (MASKY) {
         const bool vec3 = vec && (((uintptr_t)out) & 15) == 0 && (((uintptr_t)gz) & 15) == 0;
         if (vec && mask != nullptr && (((uintptr_t)gz) & 15) == 0)
             // the forward left one byte per float4 of `out` (bits 0-3: element > 0): 1/16 of the bytes of re-reading `out`
             walk_planes(d.HW >> 2, n0, n1, [&](int n, int j) {
-                const int64_t q4 = ((int64_t)n * d.C + c) * (d.HW >> 2) + j, off = 4 * q4;
+                const int64_t q4 = acc.plane(n) * (d.HW >> 2) + j, off = 4 * q4;
                 const float4 xv = *reinterpret_cast<const float4 *>(x + off);
                 float4 gv = *reinterpret_cast<const float4 *>(gy + off);
                 const unsigned mb = mask[q4];
@@ -222,7 +267,7 @@ __global__ __launch_bounds__(kThreads) void k_bn_bwd_reduce(const float *__restr
             }, flush);
         else if (vec3)
             walk_planes(d.HW >> 2, n0, n1, [&](int n, int j) {
-                const int64_t off = ((int64_t)n * d.C + c) * d.HW + 4 * j;
+                const int64_t off = acc.plane(n) * d.HW + 4 * j;
                 const float4 xv = *reinterpret_cast<const float4 *>(x + off);
                 float4 gv = *reinterpret_cast<const float4 *>(gy + off);
                 const float4 ov = *reinterpret_cast<const float4 *>(out + off);
@@ -233,32 +278,36 @@ __global__ __launch_bounds__(kThreads) void k_bn_bwd_reduce(const float *__restr
             }, flush);
         else
             walk_planes(d.HW, n0, n1, [&](int n, int j) {
-                const int64_t off = ((int64_t)n * d.C + c) * d.HW + j;
+                const int64_t off = acc.plane(n) * d.HW + j;
                 const float gv = out[off] > 0.f ? gy[off] : 0.f;
                 gz[off] = gv;
                 visit(x[off], gv);
             }, flush);
     } else if (vec)
         walk_planes(d.HW >> 2, n0, n1, [&](int n, int j) {
-            const int64_t off = ((int64_t)n * d.C + c) * d.HW + 4 * j;
+            const int64_t off = acc.plane(n) * d.HW + 4 * j;
             const float4 xv = *reinterpret_cast<const float4 *>(x + off);
             const float4 gv = *reinterpret_cast<const float4 *>(gy + off);
             visit(xv.x, gv.x); visit(xv.y, gv.y); visit(xv.z, gv.z); visit(xv.w, gv.w);
         }, flush);
     else
         walk_planes(d.HW, n0, n1, [&](int n, int j) {
-            const int64_t off = ((int64_t)n * d.C + c) * d.HW + j;
+            const int64_t off = acc.plane(n) * d.HW + j;
             visit(x[off], gy[off]);
         }, flush);
-    const double t0 = block_sum(dsg, red);
-    const double t1 = block_sum(dsgx, red);
-    if (threadIdx.x == 0) {
-        partial[((int64_t)c * d.slices + s) * 2 + 0] = t0;
-        partial[((int64_t)c * d.slices + s) * 2 + 1] = t1;
-    }
+    acc.store(partial);
 }
 
-// one thread per channel: dgamma = sum g*xhat, dbeta = sum g; coefficients for the apply pass
+// what both backward finalize kernels end in, for channel c with sg = sum g and sgx = sum g * xhat over n elements:
+// dbeta, dgamma and coef[c] = {mean(g), mean(g * xhat)} for the apply pass
+__device__ __forceinline__ void bn_bwd_tail(int c, double sg, double sgx, double n, float *dgamma, float *dbeta, float *coef) {
+    dbeta[c] = (float)sg;
+    dgamma[c] = (float)sgx;
+    coef[2 * c + 0] = (float)(sg / n);
+    coef[2 * c + 1] = (float)(sgx / n);
+}
+
+// one thread per channel: fixed-order merge of the slices
 // table (may be NULL): the [C][8] per-channel record of the apply pass when it rides in the weight-gradient kernel (cpg_common.h: WgradRider)
 __global__ void k_bn_bwd_finalize(const double *__restrict__ partial, BnDims d, float *__restrict__ dgamma,
                                   float *__restrict__ dbeta, float *__restrict__ coef /* [C][2]: mean(g), mean(g*xhat) */,
@@ -273,10 +322,7 @@ __global__ void k_bn_bwd_finalize(const double *__restrict__ partial, BnDims d, 
         sgx += partial[((int64_t)c * d.slices + k) * 2 + 1];
     }
     const double n = (double)d.N * d.HW;
-    dbeta[c] = (float)sg;
-    dgamma[c] = (float)sgx;
-    coef[2 * c + 0] = (float)(sg / n);
-    coef[2 * c + 1] = (float)(sgx / n);
+    bn_bwd_tail(c, sg, sgx, n, dgamma, dbeta, coef);
     if (table != nullptr) {
         float *t = table + 8 * c;
         t[0] = mean[c], t[1] = invstd[c], t[2] = gamma[c], t[3] = beta[c];
@@ -290,18 +336,11 @@ __global__ __launch_bounds__(kThreads) void k_bn_bwd_apply(const float *__restri
                                                            float *__restrict__ gx, BnDims d, const float *__restrict__ mean,
                                                            const float *__restrict__ invstd, const float *__restrict__ gamma,
                                                            const float *__restrict__ beta, const float *__restrict__ coef) {
-    const int64_t planes = (int64_t)d.N * d.C;
     const bool vec = (d.HW & 3) == 0 && (((uintptr_t)x) & 15) == 0 && (((uintptr_t)gy) & 15) == 0 && (((uintptr_t)gx) & 15) == 0;
-    const int gl = threadIdx.x % GROUP;
-    const int64_t g0 = (int64_t)blockIdx.x * (kThreads / GROUP) + threadIdx.x / GROUP;
-    const int64_t gstride = (int64_t)gridDim.x * (kThreads / GROUP);
-    for (int64_t pl = g0; pl < planes; pl += gstride) {
-        const int c = (int)(pl % d.C);
-        const float m = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
-        const float mg = TRAIN ? coef[2 * c] : 0.f, mgx = TRAIN ? coef[2 * c + 1] : 0.f;
-        const float scale = is * ga;
+    walk_plane_groups<GROUP>(d, [&](int64_t pl, int c, int gl) {
+        const BnBwdChan<TRAIN> ch(mean, invstd, gamma, beta, coef, c);
         const int64_t off = pl * d.HW;
-        auto one = [&](float xv, float gv) { return bn_bwd_apply_one<RELU, TRAIN>(xv, gv, m, is, ga, be, mg, mgx, scale); };
+        auto one = [&](float xv, float gv) { return ch.template dx<RELU>(xv, gv); };
         if (vec) {
             for (int i = gl; i < d.HW / 4; i += GROUP) {
                 const float4 xv = reinterpret_cast<const float4 *>(x + off)[i];
@@ -312,7 +351,7 @@ __global__ __launch_bounds__(kThreads) void k_bn_bwd_apply(const float *__restri
         } else {
             for (int i = gl; i < d.HW; i += GROUP) gx[off + i] = one(x[off + i], gy[off + i]);
         }
-    }
+    });
 }
 
 int make_dims(int N, int C, int HW, BnDims &d) {
@@ -328,29 +367,34 @@ int make_dims(int N, int C, int HW, BnDims &d) {
     return CPG_OK;
 }
 
+// A run-time flag as a template argument: f(std::true_type) or f(std::false_type), so that `on()` is a constant inside f.
+template <class F>
+void with_flag(bool on, F &&f) {
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 // small feature maps: one wave per plane (4 planes per block); otherwise a block per plane
 inline bool wave_planes(const BnDims &d) { return d.HW < 4096; }
-unsigned plane_grid(const BnDims &d) {
+unsigned plane_grid(const BnDims &d, bool wave) {
     int64_t groups = (int64_t)d.N * d.C;
-    if (wave_planes(d)) groups = (groups + 3) / 4;
+    if (wave) groups = (groups + 3) / 4;
     const int64_t cap = (int64_t)kCUs * 16;
     return (unsigned)(groups < cap ? groups : cap);
 }
-template <bool RELU>
-void launch_apply(const BnDims &d, const float *x, float *y, const float *mean, const float *invstd, const float *gamma,
+void launch_apply(bool relu, const BnDims &d, const float *x, float *y, const float *mean, const float *invstd, const float *gamma,
                   const float *beta, hipStream_t stream, const float *res = nullptr, uint8_t *mask = nullptr) {
-    if (wave_planes(d))
-        hipLaunchKernelGGL((k_bn_apply<RELU, 64>), dim3(plane_grid(d)), dim3(kThreads), 0, stream, x, res, y, d, mean, invstd, gamma, beta, mask);
-    else
-        hipLaunchKernelGGL((k_bn_apply<RELU, 256>), dim3(plane_grid(d)), dim3(kThreads), 0, stream, x, res, y, d, mean, invstd, gamma, beta, mask);
+    const bool wave = wave_planes(d);
+    with_flag(relu, [&](auto r) { with_flag(wave, [&](auto w) {
+        hipLaunchKernelGGL((k_bn_apply<r(), w() ? 64 : 256>), dim3(plane_grid(d, wave)), dim3(kThreads), 0, stream, x, res, y, d, mean, invstd, gamma, beta, mask);
+    }); });
 }
-template <bool RELU, bool TRAIN>
-void launch_bwd_apply(const BnDims &d, const float *x, const float *gy, float *gx, const float *mean, const float *invstd,
-                      const float *gamma, const float *beta, const float *coef, hipStream_t stream) {
-    if (wave_planes(d))
-        hipLaunchKernelGGL((k_bn_bwd_apply<RELU, TRAIN, 64>), dim3(plane_grid(d)), dim3(kThreads), 0, stream, x, gy, gx, d, mean, invstd, gamma, beta, coef);
-    else
-        hipLaunchKernelGGL((k_bn_bwd_apply<RELU, TRAIN, 256>), dim3(plane_grid(d)), dim3(kThreads), 0, stream, x, gy, gx, d, mean, invstd, gamma, beta, coef);
+void launch_bwd_apply(bool relu, bool train, const BnDims &d, const float *x, const float *gy, float *gx, const float *mean,
+                      const float *invstd, const float *gamma, const float *beta, const float *coef, hipStream_t stream) {
+    const bool wave = wave_planes(d);
+    with_flag(relu, [&](auto r) { with_flag(train, [&](auto t) { with_flag(wave, [&](auto w) {
+        hipLaunchKernelGGL((k_bn_bwd_apply<r(), t(), w() ? 64 : 256>), dim3(plane_grid(d, wave)), dim3(kThreads), 0, stream, x, gy, gx, d, mean, invstd, gamma, beta, coef);
+    }); }); });
 }
 
 }  // namespace
@@ -361,6 +405,43 @@ extern "C" size_t cpg_bn_workspace_bytes(int32_t N, int32_t C, int32_t HW) {
     return (size_t)C * d.slices * 2 * sizeof(double) + (size_t)C * 2 * sizeof(float);
 }
 
+namespace {
+
+// The statistics pair of a training-mode forward: per-(channel, slice) sums of x, then mean / invstd out and the running statistics
+// (when given) updated in place.
+int launch_stats(const char *what, const BnDims &d, const float *x, float eps, float momentum, float *running_mean, float *running_var,
+                 float *mean, float *invstd, void *ws, size_t ws_bytes, hipStream_t stream) {
+    CPG_REQUIRE(ws != nullptr, "%s: null workspace", what);
+    CPG_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "%s: running stats must come as a pair", what);
+    if (ws_bytes < cpg_bn_workspace_bytes(d.N, d.C, d.HW)) return fail(CPG_E_WORKSPACE, "%s: workspace too small", what);
+    double *partial = (double *)ws;
+    hipLaunchKernelGGL(k_bn_stats, dim3(d.C, d.slices), dim3(kThreads), 0, stream, x, d, partial);
+    hipLaunchKernelGGL(k_bn_finalize, dim3((d.C + 63) / 64), dim3(64), 0, stream, partial, d, eps, momentum, mean, invstd, running_mean,
+                       running_var);
+    return CPG_OK;
+}
+
+// The frame of the BatchNorm backward entry points: the checks they share, `partial` / `coef` carved out of ws, then
+// reduce(partial) -> k_bn_bwd_finalize: dgamma, dbeta, coef (and the rider's [C][8] table when given) -> apply(coef).
+// own_ptrs: the entry point's further pointers (gx, gz, table ...) are all given.
+template <class R, class A>
+int bn_backward(const char *what, const BnDims &d, bool own_ptrs, const float *x, const float *g, const float *gamma, const float *beta,
+                const float *mean, const float *invstd, float *dgamma, float *dbeta, float *table, void *ws, size_t ws_bytes,
+                hipStream_t stream, R &&reduce, A &&apply) {
+    CPG_REQUIRE(own_ptrs && x && g && gamma && beta && mean && invstd && dgamma && dbeta && ws, "%s: null pointer", what);
+    if (ws_bytes < cpg_bn_workspace_bytes(d.N, d.C, d.HW)) return fail(CPG_E_WORKSPACE, "%s: workspace too small", what);
+    double *partial = (double *)ws;
+    float *coef = (float *)(partial + (size_t)d.C * d.slices * 2);
+    reduce(partial);
+    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((d.C + 63) / 64), dim3(64), 0, stream, partial, d, dgamma, dbeta, coef, table, mean, invstd,
+                       gamma, beta);
+    apply(coef);
+    CPG_CHECK_LAUNCH(what);
+    return CPG_OK;
+}
+
+}  // namespace
+
 // training forward: batch statistics (mean / invstd out, running stats updated in place when given), then y
 extern "C" int cpg_bn_relu_fwd_train(const float *x, const float *gamma, const float *beta, float eps, float momentum,
                                      float *running_mean, float *running_var, float *mean, float *invstd, float *y, int32_t N,
@@ -368,16 +449,11 @@ extern "C" int cpg_bn_relu_fwd_train(const float *x, const float *gamma, const f
     BnDims d;
     int rc = make_dims(N, C, HW, d);
     if (rc) return rc;
-    CPG_REQUIRE(x && gamma && beta && mean && invstd && y && ws, "cpg_bn_relu_fwd_train: null pointer");
-    CPG_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "cpg_bn_relu_fwd_train: running stats must come as a pair");
-    if (ws_bytes < cpg_bn_workspace_bytes(N, C, HW)) return fail(CPG_E_WORKSPACE, "cpg_bn_relu_fwd_train: workspace too small");
+    CPG_REQUIRE(x && gamma && beta && mean && invstd && y, "cpg_bn_relu_fwd_train: null pointer");
     hipStream_t stream = (hipStream_t)stream_v;
-    double *partial = (double *)ws;
-    hipLaunchKernelGGL(k_bn_stats, dim3(C, d.slices), dim3(kThreads), 0, stream, x, d, partial);
-    hipLaunchKernelGGL(k_bn_finalize, dim3((C + 63) / 64), dim3(64), 0, stream, partial, d, eps, momentum, mean, invstd,
-                       running_mean, running_var);
-    if (relu) launch_apply<true>(d, x, y, mean, invstd, gamma, beta, stream);
-    else launch_apply<false>(d, x, y, mean, invstd, gamma, beta, stream);
+    rc = launch_stats("cpg_bn_relu_fwd_train", d, x, eps, momentum, running_mean, running_var, mean, invstd, ws, ws_bytes, stream);
+    if (rc) return rc;
+    launch_apply(relu, d, x, y, mean, invstd, gamma, beta, stream);
     CPG_CHECK_LAUNCH("cpg_bn_relu_fwd_train");
     return CPG_OK;
 }
@@ -390,9 +466,7 @@ extern "C" int cpg_bn_relu_fwd_eval(const float *x, const float *gamma, const fl
     int rc = make_dims(N, C, HW, d);
     if (rc) return rc;
     CPG_REQUIRE(x && gamma && beta && mean && invstd && y, "cpg_bn_relu_fwd_eval: null pointer");
-    hipStream_t stream = (hipStream_t)stream_v;
-    if (relu) launch_apply<true>(d, x, y, mean, invstd, gamma, beta, stream);
-    else launch_apply<false>(d, x, y, mean, invstd, gamma, beta, stream);
+    launch_apply(relu, d, x, y, mean, invstd, gamma, beta, (hipStream_t)stream_v);
     CPG_CHECK_LAUNCH("cpg_bn_relu_fwd_eval");
     return CPG_OK;
 }
@@ -433,18 +507,7 @@ __global__ __launch_bounds__(kThreads) void k_bn_finalize_tiles(const float *__r
     const double s = (s0 + s1) + (s2 + s3), ss = (q0 + q1) + (q2 + q3);
     const double ts = block_sum(s, red);
     const double tss = block_sum(ss, red);
-    if (threadIdx.x == 0) {
-        const double m = ts / count;
-        double var = tss / count - m * m;
-        if (var < 0.0) var = 0.0;
-        mean[c] = (float)m;
-        invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-        if (running_mean != nullptr) {
-            const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-            running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * m);
-            running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * unbiased);
-        }
-    }
+    if (threadIdx.x == 0) bn_stats_tail(c, ts, tss, count, eps, momentum, mean, invstd, running_mean, running_var);
 }
 }  // namespace
 
@@ -492,12 +555,7 @@ __global__ __launch_bounds__(kThreads) void k_bn_bwd_finalize_tiles(const float 
     }
     const double ts = block_sum(s, red);
     const double tsx = block_sum(sx, red);
-    if (threadIdx.x == 0) {
-        dbeta[c] = (float)ts;
-        dgamma[c] = (float)tsx;
-        coef[2 * c + 0] = (float)(ts / count);
-        coef[2 * c + 1] = (float)(tsx / count);
-    }
+    if (threadIdx.x == 0) bn_bwd_tail(c, ts, tsx, count, dgamma, dbeta, coef);
 }
 }  // namespace
 
@@ -513,7 +571,7 @@ extern "C" int cpg_bn_bwd_from_partials(const float *partials, int32_t tiles, co
     hipStream_t stream = (hipStream_t)stream_v;
     float *coef = (float *)ws;
     hipLaunchKernelGGL(k_bn_bwd_finalize_tiles, dim3(C), dim3(kThreads), 0, stream, partials, tiles, (double)N * HW, dgamma, dbeta, coef);
-    launch_bwd_apply<false, true>(d, x, gm, gx, mean, invstd, gamma, beta, coef, stream);
+    launch_bwd_apply(false, true, d, x, gm, gx, mean, invstd, gamma, beta, coef, stream);
     CPG_CHECK_LAUNCH("cpg_bn_bwd_from_partials");
     return CPG_OK;
 }
@@ -545,19 +603,12 @@ extern "C" int cpg_bn_add_relu_fwd(const float *x, const float *res, const float
     if (rc) return rc;
     CPG_REQUIRE(x && res && gamma && beta && mean && invstd && y, "cpg_bn_add_relu_fwd: null pointer");
     hipStream_t stream = (hipStream_t)stream_v;
-    if (train) {
-        CPG_REQUIRE(ws != nullptr, "cpg_bn_add_relu_fwd: null workspace");
-        CPG_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "cpg_bn_add_relu_fwd: running stats must come as a pair");
-        if (ws_bytes < cpg_bn_workspace_bytes(N, C, HW)) return fail(CPG_E_WORKSPACE, "cpg_bn_add_relu_fwd: workspace too small");
-        double *partial = (double *)ws;
-        hipLaunchKernelGGL(k_bn_stats, dim3(C, d.slices), dim3(kThreads), 0, stream, x, d, partial);
-        hipLaunchKernelGGL(k_bn_finalize, dim3((C + 63) / 64), dim3(64), 0, stream, partial, d, eps, momentum, mean, invstd,
-                           running_mean, running_var);
-    }
     if (relu_mask != nullptr)
         CPG_REQUIRE(HW % 4 == 0 && ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)res)) & 15) == 0,
                     "cpg_bn_add_relu_fwd: the ReLU mask needs 4 | HW and 16-byte aligned tensors");
-    launch_apply<true>(d, x, y, mean, invstd, gamma, beta, stream, res, relu_mask);
+    if (train) rc = launch_stats("cpg_bn_add_relu_fwd", d, x, eps, momentum, running_mean, running_var, mean, invstd, ws, ws_bytes, stream);
+    if (rc) return rc;
+    launch_apply(true, d, x, y, mean, invstd, gamma, beta, stream, res, relu_mask);
     CPG_CHECK_LAUNCH("cpg_bn_add_relu_fwd");
     return CPG_OK;
 }
@@ -569,22 +620,15 @@ extern "C" int cpg_bn_relu_bwd(const float *x, const float *gy, const float *gam
     BnDims d;
     int rc = make_dims(N, C, HW, d);
     if (rc) return rc;
-    CPG_REQUIRE(x && gy && gamma && beta && mean && invstd && gx && dgamma && dbeta && ws, "cpg_bn_relu_bwd: null pointer");
-    if (ws_bytes < cpg_bn_workspace_bytes(N, C, HW)) return fail(CPG_E_WORKSPACE, "cpg_bn_relu_bwd: workspace too small");
     hipStream_t stream = (hipStream_t)stream_v;
-    double *partial = (double *)ws;
-    float *coef = (float *)(partial + (size_t)C * d.slices * 2);
-    if (relu)
-        hipLaunchKernelGGL(k_bn_bwd_reduce<true>, dim3(C, d.slices), dim3(kThreads), 0, stream, x, gy, d, mean, invstd, gamma, beta, partial);
-    else
-        hipLaunchKernelGGL(k_bn_bwd_reduce<false>, dim3(C, d.slices), dim3(kThreads), 0, stream, x, gy, d, mean, invstd, gamma, beta, partial);
-    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((C + 63) / 64), dim3(64), 0, stream, partial, d, dgamma, dbeta, coef);
-    if (relu && train) launch_bwd_apply<true, true>(d, x, gy, gx, mean, invstd, gamma, beta, coef, stream);
-    else if (relu) launch_bwd_apply<true, false>(d, x, gy, gx, mean, invstd, gamma, beta, coef, stream);
-    else if (train) launch_bwd_apply<false, true>(d, x, gy, gx, mean, invstd, gamma, beta, coef, stream);
-    else launch_bwd_apply<false, false>(d, x, gy, gx, mean, invstd, gamma, beta, coef, stream);
-    CPG_CHECK_LAUNCH("cpg_bn_relu_bwd");
-    return CPG_OK;
+    return bn_backward(
+        "cpg_bn_relu_bwd", d, gx != nullptr, x, gy, gamma, beta, mean, invstd, dgamma, dbeta, nullptr, ws, ws_bytes, stream,
+        [&](double *partial) {
+            with_flag(relu, [&](auto r) {
+                hipLaunchKernelGGL(k_bn_bwd_reduce<r()>, dim3(C, d.slices), dim3(kThreads), 0, stream, x, gy, d, mean, invstd, gamma, beta, partial);
+            });
+        },
+        [&](const float *coef) { launch_bwd_apply(relu, train, d, x, gy, gx, mean, invstd, gamma, beta, coef, stream); });
 }
 
 // The first two launches of cpg_bn_relu_bwd(relu = 1, train = 1) alone -- reduce and finalize: dgamma, dbeta -- and the [C][8] table
@@ -595,16 +639,13 @@ extern "C" int cpg_bn_relu_bwd_reduce(const float *x, const float *gy, const flo
     BnDims d;
     int rc = make_dims(N, C, HW, d);
     if (rc) return rc;
-    CPG_REQUIRE(x && gy && gamma && beta && mean && invstd && dgamma && dbeta && table && ws, "cpg_bn_relu_bwd_reduce: null pointer");
-    if (ws_bytes < cpg_bn_workspace_bytes(N, C, HW)) return fail(CPG_E_WORKSPACE, "cpg_bn_relu_bwd_reduce: workspace too small");
     hipStream_t stream = (hipStream_t)stream_v;
-    double *partial = (double *)ws;
-    float *coef = (float *)(partial + (size_t)C * d.slices * 2);
-    hipLaunchKernelGGL(k_bn_bwd_reduce<true>, dim3(C, d.slices), dim3(kThreads), 0, stream, x, gy, d, mean, invstd, gamma, beta, partial);
-    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((C + 63) / 64), dim3(64), 0, stream, partial, d, dgamma, dbeta, coef, table, mean, invstd,
-                       gamma, beta);
-    CPG_CHECK_LAUNCH("cpg_bn_relu_bwd_reduce");
-    return CPG_OK;
+    return bn_backward(
+        "cpg_bn_relu_bwd_reduce", d, table != nullptr, x, gy, gamma, beta, mean, invstd, dgamma, dbeta, table, ws, ws_bytes, stream,
+        [&](double *partial) {
+            hipLaunchKernelGGL(k_bn_bwd_reduce<true>, dim3(C, d.slices), dim3(kThreads), 0, stream, x, gy, d, mean, invstd, gamma, beta, partial);
+        },
+        [](const float *) {});
 }
 
 // backward of out = relu(bn(x) + res) (cpg_bn_add_relu_fwd; models/resnet.py:62-71,96-104): gz = gy * [out > 0] is the gradient of
@@ -618,21 +659,17 @@ extern "C" int cpg_bn_add_relu_bwd(const float *x, const float *out, const float
     BnDims d;
     int rc = make_dims(N, C, HW, d);
     if (rc) return rc;
-    CPG_REQUIRE(x && (out || relu_mask) && gy && gamma && beta && mean && invstd && gx && gz && dgamma && dbeta && ws, "cpg_bn_add_relu_bwd: null pointer");
     if (relu_mask != nullptr)
         CPG_REQUIRE(HW % 4 == 0 && ((((uintptr_t)x) | ((uintptr_t)gy) | ((uintptr_t)gz)) & 15) == 0,
                     "cpg_bn_add_relu_bwd: the ReLU mask needs 4 | HW and 16-byte aligned tensors");
-    if (ws_bytes < cpg_bn_workspace_bytes(N, C, HW)) return fail(CPG_E_WORKSPACE, "cpg_bn_add_relu_bwd: workspace too small");
     hipStream_t stream = (hipStream_t)stream_v;
-    double *partial = (double *)ws;
-    float *coef = (float *)(partial + (size_t)C * d.slices * 2);
-    hipLaunchKernelGGL((k_bn_bwd_reduce<false, true>), dim3(C, d.slices), dim3(kThreads), 0, stream, x, gy, d, mean, invstd, gamma, beta,
-                       partial, out, gz, relu_mask);
-    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((C + 63) / 64), dim3(64), 0, stream, partial, d, dgamma, dbeta, coef);
-    if (train) launch_bwd_apply<false, true>(d, x, gz, gx, mean, invstd, gamma, beta, coef, stream);
-    else launch_bwd_apply<false, false>(d, x, gz, gx, mean, invstd, gamma, beta, coef, stream);
-    CPG_CHECK_LAUNCH("cpg_bn_add_relu_bwd");
-    return CPG_OK;
+    return bn_backward(
+        "cpg_bn_add_relu_bwd", d, (out || relu_mask) && gx && gz, x, gy, gamma, beta, mean, invstd, dgamma, dbeta, nullptr, ws, ws_bytes, stream,
+        [&](double *partial) {
+            hipLaunchKernelGGL((k_bn_bwd_reduce<false, true>), dim3(C, d.slices), dim3(kThreads), 0, stream, x, gy, d, mean, invstd, gamma, beta,
+                               partial, out, gz, relu_mask);
+        },
+        [&](const float *coef) { launch_bwd_apply(false, train, d, x, gz, gx, mean, invstd, gamma, beta, coef, stream); });
 }
 
 // =====================================================================================================
@@ -669,24 +706,19 @@ template <int GROUP>
 __global__ __launch_bounds__(kThreads) void k_bnp_apply(const float *__restrict__ x, float *__restrict__ yp, BnDims d, PoolDims p,
                                                         const float *__restrict__ mean, const float *__restrict__ invstd,
                                                         const float *__restrict__ gamma, const float *__restrict__ beta) {
-    const int64_t planes = (int64_t)d.N * d.C;
-    const int gl = threadIdx.x % GROUP;
-    const int64_t g0 = (int64_t)blockIdx.x * (kThreads / GROUP) + threadIdx.x / GROUP;
-    const int64_t gstride = (int64_t)gridDim.x * (kThreads / GROUP);
-    for (int64_t pl = g0; pl < planes; pl += gstride) {
-        const int c = (int)(pl % d.C);
-        const float m = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
+    walk_plane_groups<GROUP>(d, [&](int64_t pl, int c, int gl) {
+        const BnChan ch(mean, invstd, gamma, beta, c);
         const float *plane = x + pl * d.HW;
         float *out = yp + pl * p.wins;
         for (int i = gl; i < p.wins; i += GROUP) {
             const int pr = i / p.OW, pc = i - pr * p.OW;
             const Win w = load_win(plane, p.W, pr, pc);
-            float best = 0.0f;                       // ReLU floor
+            float best = 0.0f;                       // ReLU floor: the maximum of the four relu(bn(x))
 #pragma unroll
-            for (int k = 0; k < 4; ++k) best = fmaxf(best, bn_affine(w.v[k], m, is, ga, be));
+            for (int k = 0; k < 4; ++k) best = fmaxf(best, ch.affine(w.v[k]));
             out[i] = best;
         }
-    }
+    });
 }
 
 // grid (C, slices): partial = {sum g, sum g * xhat} with g scattered from the pooled gradient
@@ -694,34 +726,23 @@ __global__ __launch_bounds__(kThreads) void k_bnp_bwd_reduce(const float *__rest
                                                              PoolDims p, const float *__restrict__ mean,
                                                              const float *__restrict__ invstd, const float *__restrict__ gamma,
                                                              const float *__restrict__ beta, double *__restrict__ partial) {
-    __shared__ double red[4];
-    const int c = blockIdx.x, s = blockIdx.y;
-    const int n0 = s * d.imgs_per_slice, n1 = min(d.N, n0 + d.imgs_per_slice);
-    const float m = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
-    double dsg = 0.0, dsgx = 0.0;
-    float sg = 0.f, sgx = 0.f;
-    walk_planes(p.wins, n0, n1, [&](int n, int wi) {
+    SliceSums<2> acc(d);
+    const BnChan ch(mean, invstd, gamma, beta, acc.c);
+    walk_planes(p.wins, acc.n0, acc.n1, [&](int n, int wi) {
         const int pr = wi / p.OW, pc = wi - pr * p.OW;
-        const int64_t pl = (int64_t)n * d.C + c;
+        const int64_t pl = acc.plane(n);
         const Win w = load_win(x + pl * d.HW, p.W, pr, pc);
         const float g = gp[pl * p.wins + wi];
         float y[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) y[k] = bn_affine(w.v[k], m, is, ga, be);
+        for (int k = 0; k < 4; ++k) y[k] = ch.affine(w.v[k]);
         const int idx = win_argmax(y);
         if (y[idx] > 0.f) {
-            sg += g;
-            sgx += g * ((w.v[idx] - m) * is);
+            acc.run[0] += g;
+            acc.run[1] += g * ch.xhat(w.v[idx]);
         }
-    }, [&]() {
-        dsg += (double)sg; dsgx += (double)sgx; sg = 0.f; sgx = 0.f;
-    });
-    const double t0 = block_sum(dsg, red);
-    const double t1 = block_sum(dsgx, red);
-    if (threadIdx.x == 0) {
-        partial[((int64_t)c * d.slices + s) * 2 + 0] = t0;
-        partial[((int64_t)c * d.slices + s) * 2 + 1] = t1;
-    }
+    }, [&]() { acc.flush(); });
+    acc.store(partial);
 }
 
 template <bool TRAIN, int GROUP>
@@ -730,15 +751,8 @@ __global__ __launch_bounds__(kThreads) void k_bnp_bwd_apply(const float *__restr
                                                             const float *__restrict__ mean, const float *__restrict__ invstd,
                                                             const float *__restrict__ gamma, const float *__restrict__ beta,
                                                             const float *__restrict__ coef) {
-    const int64_t planes = (int64_t)d.N * d.C;
-    const int gl = threadIdx.x % GROUP;
-    const int64_t g0 = (int64_t)blockIdx.x * (kThreads / GROUP) + threadIdx.x / GROUP;
-    const int64_t gstride = (int64_t)gridDim.x * (kThreads / GROUP);
-    for (int64_t pl = g0; pl < planes; pl += gstride) {
-        const int c = (int)(pl % d.C);
-        const float m = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
-        const float mg = TRAIN ? coef[2 * c] : 0.f, mgx = TRAIN ? coef[2 * c + 1] : 0.f;
-        const float scale = is * ga;
+    walk_plane_groups<GROUP>(d, [&](int64_t pl, int c, int gl) {
+        const BnBwdChan<TRAIN> ch(mean, invstd, gamma, beta, coef, c);
         const float *plane = x + pl * d.HW;
         float *gplane = gx + pl * d.HW;
         for (int i = gl; i < p.wins; i += GROUP) {
@@ -746,18 +760,15 @@ __global__ __launch_bounds__(kThreads) void k_bnp_bwd_apply(const float *__restr
             const Win w = load_win(plane, p.W, pr, pc);
             float y[4], r[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) y[k] = bn_affine(w.v[k], m, is, ga, be);
+            for (int k = 0; k < 4; ++k) y[k] = ch.affine(w.v[k]);
             const int idx = win_argmax(y);
             const float g = (y[idx] > 0.f) ? gp[pl * p.wins + i] : 0.f;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float gk = (k == idx) ? g : 0.f;
-                r[k] = TRAIN ? (gk - mg - ((w.v[k] - m) * is) * mgx) * scale : gk * scale;
-            }
+            for (int k = 0; k < 4; ++k) r[k] = ch.template dx<false>(w.v[k], (k == idx) ? g : 0.f);
             *reinterpret_cast<float2 *>(gplane + (2 * pr) * p.W + 2 * pc) = make_float2(r[0], r[1]);
             *reinterpret_cast<float2 *>(gplane + (2 * pr + 1) * p.W + 2 * pc) = make_float2(r[2], r[3]);
         }
-    }
+    });
 }
 
 int make_pool(int H, int W, PoolDims &p) {
@@ -765,12 +776,8 @@ int make_pool(int H, int W, PoolDims &p) {
     p.H = H; p.W = W; p.OW = W / 2; p.wins = (H / 2) * (W / 2);
     return CPG_OK;
 }
-unsigned pool_grid(const BnDims &d, const PoolDims &p, bool wave) {
-    int64_t groups = (int64_t)d.N * d.C;
-    if (wave) groups = (groups + 3) / 4;
-    const int64_t cap = (int64_t)kCUs * 16;
-    return (unsigned)(groups < cap ? groups : cap);
-}
+// few windows per plane: one wave per plane, as wave_planes
+inline bool wave_windows(const PoolDims &p) { return p.wins < 1024; }
 
 }  // namespace
 
@@ -787,19 +794,12 @@ extern "C" int cpg_bn_relu_pool_fwd(const float *x, const float *gamma, const fl
     CPG_REQUIRE(x && gamma && beta && mean && invstd && y_pooled, "cpg_bn_relu_pool_fwd: null pointer");
     CPG_REQUIRE((((uintptr_t)x) & 7) == 0, "cpg_bn_relu_pool_fwd: x must be 8-byte aligned");
     hipStream_t stream = (hipStream_t)stream_v;
-    if (train) {
-        CPG_REQUIRE(ws != nullptr, "cpg_bn_relu_pool_fwd: workspace required in training mode");
-        if (ws_bytes < cpg_bn_workspace_bytes(N, C, H * W)) return fail(CPG_E_WORKSPACE, "cpg_bn_relu_pool_fwd: workspace too small");
-        double *partial = (double *)ws;
-        hipLaunchKernelGGL(k_bn_stats, dim3(C, d.slices), dim3(kThreads), 0, stream, x, d, partial);
-        hipLaunchKernelGGL(k_bn_finalize, dim3((C + 63) / 64), dim3(64), 0, stream, partial, d, eps, momentum, mean, invstd,
-                           running_mean, running_var);
-    }
-    const bool wave = p.wins < 1024;
-    if (wave)
-        hipLaunchKernelGGL(k_bnp_apply<64>, dim3(pool_grid(d, p, true)), dim3(kThreads), 0, stream, x, y_pooled, d, p, mean, invstd, gamma, beta);
-    else
-        hipLaunchKernelGGL(k_bnp_apply<256>, dim3(pool_grid(d, p, false)), dim3(kThreads), 0, stream, x, y_pooled, d, p, mean, invstd, gamma, beta);
+    if (train) rc = launch_stats("cpg_bn_relu_pool_fwd", d, x, eps, momentum, running_mean, running_var, mean, invstd, ws, ws_bytes, stream);
+    if (rc) return rc;
+    const bool wave = wave_windows(p);
+    with_flag(wave, [&](auto w) {
+        hipLaunchKernelGGL(k_bnp_apply<w() ? 64 : 256>, dim3(plane_grid(d, wave)), dim3(kThreads), 0, stream, x, y_pooled, d, p, mean, invstd, gamma, beta);
+    });
     CPG_CHECK_LAUNCH("cpg_bn_relu_pool_fwd");
     return CPG_OK;
 }
@@ -813,22 +813,19 @@ extern "C" int cpg_bn_relu_pool_bwd(const float *x, const float *g_pooled, const
     if (rc) return rc;
     rc = make_pool(H, W, p);
     if (rc) return rc;
-    CPG_REQUIRE(x && g_pooled && gamma && beta && mean && invstd && gx && dgamma && dbeta && ws, "cpg_bn_relu_pool_bwd: null pointer");
     CPG_REQUIRE((((uintptr_t)x) & 7) == 0 && (((uintptr_t)gx) & 7) == 0, "cpg_bn_relu_pool_bwd: x / gx must be 8-byte aligned");
-    if (ws_bytes < cpg_bn_workspace_bytes(N, C, H * W)) return fail(CPG_E_WORKSPACE, "cpg_bn_relu_pool_bwd: workspace too small");
     hipStream_t stream = (hipStream_t)stream_v;
-    double *partial = (double *)ws;
-    float *coef = (float *)(partial + (size_t)C * d.slices * 2);
-    hipLaunchKernelGGL(k_bnp_bwd_reduce, dim3(C, d.slices), dim3(kThreads), 0, stream, x, g_pooled, d, p, mean, invstd, gamma, beta, partial);
-    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((C + 63) / 64), dim3(64), 0, stream, partial, d, dgamma, dbeta, coef);
-    const bool wave = p.wins < 1024;
-    const dim3 grid(pool_grid(d, p, wave)), block(kThreads);
-    if (wave && train) hipLaunchKernelGGL((k_bnp_bwd_apply<true, 64>), grid, block, 0, stream, x, g_pooled, gx, d, p, mean, invstd, gamma, beta, coef);
-    else if (wave) hipLaunchKernelGGL((k_bnp_bwd_apply<false, 64>), grid, block, 0, stream, x, g_pooled, gx, d, p, mean, invstd, gamma, beta, coef);
-    else if (train) hipLaunchKernelGGL((k_bnp_bwd_apply<true, 256>), grid, block, 0, stream, x, g_pooled, gx, d, p, mean, invstd, gamma, beta, coef);
-    else hipLaunchKernelGGL((k_bnp_bwd_apply<false, 256>), grid, block, 0, stream, x, g_pooled, gx, d, p, mean, invstd, gamma, beta, coef);
-    CPG_CHECK_LAUNCH("cpg_bn_relu_pool_bwd");
-    return CPG_OK;
+    return bn_backward(
+        "cpg_bn_relu_pool_bwd", d, gx != nullptr, x, g_pooled, gamma, beta, mean, invstd, dgamma, dbeta, nullptr, ws, ws_bytes, stream,
+        [&](double *partial) {
+            hipLaunchKernelGGL(k_bnp_bwd_reduce, dim3(C, d.slices), dim3(kThreads), 0, stream, x, g_pooled, d, p, mean, invstd, gamma, beta, partial);
+        },
+        [&](const float *coef) {
+            const bool wave = wave_windows(p);
+            with_flag(train, [&](auto t) { with_flag(wave, [&](auto w) {
+                hipLaunchKernelGGL((k_bnp_bwd_apply<t(), w() ? 64 : 256>), dim3(plane_grid(d, wave)), dim3(kThreads), 0, stream, x, g_pooled, gx, d, p, mean, invstd, gamma, beta, coef);
+            }); });
+        });
 }
 
 
@@ -853,8 +850,8 @@ constexpr int kPool3SR = 8;     // window (= quad) rows per work unit; a unit st
 
 // LDS layout of a unit: zs[(2 SR + 3) * W] = relu(bn(x)) of input rows 2 r0 - 1 ... 2 r0 + 2 SR + 1 (r0 = first window row of the
 // strip; rows outside the plane are never read), idx[(SR + 1) * OW] = arg-max (flat plane index) of window rows r0 ... r0 + SR
-__device__ __forceinline__ void pool3_stage(const float *__restrict__ plane, float *zs, const Pool3Dims &p, int r0, int nrows, float m,
-                                            float is, float ga, float be) {
+__device__ __forceinline__ void pool3_stage(const float *__restrict__ plane, float *zs, const Pool3Dims &p, int r0, int nrows,
+                                            const BnChan &ch) {
     const int h0 = 2 * r0 - 1;                                   // input row of LDS row 0
     const int lo = max(h0, 0), hi = min(h0 + nrows, p.H);        // valid input rows [lo, hi)
     const float *src = plane + lo * p.W;
@@ -863,12 +860,11 @@ __device__ __forceinline__ void pool3_stage(const float *__restrict__ plane, flo
     if ((n & 3) == 0 && (((uintptr_t)src) & 15) == 0 && (((lo - h0) * p.W) & 3) == 0) {
         for (int i = threadIdx.x; i < n / 4; i += kThreads) {
             float4 v = reinterpret_cast<const float4 *>(src)[i];
-            v.x = fmaxf(bn_affine(v.x, m, is, ga, be), 0.f); v.y = fmaxf(bn_affine(v.y, m, is, ga, be), 0.f);
-            v.z = fmaxf(bn_affine(v.z, m, is, ga, be), 0.f); v.w = fmaxf(bn_affine(v.w, m, is, ga, be), 0.f);
+            v.x = ch.relu(v.x); v.y = ch.relu(v.y); v.z = ch.relu(v.z); v.w = ch.relu(v.w);
             reinterpret_cast<float4 *>(dst)[i] = v;
         }
     } else {
-        for (int i = threadIdx.x; i < n; i += kThreads) dst[i] = fmaxf(bn_affine(src[i], m, is, ga, be), 0.f);
+        for (int i = threadIdx.x; i < n; i += kThreads) dst[i] = ch.relu(src[i]);
     }
 }
 
@@ -905,7 +901,7 @@ __global__ __launch_bounds__(kThreads) void k_bnp3_apply(const float *__restrict
         const int r0 = (int)(u % p.strips) * kPool3SR, r1 = min(p.OH, r0 + kPool3SR);
         const int c = (int)(pl % d.C);
         __syncthreads();
-        pool3_stage(x + pl * d.HW, zs, p, r0, 2 * (r1 - r0) + 1, mean[c], invstd[c], gamma[c], beta[c]);
+        pool3_stage(x + pl * d.HW, zs, p, r0, 2 * (r1 - r0) + 1, BnChan(mean, invstd, gamma, beta, c));
         __syncthreads();
         for (int i = threadIdx.x; i < (r1 - r0) * p.OW; i += kThreads) {
             float best;
@@ -941,10 +937,10 @@ __device__ __forceinline__ void pool3_quad(const float *zs, const int *idx, cons
 
 // stage a strip for the backward kernels: z rows and the arg-max table of window rows r0 ... min(OH, r1 + 1) - 1
 __device__ __forceinline__ void pool3_stage_bwd(const float *__restrict__ plane, float *zs, int *idx, const Pool3Dims &p, int r0, int r1,
-                                                float m, float is, float ga, float be) {
+                                                const BnChan &ch) {
     const int wr = min(p.OH, r1 + 1) - r0;                       // window rows needed (one past the strip for its last quads)
     __syncthreads();
-    pool3_stage(plane, zs, p, r0, 2 * wr + 1, m, is, ga, be);
+    pool3_stage(plane, zs, p, r0, 2 * wr + 1, ch);
     __syncthreads();
     for (int i = threadIdx.x; i < wr * p.OW; i += kThreads) idx[i] = pool3_argmax(zs, p, 2 * r0 - 1, r0 + i / p.OW, i % p.OW);
     __syncthreads();
@@ -956,21 +952,18 @@ __global__ __launch_bounds__(kThreads) void k_bnp3_bwd_reduce(const float *__res
                                                               const float *__restrict__ gamma, const float *__restrict__ beta,
                                                               double *__restrict__ partial) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];
-    __shared__ double red[4];
     float *zs = dyn;
     int *idx = reinterpret_cast<int *>(dyn + (2 * kPool3SR + 3) * p.W);
-    const int c = blockIdx.x, s = blockIdx.y;
-    const int n0 = s * d.imgs_per_slice, n1 = min(d.N, n0 + d.imgs_per_slice);
-    const float m = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
+    SliceSums<2> acc(d);
+    const BnChan ch(mean, invstd, gamma, beta, acc.c);
+    const float m = ch.m;
     const int wins = p.OH * p.OW;
-    double dsg = 0.0, dsgx = 0.0;
-    for (int n = n0; n < n1; ++n) {
-        const int64_t pl = (int64_t)n * d.C + c;
+    for (int n = acc.n0; n < acc.n1; ++n) {
+        const int64_t pl = acc.plane(n);
         const float *src = x + pl * d.HW;
-        float sg = 0.f, sgx = 0.f;
         for (int st = 0; st < p.strips; ++st) {
             const int r0 = st * kPool3SR, r1 = min(p.OH, r0 + kPool3SR);
-            pool3_stage_bwd(src, zs, idx, p, r0, r1, m, is, ga, be);
+            pool3_stage_bwd(src, zs, idx, p, r0, r1, ch);
             // x of the quad is read again unconditionally (the strip was staged a moment ago: L2 hits, coalesced 8-byte pairs) --
             // a load under "dz != 0" is four divergent round trips per quad
             const bool pairs = (p.W & 1) == 0 && (((uintptr_t)src) & 7) == 0;
@@ -988,19 +981,13 @@ __global__ __launch_bounds__(kThreads) void k_bnp3_bwd_reduce(const float *__res
                 }
                 float dz[4];
                 pool3_quad(zs, idx, gp + pl * wins, p, r0, a, b, dz);
-                sg += (dz[0] + dz[1]) + (dz[2] + dz[3]);
-                sgx += (dz[0] * ((x0.x - m) * is) + dz[1] * ((x0.y - m) * is)) + (dz[2] * ((x1.x - m) * is) + dz[3] * ((x1.y - m) * is));
+                acc.run[0] += (dz[0] + dz[1]) + (dz[2] + dz[3]);
+                acc.run[1] += (dz[0] * ch.xhat(x0.x) + dz[1] * ch.xhat(x0.y)) + (dz[2] * ch.xhat(x1.x) + dz[3] * ch.xhat(x1.y));
             }
         }
-        dsg += (double)sg;
-        dsgx += (double)sgx;
+        acc.flush();                                             // one fold per image
     }
-    const double t0 = block_sum(dsg, red);
-    const double t1 = block_sum(dsgx, red);
-    if (threadIdx.x == 0) {
-        partial[((int64_t)c * d.slices + s) * 2 + 0] = t0;
-        partial[((int64_t)c * d.slices + s) * 2 + 1] = t1;
-    }
+    acc.store(partial);
 }
 
 template <bool TRAIN>
@@ -1017,13 +1004,12 @@ __global__ __launch_bounds__(kThreads) void k_bnp3_bwd_apply(const float *__rest
         const int64_t pl = u / p.strips;
         const int r0 = (int)(u % p.strips) * kPool3SR, r1 = min(p.OH, r0 + kPool3SR);
         const int c = (int)(pl % d.C);
-        const float m = mean[c], is = invstd[c], ga = gamma[c], be = beta[c];
-        const float mg = TRAIN ? coef[2 * c] : 0.f, mgx = TRAIN ? coef[2 * c + 1] : 0.f, scale = is * ga;
+        const BnBwdChan<TRAIN> ch(mean, invstd, gamma, beta, coef, c);
         const float *src = x + pl * d.HW;
         float *dst = gx + pl * d.HW;
-        pool3_stage_bwd(src, zs, idx, p, r0, r1, m, is, ga, be);
+        pool3_stage_bwd(src, zs, idx, p, r0, r1, ch);
         const bool pairs = (p.W & 1) == 0 && (((uintptr_t)src) & 7) == 0 && (((uintptr_t)dst) & 7) == 0;   // rows as 8-byte pairs
-        auto out = [&](float xv, float g) { return TRAIN ? (g - mg - ((xv - m) * is) * mgx) * scale : g * scale; };
+        auto out = [&](float xv, float g) { return ch.template dx<false>(xv, g); };
         for (int i = threadIdx.x; i < (r1 - r0) * p.OW; i += kThreads) {
             const int a = r0 + i / p.OW, b = i % p.OW;
             float dz[4];
@@ -1086,19 +1072,19 @@ extern "C" int cpg_bn_relu_pool3_bwd(const float *x, const float *g_pooled, cons
     int rc = make_dims(N, C, H * W, d);
     if (rc) return rc;
     if (!make_pool3(H, W, p)) return fail(CPG_E_UNSUPPORTED, "cpg_bn_relu_pool3_bwd: plane %d x %d does not fit", H, W);
-    CPG_REQUIRE(x && g_pooled && gamma && beta && mean && invstd && gx && dgamma && dbeta && ws, "cpg_bn_relu_pool3_bwd: null pointer");
-    if (ws_bytes < cpg_bn_workspace_bytes(N, C, H * W)) return fail(CPG_E_WORKSPACE, "cpg_bn_relu_pool3_bwd: workspace too small");
     hipStream_t stream = (hipStream_t)stream_v;
-    double *partial = (double *)ws;
-    float *coef = (float *)(partial + (size_t)C * d.slices * 2);
     const size_t lds = pool3_lds(p);
-    hipLaunchKernelGGL(k_bnp3_bwd_reduce, dim3(C, d.slices), dim3(kThreads), lds, stream, x, g_pooled, d, p, mean, invstd, gamma, beta, partial);
-    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((C + 63) / 64), dim3(64), 0, stream, partial, d, dgamma, dbeta, coef);
-    const dim3 grid((unsigned)std::min<int64_t>((int64_t)N * C * p.strips, (int64_t)kCUs * 32));
-    if (train) hipLaunchKernelGGL(k_bnp3_bwd_apply<true>, grid, dim3(kThreads), lds, stream, x, g_pooled, gx, d, p, mean, invstd, gamma, beta, coef);
-    else hipLaunchKernelGGL(k_bnp3_bwd_apply<false>, grid, dim3(kThreads), lds, stream, x, g_pooled, gx, d, p, mean, invstd, gamma, beta, coef);
-    CPG_CHECK_LAUNCH("cpg_bn_relu_pool3_bwd");
-    return CPG_OK;
+    return bn_backward(
+        "cpg_bn_relu_pool3_bwd", d, gx != nullptr, x, g_pooled, gamma, beta, mean, invstd, dgamma, dbeta, nullptr, ws, ws_bytes, stream,
+        [&](double *partial) {
+            hipLaunchKernelGGL(k_bnp3_bwd_reduce, dim3(C, d.slices), dim3(kThreads), lds, stream, x, g_pooled, d, p, mean, invstd, gamma, beta, partial);
+        },
+        [&](const float *coef) {
+            const dim3 grid((unsigned)std::min<int64_t>((int64_t)N * C * p.strips, (int64_t)kCUs * 32));
+            with_flag(train, [&](auto t) {
+                hipLaunchKernelGGL(k_bnp3_bwd_apply<t()>, grid, dim3(kThreads), lds, stream, x, g_pooled, gx, d, p, mean, invstd, gamma, beta, coef);
+            });
+        });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1115,26 +1101,20 @@ template <bool BIAS>
 __global__ __launch_bounds__(kThreads) void k_prelu_bwd(const float *__restrict__ x, const float *__restrict__ g,
                                                         const float *__restrict__ slope, float *__restrict__ gx, BnDims d,
                                                         int slope_stride, double *__restrict__ partial) {
-    __shared__ double red[4];
-    const int c = blockIdx.x, s = blockIdx.y;
-    const int n0 = s * d.imgs_per_slice, n1 = min(d.N, n0 + d.imgs_per_slice);
-    const float a = slope[c * slope_stride];
-    double dacc = 0.0, dbias = 0.0;
-    float acc = 0.f, accb = 0.f;
+    SliceSums<BIAS ? 2 : 1> acc(d);                          // {slope gradient, bias gradient}
+    const float a = slope[acc.c * slope_stride];
+    const int n0 = acc.n0, n1 = acc.n1;
     const bool vec = (d.HW & 3) == 0 && (((uintptr_t)x) & 15) == 0 && (((uintptr_t)g) & 15) == 0 && (((uintptr_t)gx) & 15) == 0;
-    auto flush = [&]() {
-        dacc += (double)acc; acc = 0.f;
-        if (BIAS) dbias += (double)accb, accb = 0.f;
-    };
+    auto flush = [&]() { acc.flush(); };
     auto one = [&](float xv, float gv, float &out) {
         const bool pos = xv > 0.f;
         out = pos ? gv : a * gv;
-        acc += pos ? 0.f : gv * xv;
-        if (BIAS) accb += out;
+        acc.run[0] += pos ? 0.f : gv * xv;
+        if constexpr (BIAS) acc.run[1] += out;
     };
     if (vec)
         walk_planes(d.HW >> 2, n0, n1, [&](int n, int j) {
-            const int64_t off = ((int64_t)n * d.C + c) * d.HW + 4 * j;
+            const int64_t off = acc.plane(n) * d.HW + 4 * j;
             const float4 xv = *reinterpret_cast<const float4 *>(x + off);
             const float4 gv = *reinterpret_cast<const float4 *>(g + off);
             float4 o;
@@ -1143,25 +1123,21 @@ __global__ __launch_bounds__(kThreads) void k_prelu_bwd(const float *__restrict_
         }, flush);
     else
         walk_planes(d.HW, n0, n1, [&](int n, int j) {
-            const int64_t off = ((int64_t)n * d.C + c) * d.HW + j;
+            const int64_t off = acc.plane(n) * d.HW + j;
             float o;
             one(x[off], g[off], o);
             gx[off] = o;
         }, flush);
-    const double t = block_sum(dacc, red);
-    if (threadIdx.x == 0) partial[(int64_t)c * d.slices + s] = t;
-    if (BIAS) {
-        const double tb = block_sum(dbias, red);
-        if (threadIdx.x == 0) partial[(int64_t)d.C * d.slices + (int64_t)c * d.slices + s] = tb;
-    }
+    acc.store(partial);
 }
+// partial[c][slice] = {slope-gradient sum, bias-gradient sum (BIAS)}, SliceSums' layout
 __global__ void k_prelu_bwd_finalize(const double *__restrict__ partial, BnDims d, int per_channel, float *__restrict__ gslope,
                                      float *__restrict__ gbias) {
     if (gbias != nullptr) {                                   // bias gradient of the conv below: per channel, fixed-order merge
         const int c = blockIdx.x * blockDim.x + threadIdx.x;
         if (c < d.C) {
             double s = 0.0;
-            for (int k = 0; k < d.slices; ++k) s += partial[(int64_t)d.C * d.slices + (int64_t)c * d.slices + k];
+            for (int k = 0; k < d.slices; ++k) s += partial[((int64_t)c * d.slices + k) * 2 + 1];
             gbias[c] = (float)s;
         }
     }
@@ -1169,11 +1145,11 @@ __global__ void k_prelu_bwd_finalize(const double *__restrict__ partial, BnDims 
         const int c = blockIdx.x * blockDim.x + threadIdx.x;
         if (c >= d.C) return;
         double s = 0.0;
-        for (int k = 0; k < d.slices; ++k) s += partial[(int64_t)c * d.slices + k];
+        for (int k = 0; k < d.slices; ++k) s += partial[((int64_t)c * d.slices + k) * 2];
         gslope[c] = (float)s;
     } else if (blockIdx.x == 0 && threadIdx.x == 0) {        // nn.PReLU(1): one slope shared by all channels
         double s = 0.0;
-        for (int64_t k = 0; k < (int64_t)d.C * d.slices; ++k) s += partial[k];
+        for (int64_t k = 0; k < (int64_t)d.C * d.slices; ++k) s += partial[2 * k];
         gslope[0] = (float)s;
     }
 }
@@ -1182,7 +1158,7 @@ __global__ void k_prelu_bwd_finalize(const double *__restrict__ partial, BnDims 
 extern "C" size_t cpg_prelu_workspace_bytes(int32_t N, int32_t C, int32_t HW) {
     BnDims d;
     if (make_dims(N, C, HW, d) != CPG_OK) return 0;
-    return (size_t)2 * C * d.slices * sizeof(double);        // slope-gradient partials, then (cpg_prelu_bwd_bias) the bias-gradient ones
+    return (size_t)2 * C * d.slices * sizeof(double);        // per (channel, slice): the slope-gradient partial and (cpg_prelu_bwd_bias) the bias-gradient one
 }
 
 // n_slopes: C (one slope per channel) or 1 (shared).  gbias (cpg_prelu_bwd_bias; may be NULL): per-channel sum of gx
@@ -1196,10 +1172,9 @@ static int prelu_bwd(const float *x, const float *gy, const float *slope, float 
     if (ws_bytes < cpg_prelu_workspace_bytes(N, C, HW)) return fail(CPG_E_WORKSPACE, "%s: workspace too small", what);
     hipStream_t stream = (hipStream_t)stream_v;
     double *partial = (double *)ws;
-    if (gbias != nullptr)
-        hipLaunchKernelGGL(k_prelu_bwd<true>, dim3(C, d.slices), dim3(kThreads), 0, stream, x, gy, slope, gx, d, n_slopes == C ? 1 : 0, partial);
-    else
-        hipLaunchKernelGGL(k_prelu_bwd<false>, dim3(C, d.slices), dim3(kThreads), 0, stream, x, gy, slope, gx, d, n_slopes == C ? 1 : 0, partial);
+    with_flag(gbias != nullptr, [&](auto b) {
+        hipLaunchKernelGGL(k_prelu_bwd<b()>, dim3(C, d.slices), dim3(kThreads), 0, stream, x, gy, slope, gx, d, n_slopes == C ? 1 : 0, partial);
+    });
     hipLaunchKernelGGL(k_prelu_bwd_finalize, dim3((C + 63) / 64), dim3(64), 0, stream, partial, d, n_slopes == C ? 1 : 0, gslope, gbias);
     CPG_CHECK_LAUNCH(what);
     return CPG_OK;
@@ -1220,13 +1195,9 @@ namespace {
 template <int GROUP>
 __global__ __launch_bounds__(kThreads) void k_prelu_fwd(const float *__restrict__ x, const float *__restrict__ res, const float *__restrict__ slope,
                                                         float *__restrict__ y, BnDims d, int per_channel) {
-    const int64_t planes = (int64_t)d.N * d.C;
     const bool vec = (d.HW & 3) == 0 && (((uintptr_t)x) & 15) == 0 && (((uintptr_t)y) & 15) == 0 && (((uintptr_t)res) & 15) == 0;
-    const int gl = threadIdx.x % GROUP;
-    const int64_t g0 = (int64_t)blockIdx.x * (kThreads / GROUP) + threadIdx.x / GROUP;
-    const int64_t gstride = (int64_t)gridDim.x * (kThreads / GROUP);
-    for (int64_t pl = g0; pl < planes; pl += gstride) {
-        const float a = slope[per_channel ? (int)(pl % d.C) : 0];
+    walk_plane_groups<GROUP>(d, [&](int64_t pl, int c, int gl) {
+        const float a = slope[per_channel ? c : 0];
         const float *p = x + pl * d.HW;
         const float *r = res ? res + pl * d.HW : nullptr;
         float *q = y + pl * d.HW;
@@ -1247,7 +1218,7 @@ __global__ __launch_bounds__(kThreads) void k_prelu_fwd(const float *__restrict_
                 q[i] = (v > 0.f ? v : a * v) + (r ? r[i] : 0.f);
             }
         }
-    }
+    });
 }
 }  // namespace
 
@@ -1259,10 +1230,10 @@ extern "C" int cpg_prelu_fwd(const float *x, const float *res, const float *slop
     CPG_REQUIRE(x && slope && y, "cpg_prelu_fwd: null pointer");
     CPG_REQUIRE(n_slopes == C || n_slopes == 1, "cpg_prelu_fwd: n_slopes must be C or 1");
     hipStream_t stream = (hipStream_t)stream_v;
-    if (wave_planes(d))
-        hipLaunchKernelGGL(k_prelu_fwd<64>, dim3(plane_grid(d)), dim3(kThreads), 0, stream, x, res, slope, y, d, n_slopes == C ? 1 : 0);
-    else
-        hipLaunchKernelGGL(k_prelu_fwd<256>, dim3(plane_grid(d)), dim3(kThreads), 0, stream, x, res, slope, y, d, n_slopes == C ? 1 : 0);
+    const bool wave = wave_planes(d);
+    with_flag(wave, [&](auto w) {
+        hipLaunchKernelGGL(k_prelu_fwd<w() ? 64 : 256>, dim3(plane_grid(d, wave)), dim3(kThreads), 0, stream, x, res, slope, y, d, n_slopes == C ? 1 : 0);
+    });
     CPG_CHECK_LAUNCH("cpg_prelu_fwd");
     return CPG_OK;
 }

@@ -118,17 +118,22 @@ __device__ __forceinline__ float binarize(float pm, float thr) {
     return pm > thr ? 1.0f : (pm <= thr ? 0.0f : pm);
 }
 
-// y = bn(x) before the ReLU, and one element of the BatchNorm(-> ReLU) backward apply pass:
+// The BatchNorm formulas, ONE definition each: xhat, the normalised value; y = bn(x) before the ReLU; relu(bn(x)); and one element
+// of the BatchNorm(-> ReLU) backward apply pass:
 // TRAIN: dx = (g - mean(g) - xhat * mean(g xhat)) * invstd * gamma ; EVAL (fixed statistics): dx = g * invstd * gamma, with
-// g = gy * [bn(x) > 0] under RELU.  scale = invstd * gamma.  ONE definition for k_bn_bwd_apply (bn_kernels.hip) and the rider of k_wgw
-// (conv3x3_wino_wgrad.hip): the two must round alike bit for bit.
+// g = gy * [bn(x) > 0] under RELU.  scale = invstd * gamma.  Every pass of bn_kernels.hip (plain and pooled) and the rider of k_wgw
+// (conv3x3_wino_wgrad.hip) call these: they must round alike bit for bit.
+__device__ __forceinline__ float bn_xhat(float x, float mean, float invstd) { return (x - mean) * invstd; }
 __device__ __forceinline__ float bn_affine(float x, float mean, float invstd, float gamma, float beta) {
     return (x - mean) * invstd * gamma + beta;
+}
+__device__ __forceinline__ float bn_relu_affine(float x, float mean, float invstd, float gamma, float beta) {
+    return fmaxf(bn_affine(x, mean, invstd, gamma, beta), 0.f);
 }
 template <bool RELU, bool TRAIN>
 __device__ __forceinline__ float bn_bwd_apply_one(float xv, float gv, float m, float is, float ga, float be, float mg, float mgx, float scale) {
     if (RELU && !(bn_affine(xv, m, is, ga, be) > 0.f)) gv = 0.f;
-    return TRAIN ? (gv - mg - ((xv - m) * is) * mgx) * scale : gv * scale;
+    return TRAIN ? (gv - mg - bn_xhat(xv, m, is) * mgx) * scale : gv * scale;
 }
 
 constexpr int kCUs = 256;        // MI355X

@@ -166,6 +166,22 @@ def test_routed_optimizer_arithmetic_is_written_once():
         assert retired not in code, retired
 
 
+def test_batchnorm_pass_skeletons_are_written_once():
+    """bn_kernels.hip holds ONE reduction frame (SliceSums), ONE plane-group walk (walk_plane_groups), ONE statistics launch pair and ONE
+    backward host frame; the BatchNorm formulas are cpg_common.h's, so the plain, the pooled and the riding passes cannot drift apart."""
+    strip = lambda name: re.sub(r'//[^\n]*', '', open(os.path.join(ROOT, 'cpg_amd', 'csrc', name)).read())
+    code, common = strip('bn_kernels.hip'), strip('cpg_common.h')
+    for spelled_out in ('* mgx', '- m) * is'):
+        assert spelled_out not in code, spelled_out
+    assert common.count('* mgx') == 1 and len(re.findall(r'float bn_bwd_apply_one\(', common)) == 1
+    for once in ('* d.slices + s) * 2', 'blockIdx.x * (kThreads / GROUP)', 'hipLaunchKernelGGL(k_bn_stats'):
+        assert code.count(once) == 1, once
+    # the finalize launch: one site per form (with the rider's table, without) at the most
+    launches = re.findall(r'hipLaunchKernelGGL\(k_bn_bwd_finalize,[^;]*;', code)
+    with_table = [l for l in launches if 'table' in l]
+    assert launches and len(with_table) <= 1 and len(launches) - len(with_table) <= 1, launches
+
+
 def test_struct_layouts_match_header():
     import ctypes
     assert ctypes.sizeof(L.ConvDesc) == 14 * 4
