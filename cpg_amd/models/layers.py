@@ -533,8 +533,9 @@ class SharableConv2d(_Sharable):
         return getattr(self, 'math', None) or CONV_MATH
 
     def forward_with_bn_stats(self, input, bn_hint=None):
-        """(Shared with packnet_models.layers.PlainConv2d, which borrows this method and forward_bn_eval: they may read only piggymask,
-        info['threshold'], _math(), groups, stride, padding, dilation, weight and bias; tests/test_packnet_host.py checks that.)
+        """(Shared with packnet_models.layers.PlainConv2d, which borrows this method, forward_with_skip and forward_bn_eval: they may read
+        only piggymask, info['threshold'], _math(), groups, stride, padding, dilation, weight and bias, and call forward();
+        tests/test_packnet_host.py and tests/test_packnet_nets_host.py check that.)
         (y, stats): forward plus the BatchNorm partial sums of y from the same kernel; stats is None when this shape
         has no fused-statistics kernel (groups > 1 among them: neither the grouped kernels nor the per-group calls take a statistics
         epilogue, a BatchNorm-backward hint or a bias sink -- callers get stats None and run the separate statistics pass).  Used by cpg_amd.models.fused_bn.FusedSequential

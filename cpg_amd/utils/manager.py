@@ -65,8 +65,8 @@ def make_criterion(args):
 
 
 class ManagerBase(object):
-    """What the CPG and PackNet Managers share outside their train / validate loops: the fields both set, the progress line and
-    the checkpoint path."""
+    """What the CPG and PackNet Managers share outside their train / validate loops: the fields both set, the progress line, the
+    checkpoint path, the criterion with the forward + loss + accuracy of one batch, and the scoring half of evalLFW."""
 
     def __init__(self, args, model, shared_layer_info, train_loader, val_loader):
         self.args = args
@@ -78,6 +78,10 @@ class ManagerBase(object):
         self.progress = bool(getattr(args, 'progress', True)) and tqdm is not None
         self.postfix_interval = float(getattr(args, 'postfix_interval', 0.5))
         self.last_stats = {}
+        self.last_lfw = None
+        # AngleLoss / class-weighted / plain cross-entropy; stock torch unless args.fused_loss
+        self.fused_loss = bool(getattr(args, 'fused_loss', False))
+        self.criterion = make_criterion(args)
 
     def _root(self):
         return ckpt._root(self.model)
@@ -97,26 +101,6 @@ class ManagerBase(object):
     def _path(self, folder, epoch):
         return self.args.checkpoint_format.format(save_folder=folder, epoch=epoch)
 
-
-class Manager(ManagerBase):
-    """Handles training and pruning (utils/manager.py:16-37)."""
-
-    def __init__(self, args, model, shared_layer_info, masks, train_loader, val_loader, begin_prune_step, end_prune_step):
-        super().__init__(args, model, shared_layer_info, train_loader, val_loader)
-        self.pruner = SparsePruner(self.model, masks, self.args, begin_prune_step, end_prune_step,
-                                   self.inference_dataset_idx)
-        if hasattr(model, 'set_gradient_filter'):
-            # data parallel: exchange only the gradient slots that survive the routing below (it runs right after the sync)
-            model.set_gradient_filter(self.pruner)
-        if getattr(args, 'freeze_gc', False):
-            # OPT-IN (args.freeze_gc; no counterpart in the reference): the model, its masks and the pruner exist now -- one full collection,
-            # then gc.freeze(): removes the 80 ms generation-2 collector pauses from the step loop (cpg_amd.utils.settle_host_gc: process-wide)
-            from . import settle_host_gc
-            settle_host_gc()
-        self.last_lfw = None
-        self.fused_loss = bool(getattr(args, 'fused_loss', False))
-        self.criterion = make_criterion(args)
-
     def _loss_and_accuracy(self, data, target, train):
         """(loss, accuracy of the batch or None), in the reference's order of calls: train computes the accuracy before the loss (and none
         for the face task), validate the loss before the accuracy.  Fused: the accuracy comes out of the loss kernel, and in train the face
@@ -134,6 +118,44 @@ class Manager(ManagerBase):
             return self.criterion(output, target), accuracy
         loss = self.criterion(output, target)
         return loss, classification_accuracy(output, target)
+
+    def score_pairs(self, embeddings, epoch_idx=0):
+        """The scoring half of evalLFW on eval_embeddings' list of (emb_a, emb_p, issame) batches."""
+        from .metrics import fv_evaluate
+        if not embeddings or not all(isinstance(b, tuple) and len(b) == 3 for b in embeddings):
+            raise ValueError('evalLFW needs a validation loader of (a, p, issame) batches')
+        emb_a = torch.cat([b[0] for b in embeddings])
+        emb_p = torch.cat([b[1] for b in embeddings])
+        labels = torch.cat([torch.as_tensor(b[2]).reshape(-1).to(emb_a.device) for b in embeddings])
+        tpr, fpr, accuracy, val, val_std, far = fv_evaluate(emb_a, emb_p, labels, distance_metric=True, subtract_mean=False,
+                                                            threshold_dtype=getattr(self.args, 'lfw_threshold_dtype', 'float64'))
+        mean, std = np.mean(accuracy), np.std(accuracy)
+        self.last_lfw = {'tpr': tpr, 'fpr': fpr, 'accuracy': accuracy}
+        self.last_stats = dict(self.last_stats, accuracy=float(mean), accuracy_std=float(std))
+        if self.progress:
+            print('In evalLFW(): Test set: Accuracy: {:.5f}+-{:.5f}'.format(mean, std))
+        if getattr(self.args, 'log_path', None):
+            logging.info(('In evalLFW()-> Validate Epoch #{} '.format(epoch_idx + 1)
+                          + 'Test set: Accuracy: {:.5f}+-{:.5f}, '.format(mean, std)
+                          + 'task_ratio: {:.2f}'.format(self.pruner.calculate_curr_task_ratio())))
+        return mean
+
+
+class Manager(ManagerBase):
+    """Handles training and pruning (utils/manager.py:16-37)."""
+
+    def __init__(self, args, model, shared_layer_info, masks, train_loader, val_loader, begin_prune_step, end_prune_step):
+        super().__init__(args, model, shared_layer_info, train_loader, val_loader)
+        self.pruner = SparsePruner(self.model, masks, self.args, begin_prune_step, end_prune_step,
+                                   self.inference_dataset_idx)
+        if hasattr(model, 'set_gradient_filter'):
+            # data parallel: exchange only the gradient slots that survive the routing below (it runs right after the sync)
+            model.set_gradient_filter(self.pruner)
+        if getattr(args, 'freeze_gc', False):
+            # OPT-IN (args.freeze_gc; no counterpart in the reference): the model, its masks and the pruner exist now -- one full collection,
+            # then gc.freeze(): removes the 80 ms generation-2 collector pauses from the step loop (cpg_amd.utils.settle_host_gc: process-wide)
+            from . import settle_host_gc
+            settle_host_gc()
 
     def train(self, optimizers, epoch_idx, curr_lrs, curr_prune_step):
         """One epoch of the hot loop (utils/manager.py:39-100). Returns (avg_train_acc, curr_prune_step)."""
@@ -270,27 +292,6 @@ class Manager(ManagerBase):
         as numpy 1.x did (cpg_amd/utils/metrics.py); the default is numpy >= 2's fp64 comparison.  Under data parallelism with a
         replicated pair loader every rank scores every pair and returns the same value."""
         return self.score_pairs(self.eval_embeddings(epoch_idx), epoch_idx)
-
-    def score_pairs(self, embeddings, epoch_idx=0):
-        """The scoring half of evalLFW on eval_embeddings' list of (emb_a, emb_p, issame) batches."""
-        from .metrics import fv_evaluate
-        if not embeddings or not all(isinstance(b, tuple) and len(b) == 3 for b in embeddings):
-            raise ValueError('evalLFW needs a validation loader of (a, p, issame) batches')
-        emb_a = torch.cat([b[0] for b in embeddings])
-        emb_p = torch.cat([b[1] for b in embeddings])
-        labels = torch.cat([torch.as_tensor(b[2]).reshape(-1).to(emb_a.device) for b in embeddings])
-        tpr, fpr, accuracy, val, val_std, far = fv_evaluate(emb_a, emb_p, labels, distance_metric=True, subtract_mean=False,
-                                                            threshold_dtype=getattr(self.args, 'lfw_threshold_dtype', 'float64'))
-        mean, std = np.mean(accuracy), np.std(accuracy)
-        self.last_lfw = {'tpr': tpr, 'fpr': fpr, 'accuracy': accuracy}
-        self.last_stats = dict(self.last_stats, accuracy=float(mean), accuracy_std=float(std))
-        if self.progress:
-            print('In evalLFW(): Test set: Accuracy: {:.5f}+-{:.5f}'.format(mean, std))
-        if getattr(self.args, 'log_path', None):
-            logging.info(('In evalLFW()-> Validate Epoch #{} '.format(epoch_idx + 1)
-                          + 'Test set: Accuracy: {:.5f}+-{:.5f}, '.format(mean, std)
-                          + 'task_ratio: {:.2f}'.format(self.pruner.calculate_curr_task_ratio())))
-        return mean
 
     # ------------------------------------------------------------------ checkpoints (utils/manager.py:198-320)
     def save_checkpoint(self, optimizers, epoch_idx, save_folder):

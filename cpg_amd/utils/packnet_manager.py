@@ -10,27 +10,30 @@ wall-clock interval; returned values are the reference's.
 Checkpoints keep the reference's dictionary (:175-182) and its `shared_layer_info[dataset]` keys -- conv_bias, bn_layer_running_mean /
 _var / _weight / _bias, fc_bias (and prelu_layer_weight where the dictionary has it) -- so files written by either implementation load
 in the other.  BatchNorm, conv bias and fc bias are trained by every task and stashed per task there; COPIES are stored and copied
-back (utils/checkpoint.py explains why one process needs that).  `args.fused_loss` is not honoured here; PackNet's Manager.evalLFW is
-out of scope.
+back (utils/checkpoint.py explains why one process needs that).  `args.fused_loss` (opt-in, off by default) selects the loss-head
+kernels exactly as in utils.manager.Manager.  evalLFW (:109-144) scores LFW pairs through cpg_amd/utils/metrics.py on the device.
 """
 import logging
 import time
-import types
-
 import torch
 import torch.nn as nn
 
-from . import Metric, classification_accuracy
+from . import Metric
 from .checkpoint import _HEAD_ALIAS, _put, _snap, restore_norm, stash_norm
-from .manager import ManagerBase, make_criterion
+from .manager import ManagerBase
 from .packnet_prune import SparsePruner
 
 TASK_KEYS = ('conv_bias', 'bn_layer_running_mean', 'bn_layer_running_var', 'bn_layer_weight', 'bn_layer_bias', 'fc_bias')
 
 
-def new_task_info():
-    """shared_layer_info[dataset] as the reference creates it (packnet_cifar100_main_normal.py:143-151)."""
-    return {k: {} for k in TASK_KEYS}
+def new_task_info(prelu=False):
+    """shared_layer_info[dataset] as the reference creates it (packnet_cifar100_main_normal.py:143-151, packnet_imagenet_main.py:199-207);
+    prelu: with the `prelu_layer_weight` key of the face flow (packnet_face_main.py:175-184)."""
+    return {k: {} for k in TASK_KEYS + (('prelu_layer_weight',) if prelu else ())}
+
+
+def has_prelu(model):
+    return any(isinstance(m, nn.PReLU) for m in model.modules())
 
 
 def make_masks(model):
@@ -45,8 +48,6 @@ class Manager(ManagerBase):
     def __init__(self, args, model, shared_layer_info, masks, train_loader, val_loader):
         super().__init__(args, model, shared_layer_info, train_loader, val_loader)
         self.pruner = SparsePruner(self.model, masks, self.args, None, None, self.inference_dataset_idx)
-        # AngleLoss / class-weighted / plain cross-entropy (:25-32), stock torch
-        self.criterion = make_criterion(types.SimpleNamespace(dataset=args.dataset, cuda=getattr(args, 'cuda', True), fused_loss=False))
 
     def train(self, optimizers, epoch_idx, curr_lrs):
         """One epoch (utils/packnet_manager.py:35-76).  Returns the average train accuracy."""
@@ -57,11 +58,10 @@ class Manager(ManagerBase):
             for batch_idx, (data, target) in enumerate(self.train_loader):
                 data, target = self._to_device(data, target)
                 optimizers.zero_grad()
-                output = self.model(data)
                 num = data.size(0)
-                if self.args.dataset != 'face_verification':
-                    train_accuracy.update(classification_accuracy(output, target), num)
-                loss = self.criterion(output, target)
+                loss, accuracy = self._loss_and_accuracy(data, target, train=True)
+                if accuracy is not None:
+                    train_accuracy.update(accuracy, num)
                 train_loss.update(loss, num)
                 loss.backward()
                 self.pruner.do_weight_decay_and_make_grads_zero()
@@ -90,10 +90,10 @@ class Manager(ManagerBase):
             with torch.no_grad():
                 for bi, (data, target) in enumerate(self.val_loader):
                     data, target = self._to_device(data, target)
-                    output = self.model(data)
                     num = data.size(0)
-                    val_loss.update(self.criterion(output, target), num)
-                    val_accuracy.update(classification_accuracy(output, target), num)
+                    loss, accuracy = self._loss_and_accuracy(data, target, train=False)
+                    val_loss.update(loss, num)
+                    val_accuracy.update(accuracy, num)
                     self.last_stats = {'sparsity': self.pruner.calculate_sparsity(),
                                        'task{} ratio'.format(idx): self.pruner.calculate_curr_task_ratio(),
                                        'zero ratio': self.pruner.calculate_zero_ratio()}
@@ -104,9 +104,24 @@ class Manager(ManagerBase):
                     t.update(1)
         return val_accuracy.avg.item()
 
+    def eval_embeddings(self, epoch_idx=0):
+        """The device half of evalLFW (utils/packnet_manager.py:112-136): eval mode and `forward_to_embeddings` of both images of every
+        (a, p, issame) batch.  Unlike `validate` -- and unlike the CPG Manager's evalLFW -- the reference applies NO mask here: the live
+        weights are scored.  Returns [(emb_a, emb_p, issame)], embeddings on the device."""
+        self.model.eval()
+        root = self._root()
+        out = []
+        with torch.no_grad():
+            for a, p, label in self.val_loader:
+                a, p = self._to_device(a, p)
+                out.append((root.forward_to_embeddings(a), root.forward_to_embeddings(p), label))
+        return out
+
     def evalLFW(self, epoch_idx):
-        raise NotImplementedError('PackNet Manager.evalLFW (packnet_face_main.py) is out of scope (DESIGN section 7); '
-                                  'utils.manager.Manager.evalLFW scores LFW for the CPG path')
+        """utils/packnet_manager.py:109-144: fv_evaluate(distance_metric=True, subtract_mean=False) over the pair embeddings, on the
+        scoring path of utils.manager.Manager.evalLFW (cpg_amd/utils/metrics.py: distances and the 10-fold threshold search on the device;
+        args.lfw_threshold_dtype as there).  Returns np.mean(accuracy)."""
+        return self.score_pairs(self.eval_embeddings(epoch_idx), epoch_idx)
 
     def one_shot_prune(self, one_shot_prune_perc):
         self.pruner.one_shot_prune(one_shot_prune_perc)
@@ -114,7 +129,7 @@ class Manager(ManagerBase):
     # ------------------------------------------------------------------ checkpoints (utils/packnet_manager.py:151-239)
     def collect_task_layers(self):
         """Refresh shared_layer_info[dataset] from the live modules (:155-173)."""
-        info = self.shared_layer_info.setdefault(self.args.dataset, new_task_info())
+        info = self.shared_layer_info.setdefault(self.args.dataset, new_task_info(has_prelu(self._root())))
         for name, module in self._root().named_modules():
             if isinstance(module, nn.Conv2d):
                 if module.bias is not None:
@@ -127,7 +142,7 @@ class Manager(ManagerBase):
         return info
 
     def attach_task_layers(self):
-        """Give the model the task's own BatchNorm, conv bias and fc bias (:221-239)."""
+        """Give the model the task's own BatchNorm, conv bias, fc bias and PReLU slopes (:221-239)."""
         info = self.shared_layer_info[self.args.dataset]
         for name, module in self._root().named_modules():
             if isinstance(module, nn.Conv2d):

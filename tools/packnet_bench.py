@@ -8,6 +8,9 @@
 2. cpg_rank_prune_zero against cpg_rank_prune + cpg_zero_pruned over the same layers.
 3. Images per second of a whole PackNet task (claim, finetune epochs, validate, one-shot prune, retrain epochs, a validate per epoch) of
    vgg16_bn_cifar100 on synthetic data at batch 32 (the reference's) and 256.
+4. (--nets) The train step of the PackNet ResNet-50 (224x224, cross-entropy) and SphereNet-20 (112x112, AngleLoss on the face head) as
+   utils.packnet_manager.Manager.train runs it -- forward, loss, backward, the fused PackNetSGD step --, alternating with the CPG task-1
+   step of the same topology exactly as tools/net_bench.py runs it (masked layers without piggymask, cross-entropy, torch.optim.SGD).
 
 Times are device events around `--inner` repetitions of an arm, ending in a synchronise; every arm is warmed first; `--reps` windows per
 arm, alternating.  Bytes per element are computed from the shapes and the owner mask (what the passes must move), not measured.
@@ -146,18 +149,81 @@ def task_rate(batch, dev, train_batches, val_batches, epochs, prune_epochs):
     return out
 
 
+def net_step_arms(arch, batch, dev):
+    import types
+    import torch.nn.functional as F
+    import cpg_amd.models as M
+    from cpg_amd.driver import _Plain
+    from cpg_amd.utils import Optimizers
+    from cpg_amd.utils.fused_sgd import PackNetSGD
+    from cpg_amd.utils.packnet_manager import Manager, make_masks
+    face = arch == 'spherenet20'
+    shape = (batch, 3, 112, 112) if face else (batch, 3, 224, 224)
+    x = torch.randn(*shape, device=dev)
+    t = torch.randint(0, 10, (batch,), device=dev)
+
+    def packnet_arm(dataset):
+        # the body of Manager.train without its metrics
+        torch.manual_seed(1)
+        net = pm.factory(arch)(dataset_history=[], dataset2num_classes={})
+        net.add_dataset(dataset, 10)
+        net.set_dataset(dataset)
+        model = _Plain(net.to(dev)).train()
+        args = types.SimpleNamespace(dataset=dataset, mode='finetune', weight_decay=4e-5, cuda=True, progress=False, log_path=None)
+        mgr = Manager(args, model, {}, make_masks(model), None, None)
+        mgr.pruner.make_finetuning_mask()
+        opts = Optimizers()
+        opts.add(PackNetSGD(list(model.parameters()), pruner=mgr.pruner, lr=1e-3, momentum=0.9, nesterov=True, mode='fused'), 1e-3)
+
+        def packnet():
+            opts.zero_grad()
+            loss = mgr.criterion(model(x), t)
+            loss.backward()
+            mgr.pruner.do_weight_decay_and_make_grads_zero()
+            opts.step()
+            mgr.pruner.make_pruned_zero()
+        return packnet
+    arms = {'packnet_step': packnet_arm('face_verification' if face else 't')}
+    if face:        # the comparator's head and loss on the PackNet trunk: what of a difference is the A-Softmax head (stock torch ops)
+        arms['packnet_step(plain head, CE)'] = packnet_arm('t')
+    # the comparator: tools/net_bench.py's step
+    torch.manual_seed(1)
+    cpg = getattr(M, arch)(dataset_history=[], dataset2num_classes={}, network_width_multiplier=1.0, shared_layer_info={})
+    cpg.add_dataset('t', 10)
+    cpg.set_dataset('t')
+    cpg = cpg.to(dev).train()
+    sgd = torch.optim.SGD(cpg.parameters(), lr=1e-3, momentum=0.9)
+
+    def cpg_task1():
+        sgd.zero_grad(set_to_none=True)
+        F.cross_entropy(cpg(x), t).backward()
+        sgd.step()
+    arms['cpg_task1_step(net_bench)'] = cpg_task1
+    return arms
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=12)
     ap.add_argument('--inner', type=int, default=10)
     ap.add_argument('--out', default=None)
     ap.add_argument('--skip-task', action='store_true')
+    ap.add_argument('--nets', action='store_true', help='only section 4: the ResNet-50 / SphereNet-20 steps')
+    ap.add_argument('--batch', type=int, default=256)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('packnet_bench: needs the GPU (a timing anywhere else says nothing)')
     dev = 'cuda:0'
-    result = {'device': torch.cuda.get_device_name(0), 'reps': a.reps, 'inner': a.inner, 'optimizer': {}, 'prune': {}, 'task': []}
-    for arch in ('vgg16_bn_cifar100', 'vgg16_bn'):
+    result = {'device': torch.cuda.get_device_name(0), 'reps': a.reps, 'inner': a.inner, 'optimizer': {}, 'prune': {}, 'task': [], 'nets': {}}
+    for arch in ('resnet50', 'spherenet20') if a.nets else ():
+        ms = alternate(net_step_arms(arch, a.batch, dev), a.reps, a.inner)
+        for k, v in ms.items():
+            v['images_per_s'] = a.batch / (v['mean'] * 1e-3)
+            print('%-12s batch %d %-28s %8.2f ms +- %.2f (min %.2f max %.2f, %d windows)  %.0f img/s'
+                  % (arch, a.batch, k, v['mean'], v['stdev'], v['min'], v['max'], v['windows'], v['images_per_s']), flush=True)
+        result['nets'][arch] = dict(batch=a.batch, arms=ms)
+        torch.cuda.empty_cache()
+    for arch in () if a.nets else ('vgg16_bn_cifar100', 'vgg16_bn'):
         sizes = layer_sizes(arch)
         n = sum(sizes)
         arms, free, restore = optimizer_arms(sizes, dev)
@@ -185,7 +251,7 @@ def main():
         result['prune'][arch] = dict(layers=layers, weights=n, arms=ms)
         del arms, restore
         torch.cuda.empty_cache()
-    if not a.skip_task:
+    if not a.skip_task and not a.nets:
         for batch, tb in ((32, 60), (256, 30)):
             r = task_rate(batch, dev, tb, 5, 2, 1)
             print('task batch %d: %.2f s, %d train steps, %.0f images/s over the whole task' % (batch, r['seconds'], r['train_steps'], r['images_per_s']),
