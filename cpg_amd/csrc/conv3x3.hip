@@ -1462,8 +1462,7 @@ using S2G128 = C3Cfg<128, 4, 32, 2, 2, 4, 2, 1, 0, 1>;  // anything else
 using S2G64 = C3Cfg<64, 8, 32, 1, 4, 4, 2, 1, 0, 1>;    // ... with <= 64 output channels
 
 template <class Cfg>
-int launch_fwd_s2(C3Geom g, const float *x, const float *wp, const float *bias, float *y, float *stats, hipStream_t stream) {
-    const C3BnEval bn{nullptr, nullptr, nullptr, nullptr, 0.0f, 0, nullptr};
+int launch_fwd_s2(C3Geom g, const float *x, const float *wp, const float *bias, float *y, float *stats, const C3BnEval &bn, hipStream_t stream) {
     const C3BnBwd bb{nullptr, nullptr, nullptr, nullptr, nullptr};
     g.tiles_x = (g.OW + Cfg::TW - 1) / Cfg::TW;
     g.tiles_y = (g.OH + Cfg::TH - 1) / Cfg::TH;
@@ -1490,9 +1489,11 @@ C3Plan plan_fwd_s2(const cpg_conv_desc *d) {
     return c3_direct<S2G128>(TILE_S2G128, 1, N, K, OH, OW);
 }
 
+// bn (may be null; not together with stats): the eval-mode BatchNorm (+ ReLU) epilogue, with live == nullptr -- the strided tiles skip nothing
 int run_fwd_s2(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y, float *stats,
-               void *ws, size_t ws_bytes, hipStream_t stream) {
+               const C3BnEval *bnp, void *ws, size_t ws_bytes, hipStream_t stream) {
     const char *what = "cpg_conv2d_fwd(3x3 s2)";
+    const C3BnEval bn = bnp ? *bnp : C3BnEval{nullptr, nullptr, nullptr, nullptr, 0.0f, 0, nullptr};
     float *wp = (float *)ws;
     const int rows_c = pad_to(d->C, 4), Mp = pad_to(d->K, 128);
     const size_t need = pack_bytes(d->C, d->K);
@@ -1502,11 +1503,11 @@ int run_fwd_s2(const cpg_conv_desc *d, const float *x, const float *w, const flo
                        rows_c, Mp, 0, (int *)nullptr);
     C3Geom g{d->N, d->C, d->H, d->W, d->K, Mp, 0, 0, 0, s2_out(d->H), s2_out(d->W), 0, 1};
     switch (plan_fwd_s2(d).tile) {
-        case TILE_S2P28: return launch_fwd_s2<S2P28>(g, x, wp, bias, y, stats, stream);
-        case TILE_S2M8: return launch_fwd_s2<S2M8>(g, x, wp, bias, y, stats, stream);
-        case TILE_S2S16: return launch_fwd_s2<S2S16>(g, x, wp, bias, y, stats, stream);
-        case TILE_S2G64: return launch_fwd_s2<S2G64>(g, x, wp, bias, y, stats, stream);
-        case TILE_S2G128: return launch_fwd_s2<S2G128>(g, x, wp, bias, y, stats, stream);
+        case TILE_S2P28: return launch_fwd_s2<S2P28>(g, x, wp, bias, y, stats, bn, stream);
+        case TILE_S2M8: return launch_fwd_s2<S2M8>(g, x, wp, bias, y, stats, bn, stream);
+        case TILE_S2S16: return launch_fwd_s2<S2S16>(g, x, wp, bias, y, stats, bn, stream);
+        case TILE_S2G64: return launch_fwd_s2<S2G64>(g, x, wp, bias, y, stats, bn, stream);
+        case TILE_S2G128: return launch_fwd_s2<S2G128>(g, x, wp, bias, y, stats, bn, stream);
         default: return fail(CPG_E_INVALID, "%s: not a stride-2 tile", what);
     }
 }
@@ -1547,7 +1548,14 @@ int cpg_conv3x3s2_bnstats_tiles(const cpg_conv_desc *d) { return plan_fwd_s2(d).
 int cpg_conv3x3s2_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y,
                       float *stats, void *ws, size_t ws_bytes, hipStream_t stream) {
     CPG_REQUIRE(x && w && y, "cpg_conv2d_fwd: null pointer");
-    return run_fwd_s2(d, x, w, pm, thr, bias, y, stats, ws, ws_bytes, stream);
+    return run_fwd_s2(d, x, w, pm, thr, bias, y, stats, nullptr, ws, ws_bytes, stream);
+}
+int cpg_conv3x3s2_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                              const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu, float *y,
+                              void *ws, size_t ws_bytes, hipStream_t stream) {
+    CPG_REQUIRE(x && w && y && gamma && beta && mean && var, "cpg_conv2d_fwd_bn_eval: null pointer");
+    const C3BnEval bn{gamma, beta, mean, var, eps, relu, nullptr};
+    return run_fwd_s2(d, x, w, pm, thr, bias, y, nullptr, &bn, ws, ws_bytes, stream);
 }
 int cpg_conv3x3s2_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                         size_t ws_bytes, hipStream_t stream) {

@@ -44,6 +44,10 @@ int cpg_conv3x3s2_bnstats_tiles(const cpg_conv_desc *d);
 // stats (may be null): [K][tiles][2] BatchNorm partial sums
 int cpg_conv3x3s2_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y,
                       float *stats, void *ws, size_t ws_bytes, hipStream_t stream);
+// forward with the inference-mode BatchNorm (+ ReLU) folded into the epilogue (no dead-channel skip on the strided tiles)
+int cpg_conv3x3s2_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                              const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu, float *y,
+                              void *ws, size_t ws_bytes, hipStream_t stream);
 int cpg_conv3x3s2_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                         size_t ws_bytes, hipStream_t stream);
 size_t cpg_conv3x3s2_wgrad_workspace(const cpg_conv_desc *d);
@@ -129,6 +133,10 @@ cpg::PackJob cpg_conv1x1_pack_job(const cpg_conv_desc *d, int dgrad);
 int cpg_conv1x1_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                     float *y, void *ws, size_t ws_bytes, hipStream_t stream, float *stats = nullptr);
 int cpg_conv1x1_bnstats_tiles(const cpg_conv_desc *d);
+// forward with the inference-mode BatchNorm (+ residual) (+ ReLU) folded into the epilogue; residual (may be null): dense, shaped like y
+int cpg_conv1x1_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                            const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu,
+                            const float *residual, float *y, void *ws, size_t ws_bytes, hipStream_t stream);
 // addend (may be null; stride 1 only): gx = dgrad(gy) + addend
 int cpg_conv1x1_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                       size_t ws_bytes, hipStream_t stream, const float *addend = nullptr);

@@ -710,10 +710,13 @@ extern "C" int32_t cpg_conv2d_winograd(const cpg_conv_desc *d, int32_t dgrad) {
     return dgrad ? cpg_conv3x3_wino_ok(d->N, d->K, d->C, d->H, d->W) : cpg_conv3x3_wino_ok(d->N, d->C, d->K, d->H, d->W);
 }
 
-// conv -> eval-mode BatchNorm2d (-> ReLU) in one kernel; 0 from the _supported query: use cpg_conv2d_fwd + cpg_bn_relu_fwd_eval
+// conv -> eval-mode BatchNorm2d (-> ReLU) in one kernel; 0 from the _supported query: use cpg_conv2d_fwd + cpg_bn_relu_fwd_eval.
+// The classes with such an epilogue, by the route cpg_conv2d_fwd takes: 3x3 s1 p1 (with the dead-channel skip), pointwise, 3x3 s2.
 extern "C" int32_t cpg_conv2d_fwd_bn_eval_supported(const cpg_conv_desc *d) {
     ConvGeom g;
-    return make_geom(d, g) == CPG_OK && cpg_conv3x3_supported(d) ? 1 : 0;
+    if (make_geom(d, g) != CPG_OK) return 0;
+    const ConvRoute route = fwd_route(d);
+    return route == ROUTE_C3 || route == ROUTE_C1 || route == ROUTE_C3S2 ? 1 : 0;
 }
 extern "C" int cpg_conv2d_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr,
                                       const float *bias, const float *gamma, const float *beta, const float *running_mean,
@@ -722,9 +725,41 @@ extern "C" int cpg_conv2d_fwd_bn_eval(const cpg_conv_desc *d, const float *x, co
     ConvGeom g;
     int rc = make_geom(d, g);
     if (rc) return rc;
-    if (!cpg_conv3x3_supported(d)) return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_bn_eval: only the 3x3 s1 p1 kernels fuse the epilogue");
-    return cpg_conv3x3_fwd_bn_eval(d, x, w, pm, thr, bias, gamma, beta, running_mean, running_var, eps, relu, y, skip_stats, ws,
-                                   ws_bytes, (hipStream_t)stream);
+    const ConvRoute route = fwd_route(d);
+    if (route == ROUTE_C3)
+        return cpg_conv3x3_fwd_bn_eval(d, x, w, pm, thr, bias, gamma, beta, running_mean, running_var, eps, relu, y, skip_stats, ws,
+                                       ws_bytes, (hipStream_t)stream);
+    if (route != ROUTE_C1 && route != ROUTE_C3S2)
+        return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_bn_eval: only the 3x3 s1 p1, the pointwise and the 3x3 s2 kernels fuse the epilogue");
+    PackScope scope;            // (the pointwise launch takes a packed operand as cpg_conv2d_fwd does)
+    rc = route == ROUTE_C1 ? cpg_conv1x1_fwd_bn_eval(d, x, w, pm, thr, bias, gamma, beta, running_mean, running_var, eps, relu, nullptr, y, ws,
+                                                     ws_bytes, (hipStream_t)stream)
+                           : cpg_conv3x3s2_fwd_bn_eval(d, x, w, pm, thr, bias, gamma, beta, running_mean, running_var, eps, relu, y, ws, ws_bytes,
+                                                       (hipStream_t)stream);
+    if (rc == CPG_OK && skip_stats != nullptr) {        // these classes skip nothing: what CPG_NO_DEAD_SKIP reports
+        hipError_t e = hipMemsetAsync(skip_stats, 0, 2 * sizeof(int32_t), (hipStream_t)stream);
+        if (e != hipSuccess) return hip_status(e, "cpg_conv2d_fwd_bn_eval");
+    }
+    return rc;
+}
+
+// ... and the residual block's tail, conv -> eval-mode BatchNorm2d -> + residual (-> ReLU), on the pointwise kernels
+extern "C" int32_t cpg_conv2d_fwd_bn_eval_add_supported(const cpg_conv_desc *d) {
+    ConvGeom g;
+    return make_geom(d, g) == CPG_OK && fwd_route(d) == ROUTE_C1 ? 1 : 0;
+}
+extern "C" int cpg_conv2d_fwd_bn_eval_add(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr,
+                                          const float *bias, const float *gamma, const float *beta, const float *running_mean,
+                                          const float *running_var, float eps, const float *residual, int32_t relu, float *y, void *ws,
+                                          size_t ws_bytes, void *stream) {
+    PackScope scope;
+    ConvGeom g;
+    int rc = make_geom(d, g);
+    if (rc) return rc;
+    if (fwd_route(d) != ROUTE_C1) return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_bn_eval_add: only the pointwise kernels add the residual");
+    CPG_REQUIRE(residual != nullptr, "cpg_conv2d_fwd_bn_eval_add: null residual");
+    return cpg_conv1x1_fwd_bn_eval(d, x, w, pm, thr, bias, gamma, beta, running_mean, running_var, eps, relu, residual, y, ws, ws_bytes,
+                                   (hipStream_t)stream);
 }
 
 // input gradient + the BatchNorm-backward reduction of the layer below in its epilogue (3x3 s1 p1 kernels only)

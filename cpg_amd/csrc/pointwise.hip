@@ -17,6 +17,7 @@
 // 2p / 2p+1 of a k-step) hit disjoint bank halves.
 //
 //   fwd  : reads x  [N][C][H][W]  at (oh*s, ow*s), writes y [N][K][OH][OW] densely
+//          (inference: the eval-mode BatchNorm2d, the block's residual and the ReLU behind the conv in the epilogue -- BNE below)
 //   dgrad: reads gy [N][K][OH][OW] densely, writes gx [N][C][H][W] at (oh*s, ow*s)
 //          (s > 1: the other positions of gx receive no gradient and are zeroed by a memset first)
 //   wgrad: gW[k][c] = sum_g gy[k][g] * x[c][g] for dense (stride 1), 4 | pixels-per-image layers: k_pw_wgrad below;
@@ -128,12 +129,27 @@ struct PwMask {
 // MASKX (round 5; plain-GEMM form: the INPUT gradient of a masked linear layer with a piggymask, gx = gy . (W * bin(pm))): the K-major operand
 // X is the weight itself; its piggymask (mk.pm, laid out like X) is fetched beside it and the binarised product goes to LDS -- W and pm are
 // read once, nothing is materialised.
-template <class Cfg, bool DGRAD, bool STATS = false, bool ADD = false, bool MASK = false, bool MASKX = false>
+// BNE (inference, forward launches: cpg_conv2d_fwd_bn_eval / _add on the pointwise shapes): the eval-mode BatchNorm2d behind the conv, the
+// residual block's sum and its ReLU in the epilogue -- y = [max(0,] bn(conv + bias) [+ addend] [)], models/resnet.py:86-104 under
+// model.eval() -- so the raw conv output is never written and no BatchNorm pass reads it back.  The BatchNorm is a per-channel
+// (scale, shift) pair, scale = gamma / sqrtf(var + eps), shift = beta - mean * scale, that every block forms ONCE for its BM channels,
+// into the LDS the main loop has finished with: the epilogue then spends one FMA per output (bn_affine is a subtract, two multiplies and
+// an add, and every vector instruction is MFMA issue time here) and holds no per-channel registers across the fragments (four
+// parameters x 16 channels per lane do not fit beside PwV's 112 accumulators at three waves per SIMD).  With ADD the addend is loaded
+// at the output positions, per fragment, exactly as in the input-gradient launches.
+struct PwBn {
+    const float *gamma, *beta, *mean, *var;
+    float eps;
+    int relu;
+};
+template <class Cfg, bool DGRAD, bool STATS = false, bool ADD = false, bool MASK = false, bool MASKX = false, bool BNE = false>
 __global__ __launch_bounds__(256, Cfg::MINW) void k_pw(PwGeom g, const float *__restrict__ x, const float *__restrict__ wp,
                                                        const float *__restrict__ bias, float *__restrict__ y,
                                                        float *__restrict__ stats = nullptr, const float *__restrict__ addend = nullptr,
-                                                       PwMask mk = PwMask{nullptr, nullptr, nullptr, 0.0f}) {
-    static_assert(!ADD || (DGRAD && !STATS), "the addend rides in plain input-gradient launches");
+                                                       PwMask mk = PwMask{nullptr, nullptr, nullptr, 0.0f},
+                                                       PwBn bn = PwBn{nullptr, nullptr, nullptr, nullptr, 0.0f, 0}) {
+    static_assert(!ADD || ((DGRAD || BNE) && !STATS), "the addend rides in plain input-gradient launches and in the inference forward");
+    static_assert(!BNE || (!DGRAD && !STATS && !MASK && !MASKX), "the BatchNorm epilogue rides in plain forward launches");
     static_assert(!STATS || !DGRAD, "statistics ride in forward launches");
     static_assert(!MASK || (!DGRAD && !STATS && !ADD), "the piggymask epilogue rides in plain forward-form launches");
     static_assert(!MASKX || (Cfg::VEC && !DGRAD && !STATS && !ADD && !MASK), "the masked operand: float4 staging, plain forward-form launches");
@@ -302,6 +318,21 @@ __global__ __launch_bounds__(256, Cfg::MINW) void k_pw(PwGeom g, const float *__
 #pragma unroll
             for (int e = 0; e < 16; ++e) s1[fm][e] = s2[fm][e] = 0.0f;
     }
+    // the lane's place in the output fragments.  BNE: read again from the hardware (mbcnt) instead of kept from the prologue -- the main
+    // loop of the 224-pixel tile has no register to spare at three waves per SIMD, and a thread index that lives across it is spilled
+    int eli = li, elh = lh;
+    if constexpr (BNE) {
+        const int el = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const int etid = wave * 64 + el;
+        eli = el & 31, elh = el >> 5;
+        if (etid < Cfg::BM) {                        // (scale, shift) of the block's channels (the main loop's last barrier freed the LDS)
+            const int cc = m0 + etid < g.M ? m0 + etid : 0;
+            const float sc = bn.gamma[cc] * (1.0f / sqrtf(bn.var[cc] + bn.eps));
+            smem[2 * etid] = sc;
+            smem[2 * etid + 1] = bn.beta[cc] - bn.mean[cc] * sc;
+        }
+        __syncthreads();
+    }
     const bool dense_out = g.flags & kPwDenseOut;
     const long long img_base = (long long)n_first * g.M * g.out_plane;             // (elements) image n_first, channel 0
     const long long y_total = (long long)g.N * g.M * g.out_plane;
@@ -309,12 +340,12 @@ __global__ __launch_bounds__(256, Cfg::MINW) void k_pw(PwGeom g, const float *__
     auto write_out = [&](auto has_bias) {        // two copies of the loop, picked by ONE uniform branch (the ResNet convs have no bias)
 #pragma unroll
     for (int fn = 0; fn < Cfg::FN; ++fn) {
-        const unsigned pix = (unsigned)((wn * Cfg::FN + fn) * 32 + li);
+        const unsigned pix = (unsigned)((wn * Cfg::FN + fn) * 32 + eli);
         const bool pok = g0 + pix < Gu;
         unsigned n_rel, pos;
         locate(pix, dense_out, g.out_sy, g.out_sx, n_rel, pos);
         // byte offset of (image n_first + n_rel, channel 4 lh, position) from (image n_first, channel 0)
-        const int voff = pok ? (int)((((n_rel * (unsigned)g.M + 4u * (unsigned)lh) * (unsigned)g.out_plane) + pos) * 4u) : kOutOfRange;
+        const int voff = pok ? (int)((((n_rel * (unsigned)g.M + 4u * (unsigned)elh) * (unsigned)g.out_plane) + pos) * 4u) : kOutOfRange;
 #pragma unroll
         for (int fm = 0; fm < Cfg::FM; ++fm) {
             const int rowf = m0 + (wm * Cfg::FM + fm) * 32;                         // channels rowf + 8 eg + (e & 3) + 4 lh
@@ -374,15 +405,26 @@ __global__ __launch_bounds__(256, Cfg::MINW) void k_pw(PwGeom g, const float *__
                 const int row0 = rowf + 8 * eg;
                 if (row0 >= g.M) continue;                                          // (uniform; M is a multiple of 8: whole groups)
                 const __amdgpu_buffer_rsrc_t srd_y = group_srd(y, eg);
+                f32x4 ss[2];                                                        // BNE: {scale, shift} of channels row0 + 4 lh + {0, 1}, + {2, 3}
+                if constexpr (BNE) {
+                    const float *tab = smem + 2 * ((wm * Cfg::FM + fm) * 32 + 8 * eg + 4 * elh);
+                    ss[0] = *reinterpret_cast<const f32x4 *>(tab);
+                    ss[1] = *reinterpret_cast<const f32x4 *>(tab + 4);
+                }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int e = 4 * eg + r;
                     float v = acc[fm][fn][e];
-                    if (ADD) v += av[e];
+                    if (ADD && !BNE) v += av[e];
                     if (decltype(has_bias)::value) {
-                        const int co = row0 + r + 4 * lh;
+                        const int co = row0 + r + 4 * elh;
                         v += bias[co < g.M ? co : 0];
                         if (STATS && !pok) v = 0.0f;                               // (without a bias a padded position is an exact 0)
+                    }
+                    if constexpr (BNE) {
+                        v = fmaf(v, ss[r >> 1][2 * (r & 1)], ss[r >> 1][2 * (r & 1) + 1]);
+                        if (ADD) v += av[e];
+                        if (bn.relu) v = fmaxf(v, 0.0f);
                     }
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), srd_y, voff, r * plane4, 0);
                     if (STATS) {
@@ -730,7 +772,7 @@ inline size_t pack_bytes(int c_read, int m) { return ((size_t)pad_to(c_read, 16)
 
 template <class Cfg, bool DGRAD>
 int launch(PwGeom g, const float *x, const float *wp, const float *bias, float *y, hipStream_t stream, const char *what,
-           float *stats = nullptr, const float *addend = nullptr, const PwMask *mask = nullptr) {
+           float *stats = nullptr, const float *addend = nullptr, const PwMask *mask = nullptr, const PwBn *bn = nullptr) {
     g.tiles_m = (g.M + Cfg::BM - 1) / Cfg::BM;
     pw_finish_geom(g);
     if (g.G >= (1ll << 31) - 512 || (g.N > 1 && (int64_t)g.HWo + 1024 >= (1 << 24)))
@@ -738,6 +780,17 @@ int launch(PwGeom g, const float *x, const float *wp, const float *bias, float *
     const int64_t blocks = (g.G + Cfg::BN - 1) / Cfg::BN * g.tiles_m;
     if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "conv1x1: grid too large");
     if constexpr (!DGRAD) {
+        if (bn != nullptr) {                          // inference: BatchNorm (+ addend) (+ ReLU) epilogue
+            const PwMask no_mask{nullptr, nullptr, nullptr, 0.0f};
+            if (addend != nullptr)
+                hipLaunchKernelGGL((k_pw<Cfg, false, false, true, false, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y,
+                                   (float *)nullptr, addend, no_mask, *bn);
+            else
+                hipLaunchKernelGGL((k_pw<Cfg, false, false, false, false, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y,
+                                   (float *)nullptr, (const float *)nullptr, no_mask, *bn);
+            CPG_CHECK_LAUNCH(what);
+            return CPG_OK;
+        }
         if (mask != nullptr) {
             hipLaunchKernelGGL((k_pw<Cfg, false, false, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, (float *)nullptr,
                                (const float *)nullptr, *mask);
@@ -828,10 +881,9 @@ int pw_packed_operand(const cpg_conv_desc *d, int dgrad, const float *w, const f
 }
 }  // namespace
 
-int cpg_conv1x1_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                    float *y, void *ws, size_t ws_bytes, hipStream_t stream, float *stats) {
-    const char *what = "cpg_conv2d_fwd(1x1)";
-    CPG_REQUIRE(x && w && y, "%s: null pointer", what);
+namespace {
+int pw_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y, void *ws,
+           size_t ws_bytes, hipStream_t stream, float *stats, const PwBn *bn, const float *residual, const char *what) {
     const float *wp = nullptr;
     if (const int rc = pw_packed_operand(d, 0, w, pm, thr, ws, ws_bytes, stream, what, &wp)) return rc;
     const int OH = (d->H - 1) / d->stride_h + 1, OW = (d->W - 1) / d->stride_w + 1;
@@ -841,12 +893,30 @@ int cpg_conv1x1_fwd(const cpg_conv_desc *d, const float *x, const float *w, cons
     CPG_REQUIRE(stats == nullptr || pw_tile_pixels(tile) == pw_tile_pixels(pw_fwd_tile(d, true)),
                 "%s: the fused-statistics launch needs a 16-byte aligned input", what);
     switch (tile) {
-        case PW_V64: return launch<PwV64, false>(g, x, wp, bias, y, stream, what, stats);
-        case PW_S64: return launch<PwS64, false>(g, x, wp, bias, y, stream, what, stats);
-        case PW_V2: return launch<PwV2, false>(g, x, wp, bias, y, stream, what, stats);
-        case PW_V: return launch<PwV, false>(g, x, wp, bias, y, stream, what, stats);
-        default: return launch<PwS, false>(g, x, wp, bias, y, stream, what, stats);
+        case PW_V64: return launch<PwV64, false>(g, x, wp, bias, y, stream, what, stats, residual, nullptr, bn);
+        case PW_S64: return launch<PwS64, false>(g, x, wp, bias, y, stream, what, stats, residual, nullptr, bn);
+        case PW_V2: return launch<PwV2, false>(g, x, wp, bias, y, stream, what, stats, residual, nullptr, bn);
+        case PW_V: return launch<PwV, false>(g, x, wp, bias, y, stream, what, stats, residual, nullptr, bn);
+        default: return launch<PwS, false>(g, x, wp, bias, y, stream, what, stats, residual, nullptr, bn);
     }
+}
+}  // namespace
+
+int cpg_conv1x1_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                    float *y, void *ws, size_t ws_bytes, hipStream_t stream, float *stats) {
+    const char *what = "cpg_conv2d_fwd(1x1)";
+    CPG_REQUIRE(x && w && y, "%s: null pointer", what);
+    return pw_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, stream, stats, nullptr, nullptr, what);
+}
+
+// inference: y = [max(0,] bn(conv + bias) [+ residual] [)] in one launch (k_pw's BNE instances); residual: dense, shaped like y, or null
+int cpg_conv1x1_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                            const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu,
+                            const float *residual, float *y, void *ws, size_t ws_bytes, hipStream_t stream) {
+    const char *what = residual ? "cpg_conv2d_fwd_bn_eval_add(1x1)" : "cpg_conv2d_fwd_bn_eval(1x1)";
+    CPG_REQUIRE(x && w && y && gamma && beta && mean && var, "%s: null pointer", what);
+    const PwBn bn{gamma, beta, mean, var, eps, relu};
+    return pw_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, stream, nullptr, &bn, residual, what);
 }
 
 int cpg_conv1x1_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,

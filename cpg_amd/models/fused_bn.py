@@ -29,6 +29,9 @@ RELU_BYTE_MASK = True   # relu(bn(x) + res): the forward leaves the ReLU mask as
 FUSE_STEM = True        # conv(<= 3 -> 64 channels, 3x3 s1 p1) -> BatchNorm2d -> ReLU: the conv output is never written (cpg_stem_bn_*)
 FUSE_STEM_WGRAD = True  # ... and its weight gradient inside the BatchNorm backward's apply pass (cpg_stem_bn_relu_bwd_wgrad)
 FUSE_SKIP_ADD = True    # residual blocks: the identity branch's gradient is added in conv1's input-gradient epilogue
+# Inference on the residual topologies: conv -> BatchNorm2d(eval) [-> + residual] [-> ReLU] as ONE kernel wherever the conv has such an
+# epilogue (cpg_conv2d_fwd_bn_eval / _add: pointwise, 3x3 s1, 3x3 s2).  Off: conv, then the BatchNorm pass, launch for launch as before.
+FUSE_EVAL_BLOCKS = True
 
 
 def _batch_stats(stats, nbt, N, C, HW, eps, momentum, running_mean, running_var, training, device):
@@ -409,8 +412,22 @@ def _conv_with_stats(conv, bn, x):
     return conv(x), None
 
 
+def _eval_blocks(conv, bn, x, method='forward_bn_eval'):
+    """Inference may run `conv` and `bn` as one kernel: FUSE_EVAL_BLOCKS, under torch.no_grad(), a conv that offers `method`, an
+    eval-mode, affine, stat-tracking BatchNorm2d, fp32 on the device (the conv's own method still answers None for shapes without such
+    a kernel and for another arithmetic)."""
+    return (ENABLED and FUSE_EVAL_BLOCKS and not torch.is_grad_enabled() and hasattr(conv, method) and isinstance(bn, nn.BatchNorm2d)
+            and not bn.training and bn.track_running_stats and bn.affine and x.is_cuda and x.dtype == torch.float32
+            and bn.weight.dtype == torch.float32)
+
+
 def conv_bn_act(conv, bn, act, x):
-    """act(bn(conv(x))) for the residual topologies (models/resnet.py:86-93): bn_act with the statistics pass folded into the conv."""
+    """act(bn(conv(x))) for the residual topologies (models/resnet.py:86-93): bn_act with the statistics pass folded into the conv; at
+    inference the whole triple is the conv's kernel (_eval_blocks)."""
+    if (act is None or type(act) is nn.ReLU) and _eval_blocks(conv, bn, x):
+        y = conv.forward_bn_eval(x, bn, relu=act is not None)
+        if y is not None:
+            return y
     y, stats = _conv_with_stats(conv, bn, x)
     if stats is not None and (act is None or type(act) is nn.ReLU) and fusable(bn, y):
         return bn_relu(y, bn, relu=act is not None, stats=stats)
@@ -510,7 +527,12 @@ def conv_bn_act_skip(conv, bn, act, x):
 
 
 def conv_bn_add_act(conv, bn, act, x, res):
-    """act(bn(conv(x)) + res): the block tail (models/resnet.py:94-104) with the statistics from the conv's epilogue."""
+    """act(bn(conv(x)) + res): the block tail (models/resnet.py:94-104) with the statistics from the conv's epilogue; at inference
+    the whole tail is the conv's kernel (_eval_blocks: the pointwise conv3 of a Bottleneck)."""
+    if type(act) is nn.ReLU and _eval_blocks(conv, bn, x, 'forward_bn_eval_add'):
+        y = conv.forward_bn_eval_add(x, bn, res, relu=True)
+        if y is not None:
+            return y
     y, stats = _conv_with_stats(conv, bn, x)
     return bn_add_act(bn, act, y, res, stats)
 
@@ -535,7 +557,7 @@ class FusedSequential(nn.Sequential):
         mods = list(self._modules.values())
         n = len(mods)
         mods += [None] * 3
-        steps = (self._bn_relu, self._lone_bn, self._conv_bn_relu_eval, self._stem, self._conv)
+        steps = (self._bn_relu, self._lone_bn, self._conv_bn_relu_eval, self._conv_bn_eval, self._stem, self._conv)
         i, stats, hint = 0, None, None
         while i < n:
             window = mods[i:i + 4]
@@ -583,6 +605,15 @@ class FusedSequential(nn.Sequential):
         if st is not None:
             self.skip_log.append(st)
         return 3, y, None, hint
+
+    def _conv_bn_eval(self, mods, input, stats, hint):
+        """Inference: conv -> BatchNorm2d(eval) with NO ReLU behind it (the ResNet shortcut, conv1x1 -> BN) as one kernel.  A pair with
+        a ReLU behind it is _conv_bn_relu_eval's, whether or not that step took it."""
+        m, bn, nxt2, _ = mods
+        if not (self.fuse and self.fuse_eval and not isinstance(nxt2, nn.ReLU) and _eval_blocks(m, bn, input)):
+            return None
+        y = m.forward_bn_eval(input, bn, relu=False)
+        return None if y is None else (2, y, None, None)
 
     def _stem(self, mods, input, stats, hint):
         """The stem: conv -> BatchNorm2d -> ReLU without ever writing the conv output (a following MaxPool2d keeps the pair, as above)."""

@@ -533,7 +533,7 @@ class SharableConv2d(_Sharable):
         return getattr(self, 'math', None) or CONV_MATH
 
     def forward_with_bn_stats(self, input, bn_hint=None):
-        """(Shared with packnet_models.layers.PlainConv2d, which borrows this method, forward_with_skip and forward_bn_eval: they may read
+        """(Shared with packnet_models.layers.PlainConv2d, which borrows this method, forward_with_skip, forward_bn_eval and forward_bn_eval_add: they may read
         only piggymask, info['threshold'], _math(), groups, stride, padding, dilation, weight and bias, and call forward();
         tests/test_packnet_host.py and tests/test_packnet_nets_host.py check that.)
         (y, stats): forward plus the BatchNorm partial sums of y from the same kernel; stats is None when this shape
@@ -578,6 +578,32 @@ class SharableConv2d(_Sharable):
                   _lib.dptr(bn.weight, name='bn.weight'), _lib.dptr(bn.bias, name='bn.bias'), _lib.dptr(bn.running_mean, name='running_mean'),
                   _lib.dptr(bn.running_var, name='running_var'), float(bn.eps), int(bool(relu)), _lib.dptr(y),
                   None if skip_stats is None else ctypes.c_void_p(skip_stats.data_ptr()), _lib.dptr(ws), nbytes, _lib.stream_ptr())
+        return y
+
+    def forward_bn_eval_add(self, input, bn, res, relu=True):
+        """relu(bn(conv(input)) + res), the tail of a residual block (models/resnet.py:94-104), with `bn` an eval-mode nn.BatchNorm2d, as
+        ONE kernel (cpg_conv2d_fwd_bn_eval_add: the pointwise shapes).  Inference only, like forward_bn_eval; returns None when this
+        shape has no such kernel or `res` is not a dense fp32 device tensor shaped like the output."""
+        if (torch.is_grad_enabled() or input.dim() != 4 or input.shape[0] == 0 or input.shape[1] != self.weight.shape[1] * self.groups
+                or self._math() != 'fp32' or self.groups != 1):
+            return None
+        x = input.contiguous()
+        w = self.weight.contiguous()
+        p = None if self.piggymask is None else self.piggymask.contiguous()
+        d = _conv_desc(x.shape, w.shape, self.stride, self.padding, self.dilation, self.groups)
+        L = _lib.lib()
+        if not L.cpg_conv2d_fwd_bn_eval_add_supported(ctypes.byref(d)):
+            return None
+        oh, ow = _out_hw(d)
+        if tuple(res.shape) != (d.N, d.K, oh, ow) or res.dtype != torch.float32 or not res.is_cuda:
+            return None
+        y = torch.empty((d.N, d.K, oh, ow), dtype=torch.float32, device=x.device)
+        ws, nbytes = _lib.workspace(L.cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
+        _lib.call('cpg_conv2d_fwd_bn_eval_add', ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'),
+                  _lib.dptr(p, name='piggymask'), float(self.info['threshold']), _lib.dptr(self.bias, name='bias'),
+                  _lib.dptr(bn.weight, name='bn.weight'), _lib.dptr(bn.bias, name='bn.bias'), _lib.dptr(bn.running_mean, name='running_mean'),
+                  _lib.dptr(bn.running_var, name='running_var'), float(bn.eps), _lib.dptr(res.contiguous(), name='residual'),
+                  int(bool(relu)), _lib.dptr(y), _lib.dptr(ws), nbytes, _lib.stream_ptr())
         return y
 
     def extra_repr(self):

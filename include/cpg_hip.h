@@ -413,6 +413,23 @@ int cpg_conv2d_fwd_bn_eval(const cpg_conv_desc *desc, const float *x, const floa
                            const float *bias, const float *gamma, const float *beta, const float *running_mean,
                            const float *running_var, float eps, int32_t relu, float *y, int32_t *skip_stats, void *workspace,
                            size_t workspace_bytes, void *stream);
+/* The residual topologies' inference (models/resnet.py:83-95 under model.eval(): `conv1 -> bn1 -> relu`, `conv2 -> bn2 -> relu`,
+ * `conv3 -> bn3`, and the shortcut `downsample = nn.Sequential(conv1x1, norm_layer)` of models/resnet.py:179-182): the two entry points
+ * above also take every pointwise shape (1x1, any stride, pad 0, C and K multiples of 16) and every 3x3 / stride 2 / pad 1 shape that
+ * cpg_conv2d_fwd runs on its specialised kernels, with the same contract -- y = [max(0,] (conv + bias - running_mean) /
+ * sqrtf(running_var + eps) * gamma + beta [)], invstd formed in the kernel.  These shapes have NO dead-channel skip: a non-NULL
+ * skip_stats receives {0, 0}, and cpg_conv2d_winograd(desc, 3) is 0 for them.  CPG_DISABLE_CONV1X1 / CPG_DISABLE_CONV3X3 / CPG_NO_S2
+ * take the class away from cpg_conv2d_fwd and from this query alike.
+ * cpg_conv2d_fwd_bn_eval_add is the block's tail (models/resnet.py:91-98: `out = self.bn3(self.conv3(out)); out += identity;
+ * out = self.relu(out)`) as one kernel: y = [max(0,] bn(conv + bias) + residual [)], residual dense NCHW and shaped like y (it may not
+ * be NULL: CPG_E_INVALID).  Pointwise shapes only: every other descriptor, 3x3 included, answers 0 / CPG_E_UNSUPPORTED and y is not
+ * touched.  workspace: cpg_conv2d_workspace_bytes(desc); a packed operand armed with cpg_conv2d_use_packed is consumed as by
+ * cpg_conv2d_fwd (and by cpg_conv2d_fwd_bn_eval on the pointwise shapes). */
+int32_t cpg_conv2d_fwd_bn_eval_add_supported(const cpg_conv_desc *desc);
+int cpg_conv2d_fwd_bn_eval_add(const cpg_conv_desc *desc, const float *x, const float *w, const float *piggymask, float threshold,
+                               const float *bias, const float *gamma, const float *beta, const float *running_mean,
+                               const float *running_var, float eps, const float *residual, int32_t relu, float *y, void *workspace,
+                               size_t workspace_bytes, void *stream);
 
 /* ---- OPT-IN bf16 MFMA path (north_star: "MFMA fp32/bf16 GEMM") of the 3x3 / stride 1 / pad 1 convolution ----
  * Same contraction as cpg_conv2d_fwd / cpg_conv2d_dgrad with the operands (activations, effective weights W * bin(pm))

@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Inference forward of a residual topology with fused_bn.FUSE_EVAL_BLOCKS on against off (profiles/resnet_eval_fuse.md).
+
+Full-width ResNet-50 (or --arch), model.eval() under torch.no_grad() at 224 x 224 -- Manager.validate's forward.  Both arms run in ONE
+process, alternating window by window after both are warmed, so clock and allocator state are shared; a window is --forwards forwards
+between two device events.  Per batch size one line, mean +- sample sd (min - max) of the windows per arm, and at the end one JSON
+line with everything, plus the activation bytes per image each arm moves, computed from the layer shapes alone:
+  off  every conv reads its input and writes its raw output; the BatchNorm pass behind it reads that back (+ the residual, in a block
+       tail) and writes the activation;
+  on   every conv behind the stem reads its input (+ the residual) and writes the activation."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import cpg_amd.models as M  # noqa: E402
+from cpg_amd.models import fused_bn  # noqa: E402
+from cpg_amd.models import layers as nl  # noqa: E402
+
+
+def byte_account(net, size):
+    """Activation bytes read + written per image by the convs and the BatchNorm passes behind them, {'off': .., 'on': ..}, from the
+    conv modules' input / output shapes (one image through the net on the device; weights and parameters not counted)."""
+    shapes = []
+    hooks = [m.register_forward_hook(lambda mod, inp, out, name=name: shapes.append((name, inp[0].numel(), out.numel())))
+             for name, m in net.named_modules() if isinstance(m, nl.SharableConv2d)]
+    was = fused_bn.FUSE_EVAL_BLOCKS
+    fused_bn.FUSE_EVAL_BLOCKS = False           # (the hooks see the conv modules' own forward)
+    try:
+        with torch.no_grad():
+            net(torch.zeros(1, 3, size, size, device=next(net.parameters()).device))
+    finally:
+        fused_bn.FUSE_EVAL_BLOCKS = was
+        for h in hooks:
+            h.remove()
+    off = on = 0
+    for name, n_in, n_out in shapes:
+        tail = name.endswith('conv3')
+        if name == 'conv1':                     # the stem: conv, then BatchNorm -> ReLU -> MaxPool2d(3, 2, 1) as one pass, in both arms
+            both = n_in + n_out + n_out + n_out // 4
+            off, on = off + both, on + both
+            continue
+        off += (n_in + n_out) + (n_out + (n_out if tail else 0) + n_out)
+        on += n_in + (n_out if tail else 0) + n_out
+    return {'off': 4 * off, 'on': 4 * on}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--arch', default='resnet50')
+    ap.add_argument('--batches', type=int, nargs='+', default=[100, 256])
+    ap.add_argument('--size', type=int, default=224)
+    ap.add_argument('--forwards', type=int, default=10, help='forwards per timed window')
+    ap.add_argument('--windows', type=int, default=12, help='windows per arm')
+    ap.add_argument('--warmup', type=int, default=5, help='forwards per arm before the first window')
+    a = ap.parse_args()
+    dev = 'cuda:0'
+    torch.manual_seed(1)
+    net = getattr(M, a.arch)(dataset_history=[], dataset2num_classes={}, network_width_multiplier=1.0, shared_layer_info={})
+    net.add_dataset('t', 10)
+    net.set_dataset('t')
+    net = net.to(dev).eval()
+    out = {'arch': a.arch, 'size': a.size, 'forwards_per_window': a.forwards, 'windows_per_arm': a.windows, 'batches': {},
+           'activation_bytes_per_image': byte_account(net, a.size)}
+
+    def forward(x, switch):
+        fused_bn.FUSE_EVAL_BLOCKS = switch
+        with torch.no_grad():
+            return net(x)
+    default = fused_bn.FUSE_EVAL_BLOCKS
+    try:
+        for batch in a.batches:
+            x = torch.randn(batch, 3, a.size, a.size, device=dev)
+            for switch in (True, False):
+                for _ in range(a.warmup):
+                    forward(x, switch)
+            torch.cuda.synchronize()
+            ms = {True: [], False: []}
+            for _ in range(a.windows):
+                for switch in (True, False):
+                    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    t0.record()
+                    for _ in range(a.forwards):
+                        forward(x, switch)
+                    t1.record()
+                    t1.synchronize()
+                    ms[switch].append(t0.elapsed_time(t1) / a.forwards)
+            row = {}
+            for switch, label in ((True, 'on'), (False, 'off')):
+                v = ms[switch]
+                row[label] = {'mean_ms': round(statistics.mean(v), 4), 'sd_ms': round(statistics.stdev(v), 4), 'min_ms': round(min(v), 4),
+                              'max_ms': round(max(v), 4)}
+                print('%s batch %d FUSE_EVAL_BLOCKS %-3s: %.3f +- %.3f ms per forward (%.3f - %.3f), %.0f img/s' % (
+                    a.arch, batch, label, row[label]['mean_ms'], row[label]['sd_ms'], row[label]['min_ms'], row[label]['max_ms'],
+                    batch / row[label]['mean_ms'] * 1e3))
+            gain = row['off']['mean_ms'] - row['on']['mean_ms']
+            row['gain_ms'] = round(gain, 4)
+            row['gain_over_2sd'] = bool(gain > 2 * max(row['on']['sd_ms'], row['off']['sd_ms']))
+            out['batches'][str(batch)] = row
+    finally:
+        fused_bn.FUSE_EVAL_BLOCKS = default
+    print(json.dumps(out, sort_keys=True))
+
+
+if __name__ == '__main__':
+    main()
