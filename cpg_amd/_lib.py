@@ -82,6 +82,8 @@ _SIGNATURES = {
     'cpg_bn_relu_bwd_reduce': (_int, [_vp] * 9 + [_i32] * 3 + [_vp, _sz, _vp]),
     'cpg_conv2d_wgrad_rider_supported': (_i32, [_desc]),
     'cpg_conv2d_wgrad_attach_bn_bwd': (_int, [_vp] * 4 + [_i32] * 3),
+    'cpg_conv2d_fwd_pool_max_supported': (_i32, [_desc]),
+    'cpg_conv2d_fwd_attach_pool_max': (_int, [_vp, _sz]),
     'cpg_linear_workspace_bytes': (_sz, [_i32, _i32, _i32]),
     'cpg_linear_fwd': (_int, [_vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     'cpg_linear_dgrad': (_int, [_vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
@@ -110,6 +112,9 @@ _SIGNATURES = {
     'cpg_bn_relu_fwd_eval': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     'cpg_bn_relu_pool_fwd': (_int, [_vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     'cpg_bn_relu_pool_bwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    'cpg_bn_relu_pool_attach_max': (_int, [_vp, _sz]),
+    'cpg_bn_relu_pool_fwd_from_max': (_int, [_vp, _vp, _vp, _i32, _vp, _vp, _f32, _f32] + [_vp] * 6 + [_i32] * 4 + [_vp]),
+    'cpg_bn_relu_pool_bwd_from_max': (_int, [_vp] * 10 + [_i32] * 5 + [_vp, _sz, _vp]),
     'cpg_bn_relu_bwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     'cpg_conv2d_winograd': (_i32, [_desc, _i32]),
     'cpg_conv2d_bnstats_tiles': (_i32, [_desc]),

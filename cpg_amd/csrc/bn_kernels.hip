@@ -702,14 +702,32 @@ __device__ __forceinline__ int win_argmax(const float (&y)[4]) {
     return idx;
 }
 
-template <int GROUP>
+// FROM_MAX: E[N][C][H/2][W/2] holds every window's maximum of x (written by the conv that produced x, cpg_conv2d_fwd_attach_pool_max).
+// bn_affine is a chain of correctly rounded operations, each monotone in x, so for a plane with gamma > 0
+// max_k relu(affine(x_k)) == relu(affine(max_k x_k)) as numbers: such a plane reads E (1/4 of the bytes), any other plane reads x as before.
+template <int GROUP, bool FROM_MAX = false>
 __global__ __launch_bounds__(kThreads) void k_bnp_apply(const float *__restrict__ x, float *__restrict__ yp, BnDims d, PoolDims p,
                                                         const float *__restrict__ mean, const float *__restrict__ invstd,
-                                                        const float *__restrict__ gamma, const float *__restrict__ beta) {
+                                                        const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                        const float *__restrict__ E = nullptr) {
+    const bool vec = FROM_MAX && (p.wins & 3) == 0 && (((uintptr_t)E) & 15) == 0 && (((uintptr_t)yp) & 15) == 0;
     walk_plane_groups<GROUP>(d, [&](int64_t pl, int c, int gl) {
         const BnChan ch(mean, invstd, gamma, beta, c);
         const float *plane = x + pl * d.HW;
         float *out = yp + pl * p.wins;
+        if (FROM_MAX && ch.ga > 0.f) {                   // (uniform for the group: it owns the plane)
+            const float *em = E + pl * p.wins;
+            if (vec) {
+                for (int i = gl; i < p.wins / 4; i += GROUP) {
+                    float4 v = reinterpret_cast<const float4 *>(em)[i];
+                    v.x = ch.relu(v.x), v.y = ch.relu(v.y), v.z = ch.relu(v.z), v.w = ch.relu(v.w);
+                    reinterpret_cast<float4 *>(out)[i] = v;
+                }
+            } else {
+                for (int i = gl; i < p.wins; i += GROUP) out[i] = ch.relu(em[i]);
+            }
+            return;
+        }
         for (int i = gl; i < p.wins; i += GROUP) {
             const int pr = i / p.OW, pc = i - pr * p.OW;
             const Win w = load_win(plane, p.W, pr, pc);
@@ -722,12 +740,29 @@ __global__ __launch_bounds__(kThreads) void k_bnp_apply(const float *__restrict_
 }
 
 // grid (C, slices): partial = {sum g, sum g * xhat} with g scattered from the pooled gradient
+// FROM_MAX (E as in k_bnp_apply): for a channel with gamma > 0 the window's winner has y = E, so `affine(E) > 0` is the ReLU test and
+// xhat(E) the winner's xhat whichever tied element it is: such a channel reads E and gp (walked window by window exactly as below: the
+// sums see the same terms in the same order), any other channel reads x as before.
+template <bool FROM_MAX = false>
 __global__ __launch_bounds__(kThreads) void k_bnp_bwd_reduce(const float *__restrict__ x, const float *__restrict__ gp, BnDims d,
                                                              PoolDims p, const float *__restrict__ mean,
                                                              const float *__restrict__ invstd, const float *__restrict__ gamma,
-                                                             const float *__restrict__ beta, double *__restrict__ partial) {
+                                                             const float *__restrict__ beta, double *__restrict__ partial,
+                                                             const float *__restrict__ E = nullptr) {
     SliceSums<2> acc(d);
     const BnChan ch(mean, invstd, gamma, beta, acc.c);
+    if (FROM_MAX && ch.ga > 0.f) {                       // (uniform for the block: it owns the channel)
+        walk_planes(p.wins, acc.n0, acc.n1, [&](int n, int wi) {
+            const int64_t off = acc.plane(n) * p.wins + wi;
+            const float ev = E[off], g = gp[off];
+            if (ch.affine(ev) > 0.f) {
+                acc.run[0] += g;
+                acc.run[1] += g * ch.xhat(ev);
+            }
+        }, [&]() { acc.flush(); });
+        acc.store(partial);
+        return;
+    }
     walk_planes(p.wins, acc.n0, acc.n1, [&](int n, int wi) {
         const int pr = wi / p.OW, pc = wi - pr * p.OW;
         const int64_t pl = acc.plane(n);
@@ -781,44 +816,81 @@ inline bool wave_windows(const PoolDims &p) { return p.wins < 1024; }
 
 }  // namespace
 
+// The window maxima E[N][C][H/2][W/2] of x that a caller attached for the next pooled call of its thread (cpg_bn_relu_pool_attach_max):
+// taken -- and the thread disarmed -- by cpg_bn_relu_pool_fwd / _bwd, whatever they return.  *E = null: nothing attached.
+static int take_pool_max(const char *what, int32_t N, int32_t C, int32_t H, int32_t W, const float **E) {
+    cpg::PoolMaxCtx &pc = cpg::bn_pool_max_ctx();
+    const cpg::PoolMaxCtx got = pc;
+    pc = cpg::PoolMaxCtx{};
+    *E = nullptr;
+    if (!got.armed) return CPG_OK;
+    CPG_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && got.bytes >= (size_t)N * C * (H / 2) * (W / 2) * sizeof(float),
+                "%s: the window maxima attached (%zu bytes) are not this tensor's", what, got.bytes);
+    *E = got.E;
+    return CPG_OK;
+}
+extern "C" int cpg_bn_relu_pool_attach_max(const float *E, size_t bytes) {
+    cpg::bn_pool_max_ctx() = cpg::PoolMaxCtx{};
+    if (E == nullptr) return CPG_OK;             // (disarms)
+    CPG_REQUIRE((((uintptr_t)E) & 3) == 0 && bytes > 0, "cpg_bn_relu_pool_attach_max: needs a 4-byte aligned, non-empty buffer");
+    cpg::bn_pool_max_ctx() = cpg::PoolMaxCtx{true, const_cast<float *>(E), bytes};
+    return CPG_OK;
+}
+
+// E (may be null): the window maxima of x; stats (may be null, with E only): the producing conv's partial sums, finalised first
+static int bnp_fwd(const char *what, const float *x, const float *E, const float *stats, int32_t tiles, const float *gamma, const float *beta,
+                   float eps, float momentum, float *running_mean, float *running_var, int64_t *nbt, float *mean, float *invstd,
+                   float *y_pooled, int32_t N, int32_t C, int32_t H, int32_t W, int32_t train, void *ws, size_t ws_bytes, void *stream_v) {
+    BnDims d;
+    PoolDims p;
+    int rc = make_dims(N, C, H * W, d);
+    if (rc) return rc;
+    rc = make_pool(H, W, p);
+    if (rc) return rc;
+    CPG_REQUIRE(x && gamma && beta && mean && invstd && y_pooled, "%s: null pointer", what);
+    CPG_REQUIRE((((uintptr_t)x) & 7) == 0 && (((uintptr_t)E) & 3) == 0, "%s: x must be 8-byte, the window maxima 4-byte aligned", what);
+    hipStream_t stream = (hipStream_t)stream_v;
+    if (stats != nullptr)
+        rc = bn_stats_finalize(what, stats, tiles, N, C, H * W, eps, momentum, running_mean, running_var, mean, invstd, nbt, stream_v);
+    else if (train)
+        rc = launch_stats(what, d, x, eps, momentum, running_mean, running_var, mean, invstd, ws, ws_bytes, stream);
+    if (rc) return rc;
+    const bool wave = wave_windows(p);
+    with_flag(wave, [&](auto w) { with_flag(E != nullptr, [&](auto m) {
+        hipLaunchKernelGGL((k_bnp_apply<w() ? 64 : 256, m()>), dim3(plane_grid(d, wave)), dim3(kThreads), 0, stream, x, y_pooled, d, p, mean, invstd, gamma, beta, E);
+    }); });
+    CPG_CHECK_LAUNCH(what);
+    return CPG_OK;
+}
+
 extern "C" int cpg_bn_relu_pool_fwd(const float *x, const float *gamma, const float *beta, float eps, float momentum,
                                     float *running_mean, float *running_var, float *mean, float *invstd, float *y_pooled,
                                     int32_t N, int32_t C, int32_t H, int32_t W, int32_t train, void *ws, size_t ws_bytes,
                                     void *stream_v) {
-    BnDims d;
-    PoolDims p;
-    int rc = make_dims(N, C, H * W, d);
-    if (rc) return rc;
-    rc = make_pool(H, W, p);
-    if (rc) return rc;
-    CPG_REQUIRE(x && gamma && beta && mean && invstd && y_pooled, "cpg_bn_relu_pool_fwd: null pointer");
-    CPG_REQUIRE((((uintptr_t)x) & 7) == 0, "cpg_bn_relu_pool_fwd: x must be 8-byte aligned");
-    hipStream_t stream = (hipStream_t)stream_v;
-    if (train) rc = launch_stats("cpg_bn_relu_pool_fwd", d, x, eps, momentum, running_mean, running_var, mean, invstd, ws, ws_bytes, stream);
-    if (rc) return rc;
-    const bool wave = wave_windows(p);
-    with_flag(wave, [&](auto w) {
-        hipLaunchKernelGGL(k_bnp_apply<w() ? 64 : 256>, dim3(plane_grid(d, wave)), dim3(kThreads), 0, stream, x, y_pooled, d, p, mean, invstd, gamma, beta);
-    });
-    CPG_CHECK_LAUNCH("cpg_bn_relu_pool_fwd");
-    return CPG_OK;
+    const float *E;
+    if (const int rc = take_pool_max("cpg_bn_relu_pool_fwd", N, C, H, W, &E)) return rc;
+    return bnp_fwd("cpg_bn_relu_pool_fwd", x, E, nullptr, 0, gamma, beta, eps, momentum, running_mean, running_var, nullptr, mean, invstd, y_pooled,
+                   N, C, H, W, train, ws, ws_bytes, stream_v);
 }
 
-extern "C" int cpg_bn_relu_pool_bwd(const float *x, const float *g_pooled, const float *gamma, const float *beta,
-                                    const float *mean, const float *invstd, float *gx, float *dgamma, float *dbeta, int32_t N,
-                                    int32_t C, int32_t H, int32_t W, int32_t train, void *ws, size_t ws_bytes, void *stream_v) {
+static int bnp_bwd(const char *what, const float *x, const float *E, const float *g_pooled, const float *gamma, const float *beta,
+                   const float *mean, const float *invstd, float *gx, float *dgamma, float *dbeta, int32_t N, int32_t C, int32_t H, int32_t W,
+                   int32_t train, void *ws, size_t ws_bytes, void *stream_v) {
     BnDims d;
     PoolDims p;
     int rc = make_dims(N, C, H * W, d);
     if (rc) return rc;
     rc = make_pool(H, W, p);
     if (rc) return rc;
-    CPG_REQUIRE((((uintptr_t)x) & 7) == 0 && (((uintptr_t)gx) & 7) == 0, "cpg_bn_relu_pool_bwd: x / gx must be 8-byte aligned");
+    CPG_REQUIRE((((uintptr_t)x) & 7) == 0 && (((uintptr_t)gx) & 7) == 0 && (((uintptr_t)E) & 3) == 0,
+                "%s: x / gx must be 8-byte, the window maxima 4-byte aligned", what);
     hipStream_t stream = (hipStream_t)stream_v;
     return bn_backward(
-        "cpg_bn_relu_pool_bwd", d, gx != nullptr, x, g_pooled, gamma, beta, mean, invstd, dgamma, dbeta, nullptr, ws, ws_bytes, stream,
+        what, d, gx != nullptr, x, g_pooled, gamma, beta, mean, invstd, dgamma, dbeta, nullptr, ws, ws_bytes, stream,
         [&](double *partial) {
-            hipLaunchKernelGGL(k_bnp_bwd_reduce, dim3(C, d.slices), dim3(kThreads), 0, stream, x, g_pooled, d, p, mean, invstd, gamma, beta, partial);
+            with_flag(E != nullptr, [&](auto m) {
+                hipLaunchKernelGGL(k_bnp_bwd_reduce<m()>, dim3(C, d.slices), dim3(kThreads), 0, stream, x, g_pooled, d, p, mean, invstd, gamma, beta, partial, E);
+            });
         },
         [&](const float *coef) {
             const bool wave = wave_windows(p);
@@ -826,6 +898,34 @@ extern "C" int cpg_bn_relu_pool_bwd(const float *x, const float *g_pooled, const
                 hipLaunchKernelGGL((k_bnp_bwd_apply<t(), w() ? 64 : 256>), dim3(plane_grid(d, wave)), dim3(kThreads), 0, stream, x, g_pooled, gx, d, p, mean, invstd, gamma, beta, coef);
             }); });
         });
+}
+
+extern "C" int cpg_bn_relu_pool_bwd(const float *x, const float *g_pooled, const float *gamma, const float *beta,
+                                    const float *mean, const float *invstd, float *gx, float *dgamma, float *dbeta, int32_t N,
+                                    int32_t C, int32_t H, int32_t W, int32_t train, void *ws, size_t ws_bytes, void *stream_v) {
+    const float *E;
+    if (const int rc = take_pool_max("cpg_bn_relu_pool_bwd", N, C, H, W, &E)) return rc;
+    return bnp_bwd("cpg_bn_relu_pool_bwd", x, E, g_pooled, gamma, beta, mean, invstd, gx, dgamma, dbeta, N, C, H, W, train, ws, ws_bytes, stream_v);
+}
+
+// The same pair with the window maxima E[N][C][H/2][W/2] of x as an argument (the conv that produced x wrote them:
+// cpg_conv2d_fwd_attach_pool_max).  Forward: finalize (stats != NULL: the conv's [C][tiles][2] partial sums -> mean / invstd, the running
+// statistics and the counter, as cpg_bn_stats_finalize_count; NULL: mean / invstd are inputs) plus the apply pass.  Backward: the
+// reduction reads E; the apply pass is unchanged (it needs every x of a window and keeps torch's first-maximum routing).
+extern "C" int cpg_bn_relu_pool_fwd_from_max(const float *x, const float *E, const float *stats, int32_t tiles, const float *gamma,
+                                             const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                                             int64_t *num_batches_tracked, float *mean, float *invstd, float *y_pooled, int32_t N,
+                                             int32_t C, int32_t H, int32_t W, void *stream_v) {
+    CPG_REQUIRE(E != nullptr, "cpg_bn_relu_pool_fwd_from_max: null pointer");
+    return bnp_fwd("cpg_bn_relu_pool_fwd_from_max", x, E, stats, tiles, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked,
+                   mean, invstd, y_pooled, N, C, H, W, 0, nullptr, 0, stream_v);
+}
+extern "C" int cpg_bn_relu_pool_bwd_from_max(const float *x, const float *E, const float *g_pooled, const float *gamma, const float *beta,
+                                             const float *mean, const float *invstd, float *gx, float *dgamma, float *dbeta, int32_t N,
+                                             int32_t C, int32_t H, int32_t W, int32_t train, void *ws, size_t ws_bytes, void *stream_v) {
+    CPG_REQUIRE(E != nullptr, "cpg_bn_relu_pool_bwd_from_max: null pointer");
+    return bnp_bwd("cpg_bn_relu_pool_bwd_from_max", x, E, g_pooled, gamma, beta, mean, invstd, gx, dgamma, dbeta, N, C, H, W, train, ws, ws_bytes,
+                   stream_v);
 }
 
 

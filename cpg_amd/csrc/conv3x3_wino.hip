@@ -1237,13 +1237,20 @@ struct Bop {                                  // k_wg3's B operands of one chann
 // residual units, models/spherenet.py:121-131: `x = x + relu(conv(relu(conv(x))))`: x feeds the first conv and the sum), which autograd would
 // otherwise add in a separate 3-pass kernel.  The addend comes in through the `bias` parameter (an input-gradient launch has no bias) and is
 // shaped like y.
-template <bool DGRAD, bool STATS, bool BNE = false, bool ODD = false, bool SH = false, bool SPLIT = false, bool ADD = false>
+// PMAX (forward launches with the statistics epilogue, even maps, no bias, M a multiple of 64): the maximum of every 2x2 output tile --
+// the window of the MaxPool2d(2, 2) behind the BatchNorm that follows -- also goes out, as E[n][co][H/2][W/2], one dword per (channel,
+// tile).  A wave ends the epilogue with output row ph of the tile: it leaves max(v0, v1) in the exchange slot it has just read (that slot is
+// the other wave's, already consumed, and nobody else looks at it), and after one more barrier wave ph combines the two row maxima of channel
+// half kq = ph and stores them: 32 consecutive tiles = 128 bytes per channel and half-wave.  No further LDS, no value kept in a register
+// across the stores.  E comes in through the `bias` parameter (such a launch has no bias), as the addend does under ADD.
+template <bool DGRAD, bool STATS, bool BNE = false, bool ODD = false, bool SH = false, bool SPLIT = false, bool ADD = false, bool PMAX = false>
 __global__ __launch_bounds__(SH ? 256 : 128) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, const float *__restrict__ bias,
            float *__restrict__ y, float *__restrict__ stats, WgBnEval bn) {
     static_assert(!SH || (!BNE && !ODD), "shared B operands: training launches on even maps");
     static_assert(!SPLIT || (!STATS && !BNE && !ODD), "the tail launch has the plain epilogue only");
     static_assert(!ADD || (DGRAD && !STATS && !BNE && !SPLIT), "the addend rides in plain input-gradient launches");
+    static_assert(!PMAX || (STATS && !DGRAD && !BNE && !ODD && !SPLIT && !ADD), "the window maxima go out with the statistics of an even map");
     constexpr int UNITF = 2 * 64 * 64;                       // per unit: 2 x 2 raw stages (3264 floats) / the epilogue's exchange buffer (32 KB)
     constexpr int BXF = 2 * 2 * 2 * 2 * 64 * 4;              // SH: [buffer][ph][channel j][half][lane][4] transformed operands (16 KB)
     __shared__ __attribute__((aligned(16))) float smem_all[SH ? 2 * UNITF + BXF : UNITF];
@@ -1720,6 +1727,8 @@ void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
             v0 = (v0 - mu) * is * ga + be, v1 = (v1 - mu) * is * ga + be;
             if (bn.relu) v0 = fmaxf(v0, 0.0f), v1 = fmaxf(v1, 0.0f);
         }
+        if constexpr (PMAX)                    // this wave's row maximum, into the slot `got` came from (see PMAX)
+            xch[((((ph ^ 1) * 2 + kq) * 16 + e) * 64 + lane) * 2] = fmaxf(v0, v1);
         if constexpr (FAST) {
             f32x2 o;
             o[0] = v0, o[1] = v1;
@@ -1770,7 +1779,26 @@ void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
         }
         out_half(hb, std::integral_constant<int, 0>{}, std::false_type{}), out_half(hb, std::integral_constant<int, 1>{}, std::false_type{});
     };
-    if (bias != nullptr) out_all(std::true_type{}); else out_all(std::false_type{});
+    if constexpr (PMAX) {
+        out_all(std::false_type{});            // (`bias` is E)
+        __syncthreads();                       // both waves' row maxima are in the exchange buffer
+        // wave ph: channel half kq = ph.  The tile index inside the image IS the window index: E[n][co][ty][tx]
+        float *ebase = const_cast<float *>(bias) + (int64_t)n0 * g.M * g.tiles_img;
+        const unsigned eoff = (unsigned)((nrel * g.M + kb * 64 + ph * 32 + 4 * lh_e) * g.tiles_img + ty * g.tw + tx);
+        int timg1 = g.tiles_img;               // (a running scalar channel offset behind an opaque barrier, as HW4 above)
+        asm volatile("" : "+s"(timg1));
+        int esoff = 0;
+        const float *rowmax = xch + (ph * 16 * 64 + lane) * 2;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float a = rowmax[e * 64 * 2], b = rowmax[(2 * 16 + e) * 64 * 2];      // left by wave 1 / by wave 0
+            if (tg < ttot) ebase[eoff + (unsigned)esoff] = fmaxf(a, b);
+            esoff += (e & 3) == 3 ? 5 * timg1 : timg1;
+            asm volatile("" : "+s"(esoff));
+        }
+    } else {
+        if (bias != nullptr) out_all(std::true_type{}); else out_all(std::false_type{});
+    }
     WG_STAMP(4);
     __syncthreads();                           // the exchange buffer becomes the next unit's raw stages
     }   // next logical block
@@ -1779,7 +1807,8 @@ void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
 // y = bias + sum over the pieces of k_wg3<.., SPLIT>'s partial outputs, for the logical blocks lb_first .. lb_end - 1 of the layer (each: 64 output
 // channels x 32 tiles x 2 x 2 pixels).  The pieces are added in index order: the result does not depend on which piece finished first.
 // `part` is piece 0's slice, addressed like y (image n at (n * M + m) * H W); piece s lies s * stride floats further.
-template <bool STATS>
+// PMAX (see k_wg3): the tail's share of the window maxima; E comes in through the `addend` parameter (a forward launch has no addend).
+template <bool STATS, bool PMAX = false>
 __global__ __launch_bounds__(256) void k_wg_tail_reduce(WgGeom g, const float *__restrict__ part, const float *__restrict__ bias,
                                                         float *__restrict__ y, unsigned lb_first, unsigned lb_end, float *__restrict__ stats,
                                                         const float *__restrict__ addend) {
@@ -1807,7 +1836,9 @@ __global__ __launch_bounds__(256) void k_wg_tail_reduce(WgGeom g, const float *_
                 const f32x2 v0 = *reinterpret_cast<const f32x2 *>(p), v1 = *reinterpret_cast<const f32x2 *>(p + g.W);
                 a0[0] += v0[0], a0[1] += v0[1], a1[0] += v1[0], a1[1] += v1[1];
             }
-            if (addend != nullptr) {                                 // (the fused skip gradient of an input-gradient launch: k_wg3<.., ADD>)
+            if constexpr (PMAX) {
+                const_cast<float *>(addend)[((int64_t)n * g.M + m) * g.tiles_img + r] = fmaxf(fmaxf(a0[0], a0[1]), fmaxf(a1[0], a1[1]));
+            } else if (addend != nullptr) {                          // (the fused skip gradient of an input-gradient launch: k_wg3<.., ADD>)
                 const f32x2 d0 = *reinterpret_cast<const f32x2 *>(addend + off), d1 = *reinterpret_cast<const f32x2 *>(addend + off + g.W);
                 a0[0] += d0[0], a0[1] += d0[1], a1[0] += d1[0], a1[1] += d1[1];
             }
@@ -2002,13 +2033,14 @@ extern "C" int cpg_conv3x3_wino_tiles(int N, int c_read, int m, int H, int W) {
 enum WgMode {
     WG_FWD,           // y = conv(x) (+ bias)
     WG_FWD_STATS,     // ... + the BatchNorm partial sums of y
+    WG_FWD_STATS_PMAX,// ... + the 2x2 window maxima of y (E rides in the bias slot; k_wg3 on even maps only)
     WG_FWD_BNE,       // ... + eval-mode BatchNorm (+ ReLU), dead-channel skip: the inference epilogue
     WG_DGRAD,         // gx = dgrad(gy)
     WG_DGRAD_ADD      // ... + addend (rides in the bias slot)
 };
 struct WgLaunch {     // the arguments every instance takes
     const WgGeom &g;
-    const float *x, *up, *bias;      // bias: the addend under WG_DGRAD_ADD
+    const float *x, *up, *bias;      // bias: the addend under WG_DGRAD_ADD, the window maxima E under WG_FWD_STATS_PMAX
     float *y, *stats;                // stats: passed under WG_FWD_STATS only
     const WgBnEval &bne;             // read under WG_FWD_BNE only
     hipStream_t stream;
@@ -2016,8 +2048,9 @@ struct WgLaunch {     // the arguments every instance takes
 #define WG_GO(kernel, blocks, threads, a, stats_arg) \
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, (a).stream, (a).g, (a).x, (a).up, (a).bias, (a).y, stats_arg, (a).bne)
 
-// k_wg3<DGRAD, STATS, BNE, ODD, SH, SPLIT, ADD>: 18 instances.  ODD (odd maps) and SH (two units per four-wave block) exclude each
-// other; SPLIT (a tail piece: raw partial output) exists for the plain forward and input gradient of even maps; SH has no BNE.
+// k_wg3<DGRAD, STATS, BNE, ODD, SH, SPLIT, ADD, PMAX>: 20 instances.  ODD (odd maps) and SH (two units per four-wave block) exclude each
+// other; SPLIT (a tail piece: raw partial output) exists for the plain forward and input gradient of even maps; SH has no BNE; PMAX
+// (window maxima) exists for the statistics forward of even maps, SH or not.
 template <bool ODD, bool SH, bool SPLIT>
 static int wg3_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
     static_assert(!(ODD && (SH || SPLIT)), "k_wg3: the odd-map instances neither share the transform nor split the channel loop");
@@ -2031,6 +2064,9 @@ static int wg3_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
     if (mode == WG_DGRAD) { WG_GO((k_wg3<true, false, false, ODD, SH, SPLIT>), blocks, threads, a, nullptr); return CPG_OK; }
     if constexpr (!SPLIT) {
         if (mode == WG_FWD_STATS) { WG_GO((k_wg3<false, true, false, ODD, SH>), blocks, threads, a, a.stats); return CPG_OK; }
+    }
+    if constexpr (!SPLIT && !ODD) {
+        if (mode == WG_FWD_STATS_PMAX) { WG_GO((k_wg3<false, true, false, false, SH, false, false, true>), blocks, threads, a, a.stats); return CPG_OK; }
     }
     if (mode == WG_FWD) { WG_GO((k_wg3<false, false, false, ODD, SH, SPLIT>), blocks, threads, a, nullptr); return CPG_OK; }
     return fail(CPG_E_UNSUPPORTED, "conv3x3 (winograd): k_wg3 has no instance for mode %d (odd %d, shared %d, split %d)", (int)mode, ODD, SH, SPLIT);
@@ -2066,6 +2102,13 @@ extern "C" int cpg_conv3x3_wino_dgrad_add(int N, int c_read, int m, int H, int W
     if (!cpg_conv3x3_wino_dgrad_add_ok(N, c_read, m, H, W) || addend == nullptr)
         return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_dgrad_add(winograd): shape not supported");
     return wino_run(1, N, c_read, m, H, W, K, C, gy, w, pm, thr, nullptr, gx, nullptr, ws, ws_bytes, stream, nullptr, addend);
+}
+
+// 1: a forward launch with statistics of this shape can also write the 2x2 window maxima of its output (k_wg3<.., PMAX>): the two-wave
+// kernel on an even map, whole 64-channel blocks, CPG_NO_POOL_MAX unset
+extern "C" int cpg_conv3x3_wino_pool_max_ok(int N, int c_read, int m, int H, int W) {
+    if (cpg::opt_on(cpg::OPT_NO_POOL_MAX) || ((H | W) & 1) || m % 64 != 0) return 0;
+    return cpg_conv3x3_wino_ok(N, c_read, m, H, W) && wino_variant(c_read, m, true) == WV_PAIR64 ? 1 : 0;
 }
 
 // 1: the inference epilogue is available on the Winograd kernel (the one-wave kernel only)
@@ -2117,8 +2160,17 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
         }
         const int64_t runs = (g.tiles_total + W1_T - 1) / W1_T;
         const bool persist = wino_persist();
-        const WgMode mode = bne != nullptr ? WG_FWD_BNE : dgrad ? (addend != nullptr ? WG_DGRAD_ADD : WG_DGRAD) : stats != nullptr ? WG_FWD_STATS : WG_FWD;
-        const WgLaunch whole{g, x, up, mode == WG_DGRAD_ADD ? addend : bias, y, stats, bne != nullptr ? *bne : none, stream};
+        WgMode mode = bne != nullptr ? WG_FWD_BNE : dgrad ? (addend != nullptr ? WG_DGRAD_ADD : WG_DGRAD) : stats != nullptr ? WG_FWD_STATS : WG_FWD;
+        // the window maxima a caller attached (cpg_conv2d_fwd_attach_pool_max; cpg_conv2d_fwd_bnstats has checked the buffer's size)
+        float *pool_e = nullptr;
+        if (cpg::PoolMaxCtx &pc = cpg::pool_max_ctx(); pc.armed && mode == WG_FWD_STATS) {
+            if (bias != nullptr || !cpg_conv3x3_wino_pool_max_ok(N, c_read, m, H, W) ||
+                pc.bytes < (size_t)N * m * (H / 2) * (W / 2) * sizeof(float))
+                return fail(CPG_E_INVALID, "%s: window maxima are attached but this launch cannot write them (cpg_conv2d_fwd_pool_max_supported, no bias)", what);
+            pool_e = pc.E, pc.armed = false;
+            mode = WG_FWD_STATS_PMAX;
+        }
+        const WgLaunch whole{g, x, up, mode == WG_DGRAD_ADD ? addend : pool_e != nullptr ? pool_e : bias, y, stats, bne != nullptr ? *bne : none, stream};
         int rc;
         if (variant == WV_PAIR64) {
             int64_t blocks = runs * ((g.nkb + 1) / 2);
@@ -2148,7 +2200,9 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
             }
             auto finish_tail = [&]() {
                 const dim3 rg(stream_grid((int64_t)(tail.end_lb - tail.first_lb) * 64 * W1_T, 256));
-                if (stats != nullptr)
+                if (pool_e != nullptr)
+                    hipLaunchKernelGGL((k_wg_tail_reduce<true, true>), rg, dim3(256), 0, stream, gt, part0, bias, y, tail.first_lb, tail.end_lb, stats, (const float *)pool_e);
+                else if (stats != nullptr)
                     hipLaunchKernelGGL(k_wg_tail_reduce<true>, rg, dim3(256), 0, stream, gt, part0, bias, y, tail.first_lb, tail.end_lb, stats, (const float *)nullptr);
                 else
                     hipLaunchKernelGGL(k_wg_tail_reduce<false>, rg, dim3(256), 0, stream, gt, part0, bias, y, tail.first_lb, tail.end_lb, (float *)nullptr, addend);

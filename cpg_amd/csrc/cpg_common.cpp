@@ -22,6 +22,10 @@ static thread_local PackCtx g_pack = {};
 PackCtx &pack_ctx() { return g_pack; }
 static thread_local WgradRider g_rider = {};
 WgradRider &wgrad_rider() { return g_rider; }
+static thread_local PoolMaxCtx g_pool_max = {};
+PoolMaxCtx &pool_max_ctx() { return g_pool_max; }
+static thread_local PoolMaxCtx g_bn_pool_max = {};
+PoolMaxCtx &bn_pool_max_ctx() { return g_bn_pool_max; }
 
 int take_packed(size_t bytes, const float **pre, const char *what) {
     PackCtx &c = g_pack;
@@ -56,6 +60,7 @@ const OptDef kDefs[OPT_COUNT] = {
     {"CPG_WINO_GRIDS", INT},        {"CPG_WW_UNITS", INT},         {"CPG_WW_XCD", INT},            {"CPG_PW_TILE", INT},           {"CPG_WG3_SHARE", INT},
     {"CPG_WW_SHARE", INT},          {"CPG_WINO_TAIL", INT},         {"CPG_FC_SMALL", INT},
     {"CPG_NO_WW_RIDER", BOOL},      {"CPG_NO_GROUPED", BOOL},       {"CPG_GROUPED_WIDE_MIN", INT},
+    {"CPG_NO_POOL_MAX", BOOL},
 };
 
 struct Table {

@@ -53,6 +53,7 @@ enum Opt {
     OPT_NO_WW_RIDER,      // CPG_NO_WW_RIDER=1: cpg_conv2d_wgrad_rider_supported answers 0 (the BatchNorm backward apply stays a pass of its own)
     OPT_NO_GROUPED,       // CPG_NO_GROUPED=1: descriptors with groups > 1 are reported as unsupported (callers run one groups == 1 launch per group)
     OPT_GROUPED_WIDE_MIN, // CPG_GROUPED_WIDE_MIN=n: channels per group (both sides) from which groups > 1 run the MFMA implicit GEMM instead of the direct kernels (default 16)
+    OPT_NO_POOL_MAX,      // CPG_NO_POOL_MAX=1: cpg_conv2d_fwd_pool_max_supported answers 0 (the pooled BatchNorm passes read the conv output itself)
     OPT_COUNT
 };
 constexpr int OPT_UNSET = INT32_MIN;
@@ -96,6 +97,18 @@ struct WgradRider {
     int N, C, HW;
 };
 WgradRider &wgrad_rider();    // thread-local
+
+// ---- 2x2 window maxima of the conv output from the Winograd forward's epilogue (include/cpg_hip.h: cpg_conv2d_fwd_attach_pool_max) ------
+// Same plumbing again: cpg_conv2d_fwd_attach_pool_max arms the calling thread, the next cpg_conv2d_fwd_bnstats on it consumes (or
+// refuses) the buffer and disarms.  E: [N][K][H/2][W/2].
+struct PoolMaxCtx {
+    bool armed;
+    float *E;
+    size_t bytes;
+};
+PoolMaxCtx &pool_max_ctx();   // thread-local
+// ... and the same buffer on its way into the pooled BatchNorm passes (cpg_bn_relu_pool_attach_max -> cpg_bn_relu_pool_fwd / _bwd)
+PoolMaxCtx &bn_pool_max_ctx();   // thread-local
 
 inline int hip_status(hipError_t e, const char *what) {
     if (e == hipSuccess) return CPG_OK;

@@ -71,6 +71,9 @@ bool cpg_conv3x3_wino_pack_job(int dgrad, int N, int c_read, int m, int H, int W
 extern "C" int cpg_conv3x3_wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w,
                                     const float *pm, float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes,
                                     hipStream_t stream);
+// 1: a forward launch with statistics of this shape can also write the 2x2 window maxima of its output, to the buffer armed with
+// cpg_conv2d_fwd_attach_pool_max (the two-wave kernel on an even map, m a multiple of 64; CPG_NO_POOL_MAX: never)
+extern "C" int cpg_conv3x3_wino_pool_max_ok(int N, int c_read, int m, int H, int W);
 // 1: the inference epilogue is available on the Winograd kernels (not on the cooperative block kernel)
 extern "C" int cpg_conv3x3_wino_eval_ok(int N, int c_read, int m, int H, int W);
 // forward with eval-mode BatchNorm (+ ReLU) in the epilogue; live (may be null): live_words ints, zeroed here, layout of k_c3_pack

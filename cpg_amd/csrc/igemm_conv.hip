@@ -683,10 +683,38 @@ static int32_t bnstats_tiles(const cpg_conv_desc *d, ConvRoute route) {
     }
 }
 extern "C" int32_t cpg_conv2d_bnstats_tiles(const cpg_conv_desc *d) { return bnstats_tiles(d, fwd_route(d)); }
+
+// ---- the 2x2 window maxima of the output from the Winograd forward's epilogue (include/cpg_hip.h) ------------------------------------
+extern "C" int32_t cpg_conv2d_fwd_pool_max_supported(const cpg_conv_desc *d) {
+    ConvGeom g;
+    if (d == nullptr || make_geom(d, g) != CPG_OK || fwd_route(d) != ROUTE_C3) return 0;
+    return cpg_conv3x3_wino_pool_max_ok(d->N, d->C, d->K, d->H, d->W) ? 1 : 0;
+}
+extern "C" int cpg_conv2d_fwd_attach_pool_max(float *E, size_t bytes) {
+    cpg::pool_max_ctx() = cpg::PoolMaxCtx{};
+    if (E == nullptr) return CPG_OK;             // (disarms)
+    CPG_REQUIRE((((uintptr_t)E) & 3) == 0 && bytes > 0, "cpg_conv2d_fwd_attach_pool_max: needs a 4-byte aligned, non-empty buffer");
+    cpg::pool_max_ctx() = cpg::PoolMaxCtx{true, E, bytes};
+    return CPG_OK;
+}
+namespace {
+struct PoolMaxScope {        // one-shot, like PackScope
+    ~PoolMaxScope() { cpg::pool_max_ctx() = cpg::PoolMaxCtx{}; }
+};
+}  // namespace
+
 extern "C" int cpg_conv2d_fwd_bnstats(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr,
                                       const float *bias, float *y, float *stats, size_t stats_bytes, void *ws, size_t ws_bytes,
                                       void *stream) {
     PackScope scope;
+    PoolMaxScope pool_scope;
+    if (const cpg::PoolMaxCtx &pc = cpg::pool_max_ctx(); pc.armed) {
+        if (bias != nullptr || !cpg_conv2d_fwd_pool_max_supported(d))
+            return fail(CPG_E_INVALID, "cpg_conv2d_fwd_bnstats: window maxima are attached but this launch cannot write them "
+                                       "(cpg_conv2d_fwd_pool_max_supported, no bias)");
+        const size_t need_e = (size_t)d->N * d->K * (d->H / 2) * (d->W / 2) * sizeof(float);
+        if (pc.bytes < need_e) return fail(CPG_E_INVALID, "cpg_conv2d_fwd_bnstats: window-maxima buffer %zu < %zu bytes", pc.bytes, need_e);
+    }
     const ConvRoute route = fwd_route(d);
     const int tiles = bnstats_tiles(d, route);
     if (tiles <= 0) return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_bnstats: no fused-statistics kernel for this shape");

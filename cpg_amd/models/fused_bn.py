@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from .layers import BiasGradSink, BnBwdHint, _conv_desc
+from .layers import BiasGradSink, BnBwdHint, PoolMaxSink, _conv_desc
 
 # ---- module-level switches (the per-Sequential ones -- fuse, fuse_pool, fuse_stats, fuse_eval -- are FusedSequential's attributes) ----
 ENABLED = True          # module-wide switch (tests compare the fused against the stock evaluation)
@@ -183,27 +183,36 @@ class _BnAddReluFn(torch.autograd.Function):
 
 
 def _pool_backward(name, ctx, gp):
-    """The backward shared by both BatchNorm2d -> ReLU -> MaxPool2d Functions (cpg_bn_relu_pool_bwd / cpg_bn_relu_pool3_bwd)."""
-    (x, gamma, beta, mean, invstd), gp, N, C, _, gx, dgamma, dbeta, ws, nb = _bn_backward(ctx, gp)
+    """The backward shared by both BatchNorm2d -> ReLU -> MaxPool2d Functions (cpg_bn_relu_pool_bwd / cpg_bn_relu_pool3_bwd; with the
+    window maxima saved by the forward, attached to the same call: cpg_bn_relu_pool_attach_max)."""
+    (x, gamma, beta, mean, invstd, *emax), gp, N, C, _, gx, dgamma, dbeta, ws, nb = _bn_backward(ctx, gp)
+    for e in emax:
+        # (one-shot: the call below disarms the thread when it returns, whatever its status)
+        _lib.call('cpg_bn_relu_pool_attach_max', _lib.dptr(e), e.numel() * 4)
     _lib.call(name, _lib.dptr(x), _lib.dptr(gp, name='grad_output'), _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(mean),
               _lib.dptr(invstd), _lib.dptr(gx), _lib.dptr(dgamma), _lib.dptr(dbeta), N, C, x.shape[2], x.shape[3], int(ctx.training),
               _lib.dptr(ws), nb, _lib.stream_ptr())
-    return (gx, dgamma, dbeta) + (None,) * 7
+    return (gx, dgamma, dbeta) + (None,) * 8
 
 
 class _BnReluPoolFn(torch.autograd.Function):
-    """BatchNorm2d -> ReLU -> MaxPool2d(2, 2); only the pooled tensor is written."""
+    """BatchNorm2d -> ReLU -> MaxPool2d(2, 2); only the pooled tensor is written.  pool_max: the window maxima of x from the conv that
+    produced it (PoolMaxSink.E, with that conv's `stats`): the forward apply pass and the backward reduction read them instead of x."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, training, stats=None, nbt=None):
+    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, training, stats=None, nbt=None, pool_max=None):
         def launch(x, N, C, HW, mean, invstd, own_stats, ws, nb):
             H, W = x.shape[2:]
             y = torch.empty((N, C, H // 2, W // 2), dtype=torch.float32, device=x.device)
+            use_max = pool_max is not None and not own_stats
+            if use_max:
+                # (one-shot: the call below disarms the thread when it returns, whatever its status)
+                _lib.call('cpg_bn_relu_pool_attach_max', _lib.dptr(pool_max, name='window maxima'), pool_max.numel() * 4)
             _lib.call('cpg_bn_relu_pool_fwd', _lib.dptr(x, name='input'), _lib.dptr(gamma, name='bn.weight'), _lib.dptr(beta, name='bn.bias'),
                       float(eps), float(momentum), _lib.dptr(running_mean if own_stats else None),
                       _lib.dptr(running_var if own_stats else None), _lib.dptr(mean), _lib.dptr(invstd),
                       _lib.dptr(y), N, C, H, W, int(own_stats), _lib.dptr(ws), nb, _lib.stream_ptr())
-            return y, ()
+            return y, ((pool_max,) if use_max else ())
         return _bn_forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, training, stats, nbt, launch)
 
     @staticmethod
@@ -276,11 +285,12 @@ def conv_bn_act_pool(conv, bn, act, pool, x):
     return pool(bn_act(bn, act, y))
 
 
-def bn_relu_pool(x, bn, stats=None):
+def bn_relu_pool(x, bn, stats=None, pool_max=None):
     """max_pool2d(relu(bn(x)), 2, 2) with `bn` an nn.BatchNorm2d module; H and W must be even.  `stats`: partial sums
-    of x from the conv that produced it (SharableConv2d.forward_with_bn_stats)."""
+    of x from the conv that produced it (SharableConv2d.forward_with_bn_stats); pool_max: that conv's window maxima (PoolMaxSink.E)."""
     args, training, nbt = _bn_args(bn)
-    return _BnReluPoolFn.apply(x, *args, stats if training else None, nbt)
+    use = training and stats is not None
+    return _BnReluPoolFn.apply(x, *args, stats if training else None, nbt, pool_max if use else None)
 
 
 def fusable(bn, x):
@@ -557,7 +567,7 @@ class FusedSequential(nn.Sequential):
         mods = list(self._modules.values())
         n = len(mods)
         mods += [None] * 3
-        steps = (self._bn_relu, self._lone_bn, self._conv_bn_relu_eval, self._conv_bn_eval, self._stem, self._conv)
+        steps = (self._bn_relu, self._lone_bn, self._conv_bn_relu_eval, self._conv_bn_eval, self._stem, self._conv_bn_relu_pool, self._conv)
         i, stats, hint = 0, None, None
         while i < n:
             window = mods[i:i + 4]
@@ -624,6 +634,20 @@ class FusedSequential(nn.Sequential):
             return None
         z = stem_conv_bn_relu(m, bn, input)
         return None if z is None else (3, z, None, None)
+
+    def _conv_bn_relu_pool(self, mods, input, stats, hint):
+        """A masked conv in front of a training-mode BatchNorm2d -> ReLU -> MaxPool2d(2, 2): the conv is also asked for the maximum of
+        every pool window of its output (PoolMaxSink), which the pooled BatchNorm passes then read instead of the output itself.  Where
+        the conv cannot deliver them -- or the group behind it does not fuse -- this is _conv's step and the next one is _bn_relu's."""
+        m, bn, relu, pool = mods
+        if not (self.fuse and self.fuse_pool and ENABLED and hasattr(m, 'forward_with_bn_stats') and isinstance(relu, nn.ReLU)
+                and _is_pool2(pool) and _stats_from_conv(bn, self.fuse_stats, input)):
+            return None
+        sink = PoolMaxSink()
+        y, stats = m.forward_with_bn_stats(input, bn_hint=hint, pool_sink=sink)
+        if sink.E is None or stats is None or not fusable(bn, y):
+            return 1, y, stats, None
+        return 4, bn_relu_pool(y, bn, stats, sink.E), None, None
 
     def _conv(self, mods, input, stats, hint):
         """Any other module; a masked conv in front of a training-mode BatchNorm2d also returns that BatchNorm's partial sums."""

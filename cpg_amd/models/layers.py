@@ -173,18 +173,30 @@ def _bn_bwd_rider(hint, gz, s):
     return y, gyb, dgamma, dbeta, table
 
 
+class PoolMaxSink(object):
+    """Hand-off from a conv whose output goes through BatchNorm2d -> ReLU -> MaxPool2d(2, 2) to that group: where the forward kernel can
+    (cpg_conv2d_fwd_pool_max_supported), it also writes E[N][K][H/2][W/2], the maximum of every pool window of the raw conv output, and
+    the pooled BatchNorm passes read E instead of the full-resolution output.  E stays None where it cannot.  One sink per forward."""
+    __slots__ = ('E',)
+
+    def __init__(self):
+        self.E = None
+
+
 class _MaskedConv2dFn(torch.autograd.Function):
     """y = conv2d(x, W * bin(pm), b) and its gradients, all through the C ABI."""
 
     @staticmethod
-    def forward(ctx, x, weight, pm, bias, thr, stride, padding, dilation, groups, bn_stats=False, math='fp32', bn_hint=None, bias_sink=None):
+    def forward(ctx, x, weight, pm, bias, thr, stride, padding, dilation, groups, bn_stats=False, math='fp32', bn_hint=None, bias_sink=None,
+                pool_sink=None):
         """bn_stats: also return the per-(channel, pixel tile) {sum, sum of squares} of y that the kernel accumulates
         in its epilogue (cpg_conv2d_fwd_bnstats) -- a second, non-differentiable output, empty when the shape has
         no fused-statistics kernel.
         bn_hint (BnBwdHint or None): `x` is relu(bn(ypre)) of the layer below and nothing else consumes it -- the
         input-gradient kernel may then do that BatchNorm's backward reduction in its epilogue (cpg_conv2d_dgrad_bnbwd, hint.epilogue),
         or the weight-gradient kernel that BatchNorm's backward apply pass as a side job (cpg_conv2d_wgrad_attach_bn_bwd, hint.rider).
-        bias_sink (BiasGradSink or None): the activation behind this conv delivers the bias gradient."""
+        bias_sink (BiasGradSink or None): the activation behind this conv delivers the bias gradient.
+        pool_sink (PoolMaxSink or None; with bn_stats): receives the 2x2 window maxima of y where the kernel can write them."""
         ctx.bn_hint = bn_hint
         ctx.set_materialize_grads(False)         # (no zero-filled "gradient" tensor for the statistics output on every backward)
         ctx.bias_sink = bias_sink if bias is not None else None
@@ -234,6 +246,10 @@ class _MaskedConv2dFn(torch.autograd.Function):
                     _lib.dptr(bias, name='bias'), _lib.dptr(y))
             if tiles > 0:
                 stats = torch.empty((d.K, tiles, 2), dtype=torch.float32, device=x.device)
+                if pool_sink is not None and bias is None and L.cpg_conv2d_fwd_pool_max_supported(ctypes.byref(d)):
+                    # (one-shot: cpg_conv2d_fwd_bnstats disarms the thread when it returns, whatever its status)
+                    pool_sink.E = torch.empty((d.N, d.K, oh // 2, ow // 2), dtype=torch.float32, device=x.device)
+                    _lib.call('cpg_conv2d_fwd_attach_pool_max', _lib.dptr(pool_sink.E), pool_sink.E.numel() * 4)
                 _call_packed(pk_f, 'cpg_conv2d_fwd_bnstats', *head, _lib.dptr(stats), stats.numel() * 4, _lib.dptr(ws), nbytes,
                              _lib.stream_ptr())
             else:
@@ -252,13 +268,13 @@ class _MaskedConv2dFn(torch.autograd.Function):
         """addend (only from _MaskedConv2dSkipFn): a tensor shaped like the input gradient that is added to it -- in the kernel's
         epilogue where the shape class has that (cpg_conv2d_dgrad_add), by one add otherwise."""
         if gy is None:                           # the conv's output is unused: only a skip gradient (if any) flows
-            return (addend,) + (None,) * 12
+            return (addend,) + (None,) * 13
         x, w, p = saved = ctx.saved_tensors
         d = ctx.desc
         if ctx.empty:
             # (an empty OUTPUT with a non-empty input -- out_channels == 0 -- still passes a residual branch's gradient through)
             return (addend if addend is not None else torch.zeros_like(x), torch.zeros_like(w), None if p is None else torch.zeros_like(p),
-                    torch.zeros(d.K, dtype=torch.float32, device=x.device) if ctx.has_bias else None) + (None,) * 9
+                    torch.zeros(d.K, dtype=torch.float32, device=x.device) if ctx.has_bias else None) + (None,) * 10
         gy = gy.contiguous()
         hint, ctx.bn_hint = ctx.bn_hint, None
         ws = _lib.workspace(_lib.lib().cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
@@ -266,7 +282,7 @@ class _MaskedConv2dFn(torch.autograd.Function):
         gw = gpm = gb = None
         if ctx.needs_input_grad[1] or (p is not None and ctx.needs_input_grad[2]) or (ctx.has_bias and ctx.needs_input_grad[3]):
             gw, gpm, gb = _MaskedConv2dFn._weight_grad(ctx, saved, gy, hint, gx, ws)
-        return (gx, gw, gpm, gb) + (None,) * 9
+        return (gx, gw, gpm, gb) + (None,) * 10
 
     @staticmethod
     def _input_grad(ctx, saved, gy, hint, addend, ws):
@@ -532,18 +548,18 @@ class SharableConv2d(_Sharable):
     def _math(self):
         return getattr(self, 'math', None) or CONV_MATH
 
-    def forward_with_bn_stats(self, input, bn_hint=None):
+    def forward_with_bn_stats(self, input, bn_hint=None, pool_sink=None):
         """(Shared with packnet_models.layers.PlainConv2d, which borrows this method, forward_with_skip, forward_bn_eval and forward_bn_eval_add: they may read
         only piggymask, info['threshold'], _math(), groups, stride, padding, dilation, weight and bias, and call forward();
         tests/test_packnet_host.py and tests/test_packnet_nets_host.py check that.)
         (y, stats): forward plus the BatchNorm partial sums of y from the same kernel; stats is None when this shape
         has no fused-statistics kernel (groups > 1 among them: neither the grouped kernels nor the per-group calls take a statistics
         epilogue, a BatchNorm-backward hint or a bias sink -- callers get stats None and run the separate statistics pass).  Used by cpg_amd.models.fused_bn.FusedSequential
-        for conv -> BatchNorm2d runs."""
+        for conv -> BatchNorm2d runs.  pool_sink (PoolMaxSink or None): that BatchNorm2d is followed by ReLU -> MaxPool2d(2, 2)."""
         if self.groups != 1:
             return self.forward(input), None
         y, stats = _MaskedConv2dFn.apply(input, self.weight, self.piggymask, self.bias, self.info['threshold'],
-                                         self.stride, self.padding, self.dilation, self.groups, True, self._math(), bn_hint)
+                                         self.stride, self.padding, self.dilation, self.groups, True, self._math(), bn_hint, None, pool_sink)
         return y, (stats if stats.numel() else None)
 
     def forward_with_skip(self, input, bias_sink=None, want_stats=True):

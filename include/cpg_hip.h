@@ -113,6 +113,9 @@ int32_t cpg_get_shared_chip_hint(void);
  *   no effect on any result bit (scheduling / mapping of the same work):
  *       CPG_WINO_PERSIST, CPG_WINO_GRIDS, CPG_WW_XCD, CPG_WG3_SHARE, CPG_NO_DEAD_SKIP (skips work whose inputs are exactly zero),
  *       CPG_NO_WW_RIDER (the BatchNorm backward apply as a pass of its own instead of inside the next weight gradient).
+ *   CPG_NO_POOL_MAX (cpg_conv2d_fwd_pool_max_supported answers 0: the pooled BatchNorm passes read the conv output, not its window
+ *       maxima): no effect on the forward as numbers or on dbeta; dgamma / gx may move by an ulp of one term where two different values
+ *       of a window round to the same BatchNorm output.
  * A run is bit-reproducible for a fixed set of switch values and a fixed hint; the defaults are what every committed number used.
  * The table is global state, but not per-call mutable state: no entry point writes it, and a concurrent cpg_set_option only ever
  * changes which of the above equivalent plans a LATER call picks (the workspace caveat of the hint applies to CPG_WW_UNITS,
@@ -215,6 +218,20 @@ int cpg_bn_relu_bwd_reduce(const float *x, const float *gz, const float *gamma, 
                            size_t workspace_bytes, void *stream);
 int32_t cpg_conv2d_wgrad_rider_supported(const cpg_conv_desc *desc);
 int cpg_conv2d_wgrad_attach_bn_bwd(const float *y, const float *gz, float *gy, const float *table, int32_t N, int32_t C, int32_t HW);
+
+/* The 2x2 window maxima of a conv output from the conv kernel's own epilogue, for the BatchNorm2d -> ReLU -> MaxPool2d(2, 2) group that
+ * follows (compatible addition: the ABI version stays 3; probe with dlsym("cpg_conv2d_fwd_pool_max_supported")).  An output tile of the
+ * Winograd F(2x2, 3x3) forward IS a pool window, and for a channel with gamma > 0 the pooled output and the backward reduction are
+ * functions of the window's maximum E = max(y00, y01, y10, y11) of the raw conv output alone (the BatchNorm affine map is monotone).
+ *   cpg_conv2d_fwd_pool_max_supported(desc): 1 = cpg_conv2d_fwd_bnstats of this shape (called WITHOUT a bias) can also write
+ *       E[N][K][H/2][W/2]: the two-wave Winograd kernel with the statistics epilogue, H and W even, K a multiple of 64,
+ *       CPG_NO_POOL_MAX unset.  Everything else (the one-wave and direct kernels, odd maps, other widths) answers 0.
+ *   cpg_conv2d_fwd_attach_pool_max(E, bytes): arms THE CALLING THREAD -- the next cpg_conv2d_fwd_bnstats on it also writes E (bytes >=
+ *       N K (H/2) (W/2) floats).  One-shot: that call disarms the thread when it returns, whatever its status; a shape the query refuses,
+ *       a bias or a short buffer is CPG_E_INVALID before anything is launched.  E == NULL disarms.
+ * y and the statistics are bit-equal to the call without E; E is exactly the maximum over each window of that y. */
+int32_t cpg_conv2d_fwd_pool_max_supported(const cpg_conv_desc *desc);
+int cpg_conv2d_fwd_attach_pool_max(float *E, size_t bytes);
 
 /* ---- K5: F.linear of models/layers.py:194 and its autograd ----
  * x [batch][in], w [out][in], y [batch][out]; same masking / gradient rules as conv. */
@@ -534,6 +551,24 @@ int cpg_bn_relu_pool_bwd(const float *x, const float *g_pooled, const float *gam
                          const float *mean, const float *invstd, float *gx, float *dgamma, float *dbeta,
                          int32_t N, int32_t C, int32_t H, int32_t W, int32_t train, void *ws, size_t ws_bytes,
                          void *stream);
+/* The same pair with E[N][C][H/2][W/2], the window maxima of x from the conv that produced x (cpg_conv2d_fwd_attach_pool_max; the
+ * ABI version stays 3, probe for the symbols).  A channel with gamma > 0 reads E instead of x in the forward apply pass and in the
+ * backward reduction (1/4 of the bytes); a channel with gamma <= 0 reads x exactly as above.  The backward apply pass is unchanged.
+ *   forward: stats != NULL: [C][tiles][2] partial sums of cpg_conv2d_fwd_bnstats, finalised here as cpg_bn_stats_finalize_count does
+ *       (num_batches_tracked may be NULL); stats == NULL: mean / invstd are inputs.  y_pooled equals cpg_bn_relu_pool_fwd's as numbers
+ *       (the sign of a zero may differ).
+ *   backward: dbeta is bit-equal to cpg_bn_relu_pool_bwd's; dgamma and gx are too unless two DIFFERENT values of a window round to the
+ *       same BatchNorm output, where the term of sum(g xhat) takes xhat of the larger instead of the first (an ulp of one term).
+ *   cpg_bn_relu_pool_attach_max(E, bytes): the same through the entry points above -- arms THE CALLING THREAD, and the next
+ *       cpg_bn_relu_pool_fwd or cpg_bn_relu_pool_bwd on it reads E (bytes >= N C (H/2) (W/2) floats, else CPG_E_INVALID) exactly as the
+ *       _from_max call would.  One-shot: that call disarms the thread whatever it returns.  E == NULL disarms. */
+int cpg_bn_relu_pool_attach_max(const float *E, size_t bytes);
+int cpg_bn_relu_pool_fwd_from_max(const float *x, const float *E, const float *stats, int32_t tiles, const float *gamma, const float *beta,
+                                  float eps, float momentum, float *running_mean, float *running_var, int64_t *num_batches_tracked,
+                                  float *mean, float *invstd, float *y_pooled, int32_t N, int32_t C, int32_t H, int32_t W, void *stream);
+int cpg_bn_relu_pool_bwd_from_max(const float *x, const float *E, const float *g_pooled, const float *gamma, const float *beta,
+                                  const float *mean, const float *invstd, float *gx, float *dgamma, float *dbeta, int32_t N, int32_t C,
+                                  int32_t H, int32_t W, int32_t train, void *ws, size_t ws_bytes, void *stream);
 
 /* BatchNorm2d -> ReLU -> MaxPool2d(3, stride 2, padding 1): the ResNet stem's tail (models/resnet.py:127-129,208-211 -- stock torch:
  * BatchNorm apply, max_pool2d with an int64 index tensor, max_pool2d backward, BatchNorm backward).  mean / invstd are given

@@ -8,6 +8,11 @@ the command profiled with rocprofv3 --pmc.
 Passes beside fwd / dgrad / wgrad and the opt-in bf16 ones: `wgradr` = the weight gradient with a BatchNorm-backward rider attached
 (cpg_conv2d_wgrad_attach_bn_bwd on a tensor shaped like the layer's input; skipped where the query says no), `bnbwd` / `bnred` = the
 standalone cpg_bn_relu_bwd on that tensor and its reduce + finalize part alone (their difference is the apply pass the rider replaces).
+The pooled chain of a layer whose output goes through BatchNorm2d -> ReLU -> MaxPool2d(2, 2) (f3, f10, f17, f27, f34): `fwdstats` / `fwdstatsm`
+= the forward with the statistics epilogue without / with the window maxima attached (cpg_conv2d_fwd_attach_pool_max; skipped where the
+query says no), `bnpfwd` / `bnpfwdm` = the pooled apply pass reading the conv output / the maxima, `bnpbwd` / `bnpbwdm` = the pooled backward
+(reduce + finalize + apply) with the reduction reading the conv output / the maxima: the apply pass is the same kernel in both, so their
+difference is the reduction's.
 """
 import argparse
 import ctypes
@@ -95,11 +100,35 @@ def main():
         dgb = [torch.empty(C, device=dev) for _ in range(2)]
         wsb, nbb = _lib.workspace(L.cpg_bn_workspace_bytes(a.batch, C, H * H), dev)
         rider_ok = bool(L.cpg_conv2d_wgrad_rider_supported(ctypes.byref(d))) and x.numel() * 4 < (1 << 31)
+        # the pooled chain behind this layer: BatchNorm -> ReLU -> MaxPool2d(2, 2) on y, with or without y's window maxima
+        pool_passes = {'fwdstatsm', 'bnpfwd', 'bnpfwdm', 'bnpbwd', 'bnpbwdm'} & set(a.only.split(','))
+        pmax_ok = bool(L.cpg_conv2d_fwd_pool_max_supported(ctypes.byref(d)))
+        if pool_passes:
+            emax = torch.empty(a.batch, K, H // 2, H // 2, device=dev)
+            ypool, gpool = torch.empty_like(emax), torch.randn_like(emax)
+            kp = [torch.rand(K, device=dev) + 0.5 for _ in range(2)] + [torch.zeros(K, device=dev), torch.ones(K, device=dev)]   # gamma, beta, mean, invstd
+            kdgb = [torch.empty(K, device=dev) for _ in range(2)]
+            wsk, nbk = _lib.workspace(L.cpg_bn_workspace_bytes(a.batch, K, H * H), dev)
+            if pool_passes - {'fwdstatsm'}:
+                y.normal_()
+                emax.copy_(torch.nn.functional.max_pool2d(y, 2, 2))
+        bwd_tail = lambda: (P(gpool), P(kp[0]), P(kp[1]), P(kp[2]), P(kp[3]), P(gy), P(kdgb[0]), P(kdgb[1]), a.batch, K, H, H, 1, P(wsk), nbk, st)
+
+        def fwdstats_max():
+            rc = L.cpg_conv2d_fwd_attach_pool_max(P(emax), emax.numel() * 4)
+            return rc or runs['fwdstats']()
 
         def wgrad_rider():
             rc = L.cpg_conv2d_wgrad_attach_bn_bwd(P(ry), P(gx), P(rgy), P(table), a.batch, C, H * H)
             return rc or L.cpg_conv2d_wgrad(ctypes.byref(d), P(x), P(gy), P(w), P(pm), 5e-3, P(gw), P(gpm), None, P(ws), nb, st)
         runs = {'wgradr': wgrad_rider,
+                'fwdstatsm': fwdstats_max,
+                'bnpfwd': lambda: L.cpg_bn_relu_pool_fwd(P(y), P(kp[0]), P(kp[1]), 1e-5, 0.1, None, None, P(kp[2]), P(kp[3]), P(ypool), a.batch, K, H, H, 0,
+                                                         None, 0, st),
+                'bnpfwdm': lambda: L.cpg_bn_relu_pool_fwd_from_max(P(y), P(emax), None, 0, P(kp[0]), P(kp[1]), 1e-5, 0.1, None, None, None, P(kp[2]),
+                                                                   P(kp[3]), P(ypool), a.batch, K, H, H, st),
+                'bnpbwd': lambda: L.cpg_bn_relu_pool_bwd(P(y), *bwd_tail()),           # (gy serves as the gradient output: same shape as y)
+                'bnpbwdm': lambda: L.cpg_bn_relu_pool_bwd_from_max(P(y), P(emax), *bwd_tail()),
                 'bnbwd': lambda: L.cpg_bn_relu_bwd(P(ry), P(gx), P(bp[0]), P(bp[1]), P(bp[2]), P(bp[3]), P(rgy), P(dgb[0]), P(dgb[1]), a.batch, C, H * H,
                                                    1, 1, P(wsb), nbb, st),
                 'bnred': lambda: L.cpg_bn_relu_bwd_reduce(P(ry), P(gx), P(bp[0]), P(bp[1]), P(bp[2]), P(bp[3]), P(dgb[0]), P(dgb[1]), P(table), a.batch,
@@ -118,6 +147,8 @@ def main():
             if k in ('dgrad', 'dgrad16', 'dgradx3') and name == 'f0':
                 continue
             if k == 'wgradr' and not rider_ok:
+                continue
+            if k in ('fwdstatsm', 'bnpfwdm', 'bnpbwdm') and not pmax_ok:
                 continue
             if k == 'wgradr':
                 gx.normal_()
