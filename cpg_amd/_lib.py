@@ -123,6 +123,8 @@ _SIGNATURES = {
     'cpg_conv2d_fwd_bn_eval': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
     'cpg_conv2d_fwd_bn_eval_add_supported': (_i32, [_desc]),
     'cpg_conv2d_fwd_bn_eval_add': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _vp, _vp, _sz, _vp]),
+    'cpg_conv2d_fwd_prelu_eval_supported': (_i32, [_desc, _i32]),
+    'cpg_conv2d_fwd_prelu_eval': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     'cpg_conv2d_bf16_supported': (_i32, [_desc]),
     'cpg_conv2d_bf16_workspace_bytes': (_sz, [_desc]),
     'cpg_conv2d_fwd_bf16': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _sz, _vp]),

@@ -1304,18 +1304,18 @@ __global__ __launch_bounds__(kThreads) void k_prelu_fwd(const float *__restrict_
         if (vec) {
             for (int i = gl; i < d.HW / 4; i += GROUP) {
                 float4 v = reinterpret_cast<const float4 *>(p)[i];
-                v.x = v.x > 0.f ? v.x : a * v.x; v.y = v.y > 0.f ? v.y : a * v.y;
-                v.z = v.z > 0.f ? v.z : a * v.z; v.w = v.w > 0.f ? v.w : a * v.w;
+                v.x = prelu_one(v.x, a); v.y = prelu_one(v.y, a);
+                v.z = prelu_one(v.z, a); v.w = prelu_one(v.w, a);
                 if (r != nullptr) {
                     const float4 t = reinterpret_cast<const float4 *>(r)[i];
-                    v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
+                    v.x = prelu_sum(v.x, t.x); v.y = prelu_sum(v.y, t.y); v.z = prelu_sum(v.z, t.z); v.w = prelu_sum(v.w, t.w);
                 }
                 reinterpret_cast<float4 *>(q)[i] = v;
             }
         } else {
             for (int i = gl; i < d.HW; i += GROUP) {
                 const float v = p[i];
-                q[i] = (v > 0.f ? v : a * v) + (r ? r[i] : 0.f);
+                q[i] = prelu_add(v, a, r ? r[i] : 0.f);
             }
         }
     });

@@ -64,6 +64,9 @@ __device__ __forceinline__ f32x4 ld_sv4(const float *sbase, unsigned byte_off) {
 // conv output is exactly 0, the epilogue still writes bias / BatchNorm of 0), and every block stops after the last live
 // input-channel chunk.  Whole channels die when a model that was GROWN for later tasks serves an earlier, narrower task
 // after apply_mask (every slot with owner > task is zero): the kernel then does the work of the cropped model.
+// The PReLU inference epilogue (k_c3_fwd<.., PRE>: y = prelu(acc + bias) [+ residual], cpg_common.h's prelu_one / prelu_sum) travels in the
+// same struct, so that no existing instance's arguments change: gamma = the slopes, relu = 1 for one slope per channel (0: one shared),
+// beta = the residual, dense and shaped like y, or null; mean / var unused.  `live` and the skip are the same.
 struct C3BnEval {
     const float *gamma, *beta, *mean, *var;
     float eps;
@@ -177,12 +180,13 @@ __global__ __launch_bounds__(256) void k_c3_pack(const float *__restrict__ w, co
 // (cpg_conv2d_fwd_bnstats + cpg_bn_stats_finalize; deterministic: fixed-order merges only).
 // SPLITK: g.ksplit blocks share a tile's channel chunks and atomically add their accumulators into a zeroed y.  Two addends
 // per element commute, so the result does not depend on which block arrives first (0 + a + b = 0 + b + a bitwise).
-template <class Cfg, bool DGRAD, bool STATS = false, bool SPLITK = false, bool BRED = false>
+template <class Cfg, bool DGRAD, bool STATS = false, bool SPLITK = false, bool BRED = false, bool PRE = false>
 __global__ __launch_bounds__(256, Cfg::MINW) void k_c3_fwd(C3Geom g, const float *__restrict__ x, const float *__restrict__ wp,
                                                            const float *__restrict__ bias, float *__restrict__ y,
                                                            float *__restrict__ stats, C3BnEval bn, C3BnBwd bb) {
     static_assert(!BRED || (DGRAD && !STATS && !SPLITK), "the BatchNorm-backward reduction rides in plain input-gradient launches");
     static_assert(!Cfg::S2 || (!DGRAD && !SPLITK && !BRED), "the strided tiles are forward-only (its input gradient is k_c3s2_dgrad)");
+    static_assert(!PRE || (!DGRAD && !STATS && !SPLITK && !BRED), "the PReLU epilogue rides in plain inference forward launches");
     __shared__ __attribute__((aligned(16))) float smem[Cfg::SMEM_FLOATS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / Cfg::WN, wn = wave % Cfg::WN;
@@ -436,7 +440,30 @@ __global__ __launch_bounds__(256, Cfg::MINW) void k_c3_fwd(C3Geom g, const float
                     bv[e] = bias[co < g.M ? co : 0];
                 }
             }
-            if (!DGRAD && !STATS && !SPLITK && bn.gamma != nullptr) {       // eval-mode BatchNorm (+ ReLU) in the epilogue (uniform branch)
+            if constexpr (PRE) {                                            // inference PReLU (+ the unit's residual) in the epilogue (see C3BnEval)
+                float sl[16], rv[16];
+                const float *rin = bn.beta != nullptr ? bn.beta + (int64_t)(n + img) * g.M * HWo : nullptr;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int co = m0 + (wm * Cfg::FM + fm) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+                    sl[e] = bn.gamma[bn.relu && co < g.M ? co : 0];
+                    rv[e] = 0.0f;
+                }
+                if (rin != nullptr) {                   // one uniform branch per fragment, 16 loads issued together
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) {
+                        const int co = m0 + (wm * Cfg::FM + fm) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+                        if (pok && co < g.M) rv[e] = rin[(int64_t)co * HWo + poff];
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    float v = prelu_one(acc[fm][fn][e] + bv[e], sl[e]);
+                    if (rin != nullptr) v = prelu_sum(v, rv[e]);
+                    acc[fm][fn][e] = v;
+                    bv[e] = 0.0f;
+                }
+            } else if (!DGRAD && !STATS && !SPLITK && bn.gamma != nullptr) {       // eval-mode BatchNorm (+ ReLU) in the epilogue (uniform branch)
                 float ga[16], be[16], mu[16], is[16];
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
@@ -1079,6 +1106,7 @@ struct C3Extra {
     float *stats = nullptr;         // forward: [m][tiles][2] BatchNorm partial sums of y; with bb: the BatchNorm-backward partial sums
     const C3BnEval *bn = nullptr;   // forward: eval-mode BatchNorm (+ ReLU) epilogue (its `live` is filled in from the workspace here)
     bool live = false;              // ... with the dead-channel skip: the pack writes the workspace's liveness words, the kernel reads them
+    bool prelu = false;             // ... bn carries the PReLU inference epilogue instead (see C3BnEval): the PRE instances
     const C3BnBwd *bb = nullptr;    // input gradient: BatchNorm-backward reduction of the layer below in the epilogue
 };
 
@@ -1142,6 +1170,8 @@ int launch_fwd(C3Geom g, const float *x, const float *wp, const float *bias, flo
         hipLaunchKernelGGL((k_c3_fwd<Cfg, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, nullptr, bn, bb);
     else if (stats != nullptr)
         hipLaunchKernelGGL((k_c3_fwd<Cfg, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, stats, bn, bb);
+    else if (ex.prelu && bnp != nullptr)
+        hipLaunchKernelGGL((k_c3_fwd<Cfg, false, false, false, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, nullptr, bn, bb);
     else
         hipLaunchKernelGGL((k_c3_fwd<Cfg, false>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, nullptr, bn, bb);
     CPG_CHECK_LAUNCH(what);
@@ -1210,6 +1240,9 @@ int run_fwd(bool dgrad, int N, int c_read, int m, int H, int W, int K, int C, co
         const size_t off = (pack_bytes(c_read, m) + 15) / 16 * 16;
         if (ws == nullptr || ws_bytes < off) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, off);
         int *live = ex.live ? reinterpret_cast<int *>((float *)ws + pack_floats(c_read, m)) : nullptr;
+        if (ex.prelu)
+            return cpg_conv3x3_wino_run_prelu_eval(N, c_read, m, H, W, x, w, pm, thr, bias, ex.bn->gamma, ex.bn->relu, ex.bn->beta, live, live_words(c_read, m), y,
+                                                   (char *)ws + off, ws_bytes - off, stream);
         return cpg_conv3x3_wino_run_bn_eval(N, c_read, m, H, W, x, w, pm, thr, bias, ex.bn->gamma, ex.bn->beta, ex.bn->mean, ex.bn->var, ex.bn->eps, ex.bn->relu,
                                             live, live_words(c_read, m), y, (char *)ws + off, ws_bytes - off, stream);
     }
@@ -1281,29 +1314,54 @@ int cpg_conv3x3_fwd_bnstats(const cpg_conv_desc *d, const float *x, const float 
     return run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, x, w, pm, thr, bias, y, ws, ws_bytes, stream, ex);
 }
 
-// forward with the inference-mode BatchNorm (+ ReLU) that follows the conv folded into the epilogue (Manager.validate's path)
-int cpg_conv3x3_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                            const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu, float *y,
-                            int32_t *skip_stats, void *ws, size_t ws_bytes, hipStream_t stream) {
-    CPG_REQUIRE(x && w && y && gamma && beta && mean && var, "cpg_conv2d_fwd_bn_eval: null pointer");
+// the inference forward: bn's epilogue (eval-mode BatchNorm, or the PReLU one) and the dead-channel skip; skip_stats (may be null): 2 device words
+static int run_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, const C3BnEval &bn,
+                        bool prelu, float *y, int32_t *skip_stats, void *ws, size_t ws_bytes, hipStream_t stream, const char *what) {
     const bool skip = !opt_on(OPT_NO_DEAD_SKIP);
-    const C3BnEval bn{gamma, beta, mean, var, eps, relu, nullptr};
     C3Extra ex;
     ex.bn = &bn;
     ex.live = skip;
+    ex.prelu = prelu;
     int rc = run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, x, w, pm, thr, bias, y, ws, ws_bytes, stream, ex);
     if (rc == CPG_OK && skip_stats != nullptr) {
         // {4 * (input chunks up to the last live one), output blocks skipped}: device-to-device copy of the two words behind live[Mp]
         if (skip) {
             const int *live = reinterpret_cast<const int *>((const float *)ws + pack_floats(d->C, d->K));
             hipError_t e = hipMemcpyAsync(skip_stats, live + pad_to(d->K, 128), 2 * sizeof(int), hipMemcpyDeviceToDevice, stream);
-            if (e != hipSuccess) return hip_status(e, "cpg_conv2d_fwd_bn_eval");
+            if (e != hipSuccess) return hip_status(e, what);
         } else {
             hipError_t e = hipMemsetAsync(skip_stats, 0, 2 * sizeof(int), stream);
-            if (e != hipSuccess) return hip_status(e, "cpg_conv2d_fwd_bn_eval");
+            if (e != hipSuccess) return hip_status(e, what);
         }
     }
     return rc;
+}
+
+// forward with the inference-mode BatchNorm (+ ReLU) that follows the conv folded into the epilogue (Manager.validate's path)
+int cpg_conv3x3_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                            const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu, float *y,
+                            int32_t *skip_stats, void *ws, size_t ws_bytes, hipStream_t stream) {
+    CPG_REQUIRE(x && w && y && gamma && beta && mean && var, "cpg_conv2d_fwd_bn_eval: null pointer");
+    const C3BnEval bn{gamma, beta, mean, var, eps, relu, nullptr};
+    return run_fwd_eval(d, x, w, pm, thr, bias, bn, false, y, skip_stats, ws, ws_bytes, stream, "cpg_conv2d_fwd_bn_eval");
+}
+
+// 1: the inference epilogues (cpg_conv3x3_fwd_bn_eval / _prelu_eval) have a launch for this shape under the current option table -- the
+// plan of the call itself, asked without running it.  The channel-split 14 x 14 tile (CPG_C3_FORCE=8) has no fused epilogue.
+int cpg_conv3x3_eval_epilogue_ok(const cpg_conv_desc *d) {
+    const C3Plan plan = plan_fwd(false, d->N, d->C, d->K, d->H, d->W, C3_BN_EVAL);
+    if (plan.route == C3_WINO_EVAL) return 1;
+    return plan.route == C3_DIRECT && plan.ksplit == 1 && plan.blocks <= 0x7FFFFFFFll ? 1 : 0;
+}
+
+// ... with bias, PReLU and the unit's residual folded in instead: y = prelu(conv + bias) [+ residual], the same plan and the same skip
+int cpg_conv3x3_fwd_prelu_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                               const float *slope, int per_channel, const float *residual, float *y, int32_t *skip_stats, void *ws,
+                               size_t ws_bytes, hipStream_t stream) {
+    CPG_REQUIRE(x && w && y && slope, "cpg_conv2d_fwd_prelu_eval: null pointer");
+    if (!cpg_conv3x3_eval_epilogue_ok(d)) return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_prelu_eval: no fused epilogue on channel-split tiles");
+    const C3BnEval bn{slope, residual, nullptr, nullptr, 0.0f, per_channel, nullptr};
+    return run_fwd_eval(d, x, w, pm, thr, bias, bn, true, y, skip_stats, ws, ws_bytes, stream, "cpg_conv2d_fwd_prelu_eval");
 }
 
 // the packed operand a caller may hand to the forward (dgrad = 0) or the input gradient: the Winograd launch's, where the pass runs there
@@ -1462,7 +1520,7 @@ using S2G128 = C3Cfg<128, 4, 32, 2, 2, 4, 2, 1, 0, 1>;  // anything else
 using S2G64 = C3Cfg<64, 8, 32, 1, 4, 4, 2, 1, 0, 1>;    // ... with <= 64 output channels
 
 template <class Cfg>
-int launch_fwd_s2(C3Geom g, const float *x, const float *wp, const float *bias, float *y, float *stats, const C3BnEval &bn, hipStream_t stream) {
+int launch_fwd_s2(C3Geom g, const float *x, const float *wp, const float *bias, float *y, float *stats, const C3BnEval &bn, bool prelu, hipStream_t stream) {
     const C3BnBwd bb{nullptr, nullptr, nullptr, nullptr, nullptr};
     g.tiles_x = (g.OW + Cfg::TW - 1) / Cfg::TW;
     g.tiles_y = (g.OH + Cfg::TH - 1) / Cfg::TH;
@@ -1471,6 +1529,8 @@ int launch_fwd_s2(C3Geom g, const float *x, const float *wp, const float *bias, 
     if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "conv3x3 s2: grid too large");
     if (stats != nullptr)
         hipLaunchKernelGGL((k_c3_fwd<Cfg, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, stats, bn, bb);
+    else if (prelu)
+        hipLaunchKernelGGL((k_c3_fwd<Cfg, false, false, false, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, nullptr, bn, bb);
     else
         hipLaunchKernelGGL((k_c3_fwd<Cfg, false>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, nullptr, bn, bb);
     CPG_CHECK_LAUNCH("cpg_conv2d_fwd(3x3 s2)");
@@ -1489,10 +1549,12 @@ C3Plan plan_fwd_s2(const cpg_conv_desc *d) {
     return c3_direct<S2G128>(TILE_S2G128, 1, N, K, OH, OW);
 }
 
-// bn (may be null; not together with stats): the eval-mode BatchNorm (+ ReLU) epilogue, with live == nullptr -- the strided tiles skip nothing
+// bn (may be null; not together with stats): the eval-mode BatchNorm (+ ReLU) epilogue, with live == nullptr -- the strided tiles skip nothing;
+// prelu: bn carries the PReLU epilogue instead (see C3BnEval)
 int run_fwd_s2(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y, float *stats,
-               const C3BnEval *bnp, void *ws, size_t ws_bytes, hipStream_t stream) {
+               const C3BnEval *bnp, void *ws, size_t ws_bytes, hipStream_t stream, bool prelu = false) {
     const char *what = "cpg_conv2d_fwd(3x3 s2)";
+    if (prelu && (bnp == nullptr || stats != nullptr)) return fail(CPG_E_INVALID, "%s: the PReLU epilogue needs its slopes and takes no statistics", what);
     const C3BnEval bn = bnp ? *bnp : C3BnEval{nullptr, nullptr, nullptr, nullptr, 0.0f, 0, nullptr};
     float *wp = (float *)ws;
     const int rows_c = pad_to(d->C, 4), Mp = pad_to(d->K, 128);
@@ -1503,11 +1565,11 @@ int run_fwd_s2(const cpg_conv_desc *d, const float *x, const float *w, const flo
                        rows_c, Mp, 0, (int *)nullptr);
     C3Geom g{d->N, d->C, d->H, d->W, d->K, Mp, 0, 0, 0, s2_out(d->H), s2_out(d->W), 0, 1};
     switch (plan_fwd_s2(d).tile) {
-        case TILE_S2P28: return launch_fwd_s2<S2P28>(g, x, wp, bias, y, stats, bn, stream);
-        case TILE_S2M8: return launch_fwd_s2<S2M8>(g, x, wp, bias, y, stats, bn, stream);
-        case TILE_S2S16: return launch_fwd_s2<S2S16>(g, x, wp, bias, y, stats, bn, stream);
-        case TILE_S2G64: return launch_fwd_s2<S2G64>(g, x, wp, bias, y, stats, bn, stream);
-        case TILE_S2G128: return launch_fwd_s2<S2G128>(g, x, wp, bias, y, stats, bn, stream);
+        case TILE_S2P28: return launch_fwd_s2<S2P28>(g, x, wp, bias, y, stats, bn, prelu, stream);
+        case TILE_S2M8: return launch_fwd_s2<S2M8>(g, x, wp, bias, y, stats, bn, prelu, stream);
+        case TILE_S2S16: return launch_fwd_s2<S2S16>(g, x, wp, bias, y, stats, bn, prelu, stream);
+        case TILE_S2G64: return launch_fwd_s2<S2G64>(g, x, wp, bias, y, stats, bn, prelu, stream);
+        case TILE_S2G128: return launch_fwd_s2<S2G128>(g, x, wp, bias, y, stats, bn, prelu, stream);
         default: return fail(CPG_E_INVALID, "%s: not a stride-2 tile", what);
     }
 }
@@ -1556,6 +1618,14 @@ int cpg_conv3x3s2_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const floa
     CPG_REQUIRE(x && w && y && gamma && beta && mean && var, "cpg_conv2d_fwd_bn_eval: null pointer");
     const C3BnEval bn{gamma, beta, mean, var, eps, relu, nullptr};
     return run_fwd_s2(d, x, w, pm, thr, bias, y, nullptr, &bn, ws, ws_bytes, stream);
+}
+// ... with bias and PReLU folded in: y = prelu(conv + bias).  No residual: a strided conv opens a stage, nothing of its output's shape exists yet.
+int cpg_conv3x3s2_fwd_prelu_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                                 const float *slope, int per_channel, float *y, void *ws, size_t ws_bytes, hipStream_t stream) {
+    CPG_REQUIRE(x && w && y && slope, "cpg_conv2d_fwd_prelu_eval: null pointer");
+    if (plan_fwd_s2(d).blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_prelu_eval: grid too large");
+    const C3BnEval bn{slope, nullptr, nullptr, nullptr, 0.0f, per_channel, nullptr};
+    return run_fwd_s2(d, x, w, pm, thr, bias, y, nullptr, &bn, ws, ws_bytes, stream, true);
 }
 int cpg_conv3x3s2_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                         size_t ws_bytes, hipStream_t stream) {

@@ -589,6 +589,9 @@ __global__ __launch_bounds__(256) void k_pack_jobs(const PackArgs a, const PackA
 // `live` (may be null) are the flags k_wg1_pack wrote, same layout as k_c3_pack's (live[m]: output channel m has a non-zero
 // weight; live[Mp + 4 + q]: input chunk q has one; live[Mp] receives 4 x the chunks up to the last live one, live[Mp + 1] counts
 // the waves that skipped their MFMA loop).
+// The PReLU inference epilogue (the PRE instances: y = prelu(conv + bias) [+ residual], cpg_common.h's prelu_one / prelu_sum) travels in the
+// same struct, as in conv3x3.hip: gamma = the slopes, relu = 1 for one slope per channel (0: one shared), beta = the residual, dense and
+// shaped like y, or null; mean / var unused.  `live` and the skip are the same.
 struct WgBnEval {
     const float *gamma, *beta, *mean, *var;
     float eps;
@@ -605,10 +608,11 @@ __device__ unsigned long long wg_dbg[65536 * 8];
 #else
 #define WG_STAMP(i)
 #endif
-template <bool DGRAD, bool STATS, bool BNE = false>
+template <bool DGRAD, bool STATS, bool BNE = false, bool PRE = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_wg1(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, const float *__restrict__ bias,
            float *__restrict__ y, float *__restrict__ stats, WgBnEval bn) {
+    static_assert(!PRE || (BNE && !DGRAD && !STATS), "the PReLU epilogue is an inference epilogue");
     __shared__ __attribute__((aligned(16))) float smem_all[4 * 2 * W1_RAW];
     // (readfirstlane: tells the compiler the wave index is wave-uniform, so that everything derived from it -- the tile run, the
     //  buffer descriptor of its first image -- lives in scalar registers; without it every buffer load became a waterfall loop)
@@ -879,6 +883,10 @@ void k_wg1(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
     const int ty = (int)((unsigned)r / twu), tx = (int)((unsigned)r % twu);
     float *yout = y + ((int64_t)n * g.M) * HW + (2 * ty) * g.W + 2 * tx;
     float s1[16], s2[16];
+    // (PRE) the residual, at the store's own address + the uniform distance between the two tensors: nothing new for the compiler to keep
+    // per lane across the main loop (this kernel's loop owns all 256 vector registers)
+    const bool has_res = PRE && bn.beta != nullptr;
+    const intptr_t rdelta = has_res ? reinterpret_cast<intptr_t>(bn.beta) - reinterpret_cast<intptr_t>(y) : 0;
     // hb: with / without a conv bias, decided ONCE outside (the two epilogues are separate code).  With the bias load behind a
     // branch inside the per-channel code the compiler's s_waitcnt vmcnt(0) for it sat in the common path: every channel waited for
     // the previous channel's stores to be acknowledged, 16 round trips = 3.9 us of a 29 us unit on the 64-channel layers
@@ -895,7 +903,16 @@ void k_wg1(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
         if constexpr (decltype(hb)::value) bv = bias[co < g.M ? co : 0];
         float v00 = r_[0][0] + r_[1][0] + r_[2][0] + bv, v01 = r_[0][1] + r_[1][1] + r_[2][1] + bv;
         float v10 = r_[1][0] - r_[2][0] - r_[3][0] + bv, v11 = r_[1][1] - r_[2][1] - r_[3][1] + bv;
-        if (BNE) {                             // y = [max(0,] (conv + bias - mean) * invstd * gamma + beta [)]
+        if constexpr (PRE) {                   // y = prelu(conv + bias) [+ residual]
+            const float a = bn.gamma[bn.relu && co < g.M ? co : 0];
+            v00 = prelu_one(v00, a), v01 = prelu_one(v01, a), v10 = prelu_one(v10, a), v11 = prelu_one(v11, a);
+            if (has_res && tv && co < g.M) {
+                const char *rp = reinterpret_cast<const char *>(yout + (int64_t)co * HW) + rdelta;
+                const f32x2 r0 = *reinterpret_cast<const f32x2 *>(rp), r1 = *reinterpret_cast<const f32x2 *>(rp + (int64_t)g.W * 4);
+                v00 = prelu_sum(v00, r0[0]), v01 = prelu_sum(v01, r0[1]);
+                v10 = prelu_sum(v10, r1[0]), v11 = prelu_sum(v11, r1[1]);
+            }
+        } else if (BNE) {                      // y = [max(0,] (conv + bias - mean) * invstd * gamma + beta [)]
             const int cc = co < g.M ? co : 0;
             const float mu = bn.mean[cc], is = 1.0f / sqrtf(bn.var[cc] + bn.eps), ga = bn.gamma[cc], be = bn.beta[cc];
             v00 = (v00 - mu) * is * ga + be, v01 = (v01 - mu) * is * ga + be;
@@ -957,7 +974,7 @@ constexpr int W2_RAW = 4 * 3 * W1_ROW;                    // one stage of one wa
 
 
 
-template <bool DGRAD, bool STATS, bool BNE = false>
+template <bool DGRAD, bool STATS, bool BNE = false, bool PRE = false>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_wg2(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, const float *__restrict__ bias,
            float *__restrict__ y, float *__restrict__ stats, WgBnEval bn) {
@@ -1169,7 +1186,14 @@ void k_wg2(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
             const float bv = bias[co < g.M ? co : 0];
             v0 += bv, v1 += bv;
         }
-        if (BNE) {                             // y = [max(0,] (conv + bias - mean) * invstd * gamma + beta [)]
+        if constexpr (PRE) {                   // y = prelu(conv + bias) [+ residual]
+            const float a = bn.gamma[bn.relu && co < g.M ? co : 0];
+            v0 = prelu_one(v0, a), v1 = prelu_one(v1, a);
+            if (bn.beta != nullptr && tv && co < g.M) {
+                const f32x2 rr = *reinterpret_cast<const f32x2 *>(bn.beta + (yout - y) + (int64_t)co * HW);
+                v0 = prelu_sum(v0, rr[0]), v1 = prelu_sum(v1, rr[1]);
+            }
+        } else if (BNE) {                      // y = [max(0,] (conv + bias - mean) * invstd * gamma + beta [)]
             const int cc = co < g.M ? co : 0;
             const float mu = bn.mean[cc], is = 1.0f / sqrtf(bn.var[cc] + bn.eps), ga = bn.gamma[cc], be = bn.beta[cc];
             v0 = (v0 - mu) * is * ga + be, v1 = (v1 - mu) * is * ga + be;
@@ -1243,10 +1267,15 @@ struct Bop {                                  // k_wg3's B operands of one chann
 // the other wave's, already consumed, and nobody else looks at it), and after one more barrier wave ph combines the two row maxima of channel
 // half kq = ph and stores them: 32 consecutive tiles = 128 bytes per channel and half-wave.  No further LDS, no value kept in a register
 // across the stores.  E comes in through the `bias` parameter (such a launch has no bias), as the addend does under ADD.
-template <bool DGRAD, bool STATS, bool BNE = false, bool ODD = false, bool SH = false, bool SPLIT = false, bool ADD = false, bool PMAX = false>
+// PRE (inference launches, with BNE: the same skip): y = prelu(conv + bias) [+ residual] instead of the BatchNorm expression (see WgBnEval).
+// The residual is fetched as ADD fetches its addend -- on the fast path four channels' worth with the group's exchange reads, at y's own
+// offsets -- but from bn.beta: the bias slot holds the conv's bias here.
+template <bool DGRAD, bool STATS, bool BNE = false, bool ODD = false, bool SH = false, bool SPLIT = false, bool ADD = false, bool PMAX = false,
+          bool PRE = false>
 __global__ __launch_bounds__(SH ? 256 : 128) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, const float *__restrict__ bias,
            float *__restrict__ y, float *__restrict__ stats, WgBnEval bn) {
+    static_assert(!PRE || (BNE && !DGRAD && !STATS), "the PReLU epilogue is an inference epilogue");
     static_assert(!SH || (!BNE && !ODD), "shared B operands: training launches on even maps");
     static_assert(!SPLIT || (!STATS && !BNE && !ODD), "the tail launch has the plain epilogue only");
     static_assert(!ADD || (DGRAD && !STATS && !BNE && !SPLIT), "the addend rides in plain input-gradient launches");
@@ -1671,6 +1700,10 @@ void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
     // (ADD) the addend at the same offsets as y: `bias` IS the addend tensor
     const char *abase = reinterpret_cast<const char *>(bias + (ADD ? (int64_t)n0 * g.M * HW : 0));
     const float *aout = bias + (ADD ? ((int64_t)n * g.M) * HW + (2 * ty + ph) * g.W + 2 * tx : 0);
+    // (PRE) the residual at the same offsets as y; null: none (a wave-uniform test)
+    const bool has_res = PRE && bn.beta != nullptr;
+    const char *rbase = reinterpret_cast<const char *>(bn.beta + (has_res ? (int64_t)n0 * g.M * HW : 0));
+    const float *rout = bn.beta + (has_res ? ((int64_t)n * g.M) * HW + (2 * ty + ph) * g.W + 2 * tx : 0);
     const unsigned yoff = (unsigned)(((nrel * g.M + kb * 64 + 4 * lh_e) * HW + (2 * ty + ph) * g.W + 2 * tx) * 4);
     // (the scalar channel offsets are a running sum behind an opaque barrier: as multiples of HW they are invariant in the persistent
     //  loop, the compiler would compute all 32 in front of it and spill scalar registers into vector lanes)
@@ -1684,7 +1717,7 @@ void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
     float s1[16], s2[16];
     constexpr int GR = STATS ? 2 : 4;          // (the statistics variant has no registers for four)
     f32x2 got4[GR];
-    f32x2 ad4[(ADD && FAST) ? GR : 1];         // (ADD, fast path) the addend of the group's GR channels, requested with the exchange reads
+    f32x2 ad4[((ADD || PRE) && FAST) ? GR : 1];         // (ADD / PRE, fast path) the addend of the group's GR channels, requested with the exchange reads
     int soff = kq * 32 * HW4;                  // (kq * 32 + (e & 3) + 8 * (e >> 2)) * HW4, stepped
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -1699,6 +1732,14 @@ void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
 #pragma unroll
                 for (int j = 0; j < GR; ++j)
                     ad4[j] = *reinterpret_cast<const f32x2 *>(abase + (size_t)(yoff + (unsigned)(soff + j * HW4)));
+            }
+            if constexpr (PRE && FAST) {
+                static_assert(!PRE || GR == 4, "a group is the four channels between two 5 HW jumps of the running offset");
+                if (has_res) {
+#pragma unroll
+                    for (int j = 0; j < GR; ++j)
+                        ad4[j] = *reinterpret_cast<const f32x2 *>(rbase + (size_t)(yoff + (unsigned)(soff + j * HW4)));
+                }
             }
         }
         const f32x2 got = got4[e & (GR - 1)];
@@ -1721,7 +1762,22 @@ void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
                 v0 += bv, v1 += bv;
             }
         }
-        if (BNE) {                             // y = [max(0,] (conv + bias - mean) * invstd * gamma + beta [)]
+        if constexpr (PRE) {                   // y = prelu(conv + bias) [+ residual]
+            const float a = bn.gamma[bn.relu && co < g.M ? co : 0];
+            v0 = prelu_one(v0, a), v1 = prelu_one(v1, a);
+            if (has_res) {
+                if constexpr (FAST) {
+                    v0 = prelu_sum(v0, ad4[e & (GR - 1)][0]), v1 = prelu_sum(v1, ad4[e & (GR - 1)][1]);
+                } else if (tv && co < g.M) {
+                    if (ODD && oddcol) {
+                        v0 = prelu_sum(v0, rout[(int64_t)co * HW]);
+                    } else {
+                        const f32x2 rr = *reinterpret_cast<const f32x2 *>(rout + (int64_t)co * HW);
+                        v0 = prelu_sum(v0, rr[0]), v1 = prelu_sum(v1, rr[1]);
+                    }
+                }
+            }
+        } else if (BNE) {                      // y = [max(0,] (conv + bias - mean) * invstd * gamma + beta [)]
             const int cc = co < g.M ? co : 0;
             const float mu = bn.mean[cc], is = 1.0f / sqrtf(bn.var[cc] + bn.eps), ga = bn.gamma[cc], be = bn.beta[cc];
             v0 = (v0 - mu) * is * ga + be, v1 = (v1 - mu) * is * ga + be;
@@ -2035,6 +2091,7 @@ enum WgMode {
     WG_FWD_STATS,     // ... + the BatchNorm partial sums of y
     WG_FWD_STATS_PMAX,// ... + the 2x2 window maxima of y (E rides in the bias slot; k_wg3 on even maps only)
     WG_FWD_BNE,       // ... + eval-mode BatchNorm (+ ReLU), dead-channel skip: the inference epilogue
+    WG_FWD_PRE,       // ... + PReLU (+ residual) instead of the BatchNorm, the same skip: SphereNet's inference epilogue
     WG_DGRAD,         // gx = dgrad(gy)
     WG_DGRAD_ADD      // ... + addend (rides in the bias slot)
 };
@@ -2042,13 +2099,13 @@ struct WgLaunch {     // the arguments every instance takes
     const WgGeom &g;
     const float *x, *up, *bias;      // bias: the addend under WG_DGRAD_ADD, the window maxima E under WG_FWD_STATS_PMAX
     float *y, *stats;                // stats: passed under WG_FWD_STATS only
-    const WgBnEval &bne;             // read under WG_FWD_BNE only
+    const WgBnEval &bne;             // read under WG_FWD_BNE / WG_FWD_PRE only
     hipStream_t stream;
 };
 #define WG_GO(kernel, blocks, threads, a, stats_arg) \
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, (a).stream, (a).g, (a).x, (a).up, (a).bias, (a).y, stats_arg, (a).bne)
 
-// k_wg3<DGRAD, STATS, BNE, ODD, SH, SPLIT, ADD, PMAX>: 20 instances.  ODD (odd maps) and SH (two units per four-wave block) exclude each
+// k_wg3<DGRAD, STATS, BNE, ODD, SH, SPLIT, ADD, PMAX, PRE>: 22 instances (PRE: where BNE exists).  ODD (odd maps) and SH (two units per four-wave block) exclude each
 // other; SPLIT (a tail piece: raw partial output) exists for the plain forward and input gradient of even maps; SH has no BNE; PMAX
 // (window maxima) exists for the statistics forward of even maps, SH or not.
 template <bool ODD, bool SH, bool SPLIT>
@@ -2069,9 +2126,12 @@ static int wg3_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
         if (mode == WG_FWD_STATS_PMAX) { WG_GO((k_wg3<false, true, false, false, SH, false, false, true>), blocks, threads, a, a.stats); return CPG_OK; }
     }
     if (mode == WG_FWD) { WG_GO((k_wg3<false, false, false, ODD, SH, SPLIT>), blocks, threads, a, nullptr); return CPG_OK; }
+    if constexpr (!SH && !SPLIT) {
+        if (mode == WG_FWD_PRE) { WG_GO((k_wg3<false, false, true, ODD, false, false, false, false, true>), blocks, threads, a, nullptr); return CPG_OK; }
+    }
     return fail(CPG_E_UNSUPPORTED, "conv3x3 (winograd): k_wg3 has no instance for mode %d (odd %d, shared %d, split %d)", (int)mode, ODD, SH, SPLIT);
 }
-// k_wg2<DGRAD, STATS, BNE> and k_wg1<DGRAD, STATS, BNE>: 4 instances each, no addend
+// k_wg2<DGRAD, STATS, BNE, PRE> and k_wg1<DGRAD, STATS, BNE, PRE>: 5 instances each, no addend
 static int wg2_launch(WgMode mode, unsigned blocks, const WgLaunch &a);
 static int wg1_launch(WgMode mode, unsigned blocks, const WgLaunch &a);
 // the cooperative block kernel k_wg_fwd (CPG_WINO_KERNEL=block only): packs for itself, no inference epilogue
@@ -2084,7 +2144,7 @@ static int wino_run_block(int dgrad, int N, int c_read, int m, int H, int W, int
 // w is the layer's [K][C][3][3] weight.  stats (forward only, may be null): [m][tiles][2] partial sums for the BatchNorm.
 static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
                     float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream, const WgBnEval *bne,
-                    const float *addend = nullptr);
+                    const float *addend = nullptr, bool prelu = false);
 
 extern "C" int cpg_conv3x3_wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x,
                                     const float *w, const float *pm, float thr, const float *bias, float *y, float *stats,
@@ -2129,9 +2189,23 @@ extern "C" int cpg_conv3x3_wino_run_bn_eval(int N, int C, int K, int H, int W, c
     return wino_run(0, N, C, K, H, W, K, C, x, w, pm, thr, bias, y, nullptr, ws, ws_bytes, stream, &bne);
 }
 
+// ... with bias, PReLU (+ residual) in the epilogue instead (bne = null is refused: the mode is an inference mode)
+extern "C" int cpg_conv3x3_wino_run_prelu_eval(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr,
+                                               const float *bias, const float *slope, int per_channel, const float *residual, int *live,
+                                               size_t live_words, float *y, void *ws, size_t ws_bytes, hipStream_t stream) {
+    if (slope == nullptr) return fail(CPG_E_INVALID, "cpg_conv2d_fwd_prelu_eval(winograd): null slope");
+    if (live != nullptr) {
+        hipError_t e = hipMemsetAsync(live, 0, live_words * sizeof(int), stream);
+        if (e != hipSuccess) return hip_status(e, "cpg_conv2d_fwd_prelu_eval(winograd)");
+    }
+    const WgBnEval pre{slope, residual, nullptr, nullptr, 0.0f, per_channel ? 1 : 0, live, pad_to(K, 128)};
+    return wino_run(0, N, C, K, H, W, K, C, x, w, pm, thr, bias, y, nullptr, ws, ws_bytes, stream, &pre, nullptr, true);
+}
+
 static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
                     float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream, const WgBnEval *bne,
-                    const float *addend) {
+                    const float *addend, bool prelu) {
+    if (prelu && bne == nullptr) return fail(CPG_E_INVALID, "cpg_conv2d_fwd(winograd): the PReLU epilogue needs its slopes");
     const char *what = dgrad ? "cpg_conv2d_dgrad(winograd)" : "cpg_conv2d_fwd(winograd)";
     // addend (input-gradient launches of the two-wave kernel only: cpg_conv3x3_wino_dgrad_add_ok): added to the result in the epilogue
     // (k_wg3<.., ADD>; the tail pieces' share in k_wg_tail_reduce)
@@ -2160,7 +2234,7 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
         }
         const int64_t runs = (g.tiles_total + W1_T - 1) / W1_T;
         const bool persist = wino_persist();
-        WgMode mode = bne != nullptr ? WG_FWD_BNE : dgrad ? (addend != nullptr ? WG_DGRAD_ADD : WG_DGRAD) : stats != nullptr ? WG_FWD_STATS : WG_FWD;
+        WgMode mode = bne != nullptr ? (prelu ? WG_FWD_PRE : WG_FWD_BNE) : dgrad ? (addend != nullptr ? WG_DGRAD_ADD : WG_DGRAD) : stats != nullptr ? WG_FWD_STATS : WG_FWD;
         // the window maxima a caller attached (cpg_conv2d_fwd_attach_pool_max; cpg_conv2d_fwd_bnstats has checked the buffer's size)
         float *pool_e = nullptr;
         if (cpg::PoolMaxCtx &pc = cpg::pool_max_ctx(); pc.armed && mode == WG_FWD_STATS) {
@@ -2255,6 +2329,7 @@ static int wg2_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
         case WG_DGRAD: WG_GO((k_wg2<true, false>), blocks, 128, a, nullptr); return CPG_OK;
         case WG_FWD_STATS: WG_GO((k_wg2<false, true>), blocks, 128, a, a.stats); return CPG_OK;
         case WG_FWD: WG_GO((k_wg2<false, false>), blocks, 128, a, nullptr); return CPG_OK;
+        case WG_FWD_PRE: WG_GO((k_wg2<false, false, true, true>), blocks, 128, a, nullptr); return CPG_OK;
         default: return fail(CPG_E_UNSUPPORTED, "conv3x3 (winograd): k_wg2 takes no addend");
     }
 }
@@ -2264,6 +2339,7 @@ static int wg1_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
         case WG_DGRAD: WG_GO((k_wg1<true, false>), blocks, 256, a, nullptr); return CPG_OK;
         case WG_FWD_STATS: WG_GO((k_wg1<false, true>), blocks, 256, a, a.stats); return CPG_OK;
         case WG_FWD: WG_GO((k_wg1<false, false>), blocks, 256, a, nullptr); return CPG_OK;
+        case WG_FWD_PRE: WG_GO((k_wg1<false, false, true, true>), blocks, 256, a, nullptr); return CPG_OK;
         default: return fail(CPG_E_UNSUPPORTED, "conv3x3 (winograd): k_wg1 takes no addend");
     }
 }

@@ -149,6 +149,17 @@ __device__ __forceinline__ float bn_bwd_apply_one(float xv, float gv, float m, f
     return TRAIN ? (gv - mg - bn_xhat(xv, m, is) * mgx) * scale : gv * scale;
 }
 
+// The PReLU formula (SphereNet's activation), ONE definition: z = v > 0 ? v : a v, and z + r behind it where a unit's residual rides
+// along.  The product is rounded, then selected, then the sum is rounded -- never a fused multiply-add across the select (contraction is
+// off inside): k_prelu_fwd (bn_kernels.hip) and the inference epilogues of the 3x3 kernels (cpg_conv2d_fwd_prelu_eval) call these and must
+// round alike bit for bit.
+__device__ __forceinline__ float prelu_one(float v, float a) { return v > 0.f ? v : a * v; }
+__device__ __forceinline__ float prelu_sum(float z, float r) {
+#pragma clang fp contract(off)
+    return z + r;
+}
+__device__ __forceinline__ float prelu_add(float v, float a, float r) { return prelu_sum(prelu_one(v, a), r); }
+
 constexpr int kCUs = 256;        // MI355X
 constexpr int kXCDs = 8;
 

@@ -21,6 +21,13 @@ int cpg_conv3x3_fwd_bnstats(const cpg_conv_desc *d, const float *x, const float 
 int cpg_conv3x3_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                             const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu, float *y,
                             int32_t *skip_stats, void *ws, size_t ws_bytes, hipStream_t stream);
+// 1: the inference epilogues have a launch for this shape under the current option table (the planner's answer; 0: the channel-split tile)
+int cpg_conv3x3_eval_epilogue_ok(const cpg_conv_desc *d);
+// forward with bias, PReLU and the unit's residual folded into the epilogue: y = prelu(conv + bias) [+ residual]; the plan, the workspace
+// and the dead-channel skip of cpg_conv3x3_fwd_bn_eval.  per_channel: K slopes (0: one shared); residual (may be null): dense, shaped like y
+int cpg_conv3x3_fwd_prelu_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                               const float *slope, int per_channel, const float *residual, float *y, int32_t *skip_stats, void *ws,
+                               size_t ws_bytes, hipStream_t stream);
 int cpg_conv3x3_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                       size_t ws_bytes, hipStream_t stream);
 // the packed operand cpg_conv3x3_fwd / _fwd_bnstats (dgrad = 0) or cpg_conv3x3_dgrad streams and a caller may hand in (cpg_conv2d_use_packed);
@@ -48,6 +55,9 @@ int cpg_conv3x3s2_fwd(const cpg_conv_desc *d, const float *x, const float *w, co
 int cpg_conv3x3s2_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                               const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu, float *y,
                               void *ws, size_t ws_bytes, hipStream_t stream);
+// forward with bias and PReLU folded into the epilogue (no residual, no dead-channel skip on the strided tiles)
+int cpg_conv3x3s2_fwd_prelu_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                                 const float *slope, int per_channel, float *y, void *ws, size_t ws_bytes, hipStream_t stream);
 int cpg_conv3x3s2_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                         size_t ws_bytes, hipStream_t stream);
 size_t cpg_conv3x3s2_wgrad_workspace(const cpg_conv_desc *d);
@@ -81,6 +91,10 @@ extern "C" int cpg_conv3x3_wino_run_bn_eval(int N, int C, int K, int H, int W, c
                                             const float *bias, const float *gamma, const float *beta, const float *mean, const float *var,
                                             float eps, int relu, int *live, size_t live_words, float *y, void *ws, size_t ws_bytes,
                                             hipStream_t stream);
+// forward with bias, PReLU (+ residual) in the epilogue: the same launch plan, liveness words and skip, the PRE instances
+extern "C" int cpg_conv3x3_wino_run_prelu_eval(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr,
+                                               const float *bias, const float *slope, int per_channel, const float *residual, int *live,
+                                               size_t live_words, float *y, void *ws, size_t ws_bytes, hipStream_t stream);
 // input gradient + addend (gx = dgrad(gy) + addend): the two-wave kernel's launches (>= 64 channels on both sides, or an odd map)
 extern "C" int cpg_conv3x3_wino_dgrad_add_ok(int N, int c_read, int m, int H, int W);
 extern "C" int cpg_conv3x3_wino_dgrad_add(int N, int c_read, int m, int H, int W, int K, int C, const float *gy, const float *w, const float *pm,

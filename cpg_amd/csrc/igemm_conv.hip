@@ -790,6 +790,40 @@ extern "C" int cpg_conv2d_fwd_bn_eval_add(const cpg_conv_desc *d, const float *x
                                    (hipStream_t)stream);
 }
 
+// SphereNet's inference: conv -> (+ bias) -> PReLU (-> + the unit's residual) in one kernel, y = prelu(conv + bias) [+ residual].  The
+// classes: 3x3 s1 p1 (cpg_conv2d_fwd_bn_eval's plan and dead-channel skip; with or without a residual) and 3x3 s2 (no residual, no skip).
+// The query is the planner's answer: no launch code runs for it.
+extern "C" int32_t cpg_conv2d_fwd_prelu_eval_supported(const cpg_conv_desc *d, int32_t with_residual) {
+    ConvGeom g;
+    if (d == nullptr || make_geom(d, g) != CPG_OK) return 0;
+    const ConvRoute route = fwd_route(d);
+    if (route == ROUTE_C3) return cpg_conv3x3_eval_epilogue_ok(d);
+    return route == ROUTE_C3S2 && !with_residual ? 1 : 0;
+}
+extern "C" int cpg_conv2d_fwd_prelu_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr,
+                                         const float *bias, const float *slope, int32_t n_slopes, const float *residual, float *y,
+                                         int32_t *skip_stats, void *ws, size_t ws_bytes, void *stream) {
+    ConvGeom g;
+    int rc = make_geom(d, g);
+    if (rc) return rc;
+    CPG_REQUIRE(x && w && y && slope, "cpg_conv2d_fwd_prelu_eval: null pointer");
+    CPG_REQUIRE(n_slopes == d->K || n_slopes == 1, "cpg_conv2d_fwd_prelu_eval: n_slopes must be K or 1");
+    if (!cpg_conv2d_fwd_prelu_eval_supported(d, residual != nullptr ? 1 : 0))
+        return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_prelu_eval: only the 3x3 s1 p1 kernels (and, without a residual, the 3x3 s2 kernels) "
+                                       "fuse the epilogue; not on channel-split tiles");
+    // (K == 1: one slope either way -- read as per-channel, index 0)
+    const int per_channel = n_slopes == d->K ? 1 : 0;
+    if (fwd_route(d) == ROUTE_C3)
+        return cpg_conv3x3_fwd_prelu_eval(d, x, w, pm, thr, bias, slope, per_channel, residual, y, skip_stats, ws, ws_bytes, (hipStream_t)stream);
+    PackScope scope;
+    rc = cpg_conv3x3s2_fwd_prelu_eval(d, x, w, pm, thr, bias, slope, per_channel, y, ws, ws_bytes, (hipStream_t)stream);
+    if (rc == CPG_OK && skip_stats != nullptr) {        // the strided tiles skip nothing: what CPG_NO_DEAD_SKIP reports
+        hipError_t e = hipMemsetAsync(skip_stats, 0, 2 * sizeof(int32_t), (hipStream_t)stream);
+        if (e != hipSuccess) return hip_status(e, "cpg_conv2d_fwd_prelu_eval");
+    }
+    return rc;
+}
+
 // input gradient + the BatchNorm-backward reduction of the layer below in its epilogue (3x3 s1 p1 kernels only)
 extern "C" int32_t cpg_conv2d_dgrad_bnbwd_tiles(const cpg_conv_desc *d) {
     ConvGeom g;

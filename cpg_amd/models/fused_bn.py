@@ -32,6 +32,13 @@ FUSE_SKIP_ADD = True    # residual blocks: the identity branch's gradient is add
 # Inference on the residual topologies: conv -> BatchNorm2d(eval) [-> + residual] [-> ReLU] as ONE kernel wherever the conv has such an
 # epilogue (cpg_conv2d_fwd_bn_eval / _add: pointwise, 3x3 s1, 3x3 s2).  Off: conv, then the BatchNorm pass, launch for launch as before.
 FUSE_EVAL_BLOCKS = True
+# Inference on SphereNet: conv -> (+ bias) -> PReLU [-> + the unit's residual] as ONE kernel wherever the conv has such an epilogue
+# (cpg_conv2d_fwd_prelu_eval: 3x3 s1, 3x3 s2 without a residual).  Off: conv, then cpg_prelu_fwd, launch for launch as before.
+# OFF by default (profiles/spherenet_eval_fuse.md): the full-width forward measured 2.96 ms on against 2.66 ms off at batch 100 and 6.07
+# against 5.89 ms at batch 256.  The epilogue itself saves what was estimated on the 56 x 56 layers (-0.046 ms per pair), but the fused call
+# runs the INFERENCE plan of the conv, and on the eight 256 -> 256 pairs at 14 x 14 that plan -- the two-wave Winograd kernel without the
+# shared input transform and without the tail launch of the training forward -- is 0.043 ms per pair slower than cpg_conv2d_fwd + the pass.
+FUSE_EVAL_PRELU = False
 
 
 def _batch_stats(stats, nbt, N, C, HW, eps, momentum, running_mean, running_var, training, device):
@@ -359,9 +366,21 @@ def _prelu_fits(mod, x, conv=None):
             and (conv is None or (torch.is_grad_enabled() and conv._math() == 'fp32' and getattr(conv, 'groups', 1) == 1)))
 
 
+def _conv_prelu_eval(conv, mod, x, res=None):
+    """Inference: mod(conv(x)) [+ res] as one kernel (FUSE_EVAL_PRELU, under torch.no_grad(), a conv that offers forward_prelu_eval), or
+    None -- the method itself refuses what it has no kernel for."""
+    if ENABLED and FUSE_EVAL_PRELU and not torch.is_grad_enabled() and hasattr(conv, 'forward_prelu_eval'):
+        return conv.forward_prelu_eval(x, mod, res)
+    return None
+
+
 def conv_prelu(conv, mod, x, res=None):
     """mod(conv(x)) [+ res] for SphereNet's biased conv -> PReLU pairs (models/spherenet.py:203-247): the PReLU's backward pass also
-    delivers the conv's bias gradient (the per-channel sum of the gradient it writes), so the conv's backward runs no bias reduction."""
+    delivers the conv's bias gradient (the per-channel sum of the gradient it writes), so the conv's backward runs no bias reduction.
+    Under torch.no_grad() the pair (and the residual) is one kernel where the conv has the epilogue (_conv_prelu_eval)."""
+    y = _conv_prelu_eval(conv, mod, x, res)
+    if y is not None:
+        return y
     if getattr(conv, 'bias', None) is not None and _prelu_fits(mod, x, conv):
         sink = BiasGradSink()
         y = conv(x, bias_sink=sink)
@@ -375,7 +394,11 @@ def conv_prelu_skip(conv, mod, x):
     """(mod(conv(x)), x) for the FIRST conv of a SphereNet residual unit (models/spherenet.py:121-131: `x = x + relu(conv(relu(conv(x))))`):
     x feeds this conv and the unit's sum.  The returned x is routed through the conv's autograd node, which then receives BOTH gradients
     of x and adds the sum's in its input-gradient epilogue (cpg_conv2d_dgrad_add: the two-wave Winograd kernel's ADD instances) instead of
-    leaving a separate add kernel to autograd.  Falls back to (conv_prelu(conv, mod, x), x) when the pair does not qualify."""
+    leaving a separate add kernel to autograd.  Falls back to (conv_prelu(conv, mod, x), x) when the pair does not qualify -- under
+    torch.no_grad() that is the one-kernel inference pair."""
+    y = _conv_prelu_eval(conv, mod, x)
+    if y is not None:
+        return y, x
     if x.requires_grad and _prelu_fits(mod, x, conv) and x.dim() == 4 and x.is_contiguous():
         sink = BiasGradSink() if getattr(conv, 'bias', None) is not None else None
         y, _, skip = conv.forward_with_skip(x, bias_sink=sink, want_stats=False)

@@ -549,7 +549,7 @@ class SharableConv2d(_Sharable):
         return getattr(self, 'math', None) or CONV_MATH
 
     def forward_with_bn_stats(self, input, bn_hint=None, pool_sink=None):
-        """(Shared with packnet_models.layers.PlainConv2d, which borrows this method, forward_with_skip, forward_bn_eval and forward_bn_eval_add: they may read
+        """(Shared with packnet_models.layers.PlainConv2d, which borrows this method, forward_with_skip, forward_bn_eval, forward_bn_eval_add and forward_prelu_eval: they may read
         only piggymask, info['threshold'], _math(), groups, stride, padding, dilation, weight and bias, and call forward();
         tests/test_packnet_host.py and tests/test_packnet_nets_host.py check that.)
         (y, stats): forward plus the BatchNorm partial sums of y from the same kernel; stats is None when this shape
@@ -620,6 +620,39 @@ class SharableConv2d(_Sharable):
                   _lib.dptr(bn.weight, name='bn.weight'), _lib.dptr(bn.bias, name='bn.bias'), _lib.dptr(bn.running_mean, name='running_mean'),
                   _lib.dptr(bn.running_var, name='running_var'), float(bn.eps), _lib.dptr(res.contiguous(), name='residual'),
                   int(bool(relu)), _lib.dptr(y), _lib.dptr(ws), nbytes, _lib.stream_ptr())
+        return y
+
+    def forward_prelu_eval(self, input, prelu, res=None, skip_stats=None):
+        """prelu(conv(input)) [+ res] -- a conv of models/spherenet.py with the nn.PReLU behind it and, at the end of a unit, the unit's
+        residual (added AFTER the activation) -- as ONE kernel (cpg_conv2d_fwd_prelu_eval: the 3x3 s1 p1 shapes, with the dead-channel
+        skip of forward_bn_eval, and without `res` the 3x3 s2 shapes).  Inference only, like forward_bn_eval; returns None when grad
+        mode is on, `prelu` is not a plain nn.PReLU with 1 or out_channels slopes, this shape or arithmetic has no such kernel, or `res`
+        is not a dense fp32 device tensor shaped like the output."""
+        if torch.is_grad_enabled() or type(prelu) is not torch.nn.PReLU or prelu.weight.numel() not in (1, self.weight.shape[0]):
+            return None
+        if (input.dim() != 4 or input.shape[0] == 0 or input.shape[1] != self.weight.shape[1] * self.groups
+                or self._math() != 'fp32' or self.groups != 1):
+            return None
+        x = input.contiguous()
+        w = self.weight.contiguous()
+        p = None if self.piggymask is None else self.piggymask.contiguous()
+        d = _conv_desc(x.shape, w.shape, self.stride, self.padding, self.dilation, self.groups)
+        L = _lib.lib()
+        if not L.cpg_conv2d_fwd_prelu_eval_supported(ctypes.byref(d), 0 if res is None else 1):
+            return None
+        oh, ow = _out_hw(d)
+        if res is not None and (tuple(res.shape) != (d.N, d.K, oh, ow) or res.dtype != torch.float32 or not res.is_cuda
+                                or not res.is_contiguous() or res.data_ptr() % 16):
+            return None
+        slope = prelu.weight
+        if slope.dtype != torch.float32 or not slope.is_cuda:
+            return None
+        y = torch.empty((d.N, d.K, oh, ow), dtype=torch.float32, device=x.device)
+        ws, nbytes = _lib.workspace(L.cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
+        _lib.call('cpg_conv2d_fwd_prelu_eval', ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'),
+                  _lib.dptr(p, name='piggymask'), float(self.info['threshold']), _lib.dptr(self.bias, name='bias'),
+                  _lib.dptr(slope.contiguous(), name='prelu.weight'), slope.numel(), _lib.dptr(res, name='residual'), _lib.dptr(y),
+                  None if skip_stats is None else ctypes.c_void_p(skip_stats.data_ptr()), _lib.dptr(ws), nbytes, _lib.stream_ptr())
         return y
 
     def extra_repr(self):

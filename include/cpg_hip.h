@@ -448,6 +448,25 @@ int cpg_conv2d_fwd_bn_eval_add(const cpg_conv_desc *desc, const float *x, const 
                                const float *running_var, float eps, const float *residual, int32_t relu, float *y, void *workspace,
                                size_t workspace_bytes, void *stream);
 
+/* SphereNet's inference (models/spherenet.py: `x = relu1_1(conv1_1(x)); x = x + relu1_3(conv1_3(relu1_2(conv1_2(x))))` with nn.PReLU
+ * activations, under model.eval() and torch.no_grad()): conv -> (+ bias) -> PReLU (-> + the unit's residual) as ONE kernel,
+ *     v = conv(x, W_eff) + bias;  z = v > 0 ? v : slope[k] * v;  y = z + residual
+ * -- the residual is added AFTER the PReLU (unlike cpg_conv2d_fwd_bn_eval_add's tail).  The product is rounded, then selected, then the
+ * sum is rounded: bit for bit what cpg_conv2d_fwd_bn_eval with the identity BatchNorm followed by cpg_prelu_fwd computes.
+ * slope: n_slopes = K values (one per output channel) or 1 (shared); NULL or another count: CPG_E_INVALID.  bias and residual may be
+ * NULL; residual is dense NCHW, shaped like y, and must not overlap y.
+ * Classes, by the route cpg_conv2d_fwd takes: 3x3 s1 p1 with or without a residual -- the launch plan (kernel, tile, workspace layout),
+ * the dead-channel skip and skip_stats of cpg_conv2d_fwd_bn_eval for the same descriptor and option table; a block with no live output
+ * channel writes prelu(bias) + residual -- and 3x3 s2 p1 without a residual (no skip: skip_stats receives {0, 0}).  Everything else
+ * (pointwise, generic, grouped descriptors, a residual on the strided class, the channel-split 14 x 14 tile of CPG_C3_FORCE=8) answers 0
+ * from cpg_conv2d_fwd_prelu_eval_supported(desc, with_residual) -- the planner's answer, no launch code runs for it -- and
+ * CPG_E_UNSUPPORTED from the call, before anything is launched: y is not touched.  workspace: cpg_conv2d_workspace_bytes(desc).
+ * No gradient counterpart.  Callers probe for the symbols; CPG_ABI_VERSION is unchanged. */
+int32_t cpg_conv2d_fwd_prelu_eval_supported(const cpg_conv_desc *desc, int32_t with_residual);
+int cpg_conv2d_fwd_prelu_eval(const cpg_conv_desc *desc, const float *x, const float *w, const float *piggymask, float threshold,
+                              const float *bias, const float *slope, int32_t n_slopes, const float *residual, float *y,
+                              int32_t *skip_stats, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- OPT-IN bf16 MFMA path (north_star: "MFMA fp32/bf16 GEMM") of the 3x3 / stride 1 / pad 1 convolution ----
  * Same contraction as cpg_conv2d_fwd / cpg_conv2d_dgrad with the operands (activations, effective weights W * bin(pm))
  * rounded to bf16 on their way into LDS, exact products, fp32 accumulation (v_mfma_f32_32x32x16_bf16) -- the arithmetic of

@@ -110,6 +110,7 @@ def planner_digest():
               [(getattr(lib, n), ()) for n in ('cpg_conv2d_bnstats_tiles', 'cpg_conv2d_dgrad_bnbwd_tiles', 'cpg_conv2d_dgrad_add_supported',
                                                'cpg_conv2d_fwd_bn_eval_supported', 'cpg_conv2d_fwd_bn_eval_add_supported',
                                                'cpg_conv2d_wgrad_rider_supported')] + \
+              [(lib.cpg_conv2d_fwd_prelu_eval_supported, (r,)) for r in range(2)] + \
               [(lib.cpg_conv2d_pack_bytes, (p,)) for p in range(3)] + \
               [(getattr(lib, n), ()) for n in ('cpg_conv2d_bf16_supported', 'cpg_conv2d_bf16_workspace_bytes', 'cpg_conv2d_wgrad_bf16_supported',
                                                'cpg_conv2d_wgrad_bf16_workspace_bytes', 'cpg_stem_bn_supported', 'cpg_stem_bn_tiles',

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Inference forward of a residual topology with fused_bn.FUSE_EVAL_BLOCKS on against off (profiles/resnet_eval_fuse.md).
+"""Inference forward of a residual topology with its fused_bn switch on against off: FUSE_EVAL_BLOCKS for the ResNets
+(profiles/resnet_eval_fuse.md), FUSE_EVAL_PRELU for --arch spherenet20 (profiles/spherenet_eval_fuse.md; 112 x 112).
 
 Full-width ResNet-50 (or --arch), model.eval() under torch.no_grad() at 224 x 224 -- Manager.validate's forward.  Both arms run in ONE
 process, alternating window by window after both are warmed, so clock and allocator state are shared; a window is --forwards forwards
@@ -7,7 +8,9 @@ between two device events.  Per batch size one line, mean +- sample sd (min - ma
 line with everything, plus the activation bytes per image each arm moves, computed from the layer shapes alone:
   off  every conv reads its input and writes its raw output; the BatchNorm pass behind it reads that back (+ the residual, in a block
        tail) and writes the activation;
-  on   every conv behind the stem reads its input (+ the residual) and writes the activation."""
+  on   every conv behind the stem reads its input (+ the residual) and writes the activation.
+SphereNet-20: "the pass behind it" is the PReLU pass (+ the unit's residual in the second pair of a unit); conv1_1 (3 input channels) has
+no fused epilogue and runs conv + PReLU pass in both arms."""
 import argparse
 import json
 import os
@@ -49,29 +52,57 @@ def byte_account(net, size):
     return {'off': 4 * off, 'on': 4 * on}
 
 
+def byte_account_sphere(net, size):
+    """The same account for SphereNet-20: conv -> PReLU pairs, the second pair of a residual unit also reads the unit's input."""
+    shapes = []
+    hooks = [m.register_forward_hook(lambda mod, inp, out, name=name: shapes.append((name, inp[0].numel(), out.numel())))
+             for name, m in net.named_modules() if isinstance(m, nl.SharableConv2d)]
+    was = getattr(fused_bn, 'FUSE_EVAL_PRELU', False)
+    fused_bn.FUSE_EVAL_PRELU = False            # (the hooks see the conv modules' own forward)
+    try:
+        with torch.no_grad():
+            net(torch.zeros(1, 3, size, size, device=next(net.parameters()).device))
+    finally:
+        fused_bn.FUSE_EVAL_PRELU = was
+        for h in hooks:
+            h.remove()
+    off = on = 0
+    for name, n_in, n_out in shapes:
+        i = int(name.rsplit('_', 1)[1])
+        res = n_out if i >= 3 and i % 2 == 1 else 0          # conv{s}_3, _5, ...: the unit's second pair
+        pair = (n_in + n_out) + (n_out + res + n_out)
+        off += pair
+        on += pair if name == 'conv1_1' else n_in + res + n_out
+    return {'off': 4 * off, 'on': 4 * on}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--arch', default='resnet50')
     ap.add_argument('--batches', type=int, nargs='+', default=[100, 256])
-    ap.add_argument('--size', type=int, default=224)
+    ap.add_argument('--size', type=int, default=None, help='default: 224, spherenet20: 112')
     ap.add_argument('--forwards', type=int, default=10, help='forwards per timed window')
     ap.add_argument('--windows', type=int, default=12, help='windows per arm')
     ap.add_argument('--warmup', type=int, default=5, help='forwards per arm before the first window')
     a = ap.parse_args()
+    sphere = a.arch.startswith('spherenet')
+    SWITCH = 'FUSE_EVAL_PRELU' if sphere else 'FUSE_EVAL_BLOCKS'
+    if a.size is None:
+        a.size = 112 if sphere else 224
     dev = 'cuda:0'
     torch.manual_seed(1)
     net = getattr(M, a.arch)(dataset_history=[], dataset2num_classes={}, network_width_multiplier=1.0, shared_layer_info={})
     net.add_dataset('t', 10)
     net.set_dataset('t')
     net = net.to(dev).eval()
-    out = {'arch': a.arch, 'size': a.size, 'forwards_per_window': a.forwards, 'windows_per_arm': a.windows, 'batches': {},
-           'activation_bytes_per_image': byte_account(net, a.size)}
+    out = {'arch': a.arch, 'size': a.size, 'switch': SWITCH, 'forwards_per_window': a.forwards, 'windows_per_arm': a.windows, 'batches': {},
+           'activation_bytes_per_image': (byte_account_sphere if sphere else byte_account)(net, a.size)}
 
     def forward(x, switch):
-        fused_bn.FUSE_EVAL_BLOCKS = switch
+        setattr(fused_bn, SWITCH, switch)
         with torch.no_grad():
             return net(x)
-    default = fused_bn.FUSE_EVAL_BLOCKS
+    default = getattr(fused_bn, SWITCH, None)     # (None: a tree without the switch -- both arms then run the one path it has)
     try:
         for batch in a.batches:
             x = torch.randn(batch, 3, a.size, a.size, device=dev)
@@ -94,15 +125,18 @@ def main():
                 v = ms[switch]
                 row[label] = {'mean_ms': round(statistics.mean(v), 4), 'sd_ms': round(statistics.stdev(v), 4), 'min_ms': round(min(v), 4),
                               'max_ms': round(max(v), 4)}
-                print('%s batch %d FUSE_EVAL_BLOCKS %-3s: %.3f +- %.3f ms per forward (%.3f - %.3f), %.0f img/s' % (
-                    a.arch, batch, label, row[label]['mean_ms'], row[label]['sd_ms'], row[label]['min_ms'], row[label]['max_ms'],
+                print('%s batch %d %s %-3s: %.3f +- %.3f ms per forward (%.3f - %.3f), %.0f img/s' % (
+                    a.arch, batch, SWITCH, label, row[label]['mean_ms'], row[label]['sd_ms'], row[label]['min_ms'], row[label]['max_ms'],
                     batch / row[label]['mean_ms'] * 1e3))
             gain = row['off']['mean_ms'] - row['on']['mean_ms']
             row['gain_ms'] = round(gain, 4)
             row['gain_over_2sd'] = bool(gain > 2 * max(row['on']['sd_ms'], row['off']['sd_ms']))
             out['batches'][str(batch)] = row
     finally:
-        fused_bn.FUSE_EVAL_BLOCKS = default
+        if default is None:
+            delattr(fused_bn, SWITCH)
+        else:
+            setattr(fused_bn, SWITCH, default)
     print(json.dumps(out, sort_keys=True))
 
 
