@@ -215,7 +215,7 @@ __global__ __launch_bounds__(kThreads) void k_bn_apply(const float *__restrict__
                     v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
                 }
                 if (RELU) {
-                    v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+                    v.x = relu_keep(v.x); v.y = relu_keep(v.y); v.z = relu_keep(v.z); v.w = relu_keep(v.w);
                 }
                 reinterpret_cast<float4 *>(q)[i] = v;
                 if (mask != nullptr)
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(kThreads) void k_bn_apply(const float *__restrict__
             for (int i = gl; i < d.HW; i += GROUP) {
                 float v = ch.affine(p[i]);
                 if (res != nullptr) v += res[pl * d.HW + i];
-                q[i] = RELU ? fmaxf(v, 0.f) : v;
+                q[i] = RELU ? relu_keep(v) : v;
             }
         }
     });
@@ -698,7 +698,7 @@ __device__ __forceinline__ int win_argmax(const float (&y)[4]) {
     int idx = 0;
 #pragma unroll
     for (int k = 1; k < 4; ++k)
-        if (y[k] > y[idx]) idx = k;      // strict: first maximum wins, as torch's max_pool2d
+        if (y[k] > y[idx] || y[k] != y[k]) idx = k;      // strict: first maximum wins, and a NaN wins and stays, as torch's max_pool2d
     return idx;
 }
 
@@ -731,10 +731,8 @@ __global__ __launch_bounds__(kThreads) void k_bnp_apply(const float *__restrict_
         for (int i = gl; i < p.wins; i += GROUP) {
             const int pr = i / p.OW, pc = i - pr * p.OW;
             const Win w = load_win(plane, p.W, pr, pc);
-            float best = 0.0f;                       // ReLU floor: the maximum of the four relu(bn(x))
-#pragma unroll
-            for (int k = 0; k < 4; ++k) best = fmaxf(best, ch.affine(w.v[k]));
-            out[i] = best;
+            // the maximum of the four bn(x), then the ReLU (a NaN among them stays): two levels of independent maxima
+            out[i] = relu_keep(max_keep(max_keep(ch.affine(w.v[0]), ch.affine(w.v[1])), max_keep(ch.affine(w.v[2]), ch.affine(w.v[3]))));
         }
     });
 }

@@ -475,7 +475,7 @@ __global__ __launch_bounds__(256, Cfg::MINW) void k_c3_fwd(C3Geom g, const float
                 for (int e = 0; e < 16; ++e) {
                     is[e] = 1.0f / sqrtf(is[e] + bn.eps);
                     float v = ((acc[fm][fn][e] + bv[e]) - mu[e]) * is[e] * ga[e] + be[e];
-                    if (bn.relu) v = fmaxf(v, 0.0f);
+                    if (bn.relu) v = relu_keep(v);
                     acc[fm][fn][e] = v;
                     bv[e] = 0.0f;
                 }

@@ -300,7 +300,7 @@ void k_stem_fwd(StemGeom g, const float *__restrict__ x, const float *__restrict
                         s2[e] = fmaf(vm, vm, s2[e]);
                     }
                     if constexpr (MODE == ST_BN_RELU) {                    // bn_affine of bn_kernels.hip, then the ReLU
-                        const float z = fmaxf((v - cm[e]) * cis[e] * cga[e] + cbe[e], 0.0f);
+                        const float z = relu_keep((v - cm[e]) * cis[e] * cga[e] + cbe[e]);
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, z), srd_y, voff_of(mb, e), cu * HW4, 0);
                     }
                     if constexpr (MODE >= ST_BWD_REDUCE) {

@@ -917,7 +917,7 @@ void k_wg1(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
             const float mu = bn.mean[cc], is = 1.0f / sqrtf(bn.var[cc] + bn.eps), ga = bn.gamma[cc], be = bn.beta[cc];
             v00 = (v00 - mu) * is * ga + be, v01 = (v01 - mu) * is * ga + be;
             v10 = (v10 - mu) * is * ga + be, v11 = (v11 - mu) * is * ga + be;
-            if (bn.relu) v00 = fmaxf(v00, 0.0f), v01 = fmaxf(v01, 0.0f), v10 = fmaxf(v10, 0.0f), v11 = fmaxf(v11, 0.0f);
+            if (bn.relu) v00 = relu_keep(v00), v01 = relu_keep(v01), v10 = relu_keep(v10), v11 = relu_keep(v11);
         }
         if (tv && co < g.M) {
             f32x2 o;
@@ -1197,7 +1197,7 @@ void k_wg2(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
             const int cc = co < g.M ? co : 0;
             const float mu = bn.mean[cc], is = 1.0f / sqrtf(bn.var[cc] + bn.eps), ga = bn.gamma[cc], be = bn.beta[cc];
             v0 = (v0 - mu) * is * ga + be, v1 = (v1 - mu) * is * ga + be;
-            if (bn.relu) v0 = fmaxf(v0, 0.0f), v1 = fmaxf(v1, 0.0f);
+            if (bn.relu) v0 = relu_keep(v0), v1 = relu_keep(v1);
         }
         if (tv && co < g.M) {
             f32x2 o;
@@ -1781,10 +1781,10 @@ void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
             const int cc = co < g.M ? co : 0;
             const float mu = bn.mean[cc], is = 1.0f / sqrtf(bn.var[cc] + bn.eps), ga = bn.gamma[cc], be = bn.beta[cc];
             v0 = (v0 - mu) * is * ga + be, v1 = (v1 - mu) * is * ga + be;
-            if (bn.relu) v0 = fmaxf(v0, 0.0f), v1 = fmaxf(v1, 0.0f);
+            if (bn.relu) v0 = relu_keep(v0), v1 = relu_keep(v1);
         }
         if constexpr (PMAX)                    // this wave's row maximum, into the slot `got` came from (see PMAX)
-            xch[((((ph ^ 1) * 2 + kq) * 16 + e) * 64 + lane) * 2] = fmaxf(v0, v1);
+            xch[((((ph ^ 1) * 2 + kq) * 16 + e) * 64 + lane) * 2] = max_keep(v0, v1);
         if constexpr (FAST) {
             f32x2 o;
             o[0] = v0, o[1] = v1;
@@ -1848,7 +1848,7 @@ void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const float a = rowmax[e * 64 * 2], b = rowmax[(2 * 16 + e) * 64 * 2];      // left by wave 1 / by wave 0
-            if (tg < ttot) ebase[eoff + (unsigned)esoff] = fmaxf(a, b);
+            if (tg < ttot) ebase[eoff + (unsigned)esoff] = max_keep(a, b);
             esoff += (e & 3) == 3 ? 5 * timg1 : timg1;
             asm volatile("" : "+s"(esoff));
         }
@@ -1893,7 +1893,7 @@ __global__ __launch_bounds__(256) void k_wg_tail_reduce(WgGeom g, const float *_
                 a0[0] += v0[0], a0[1] += v0[1], a1[0] += v1[0], a1[1] += v1[1];
             }
             if constexpr (PMAX) {
-                const_cast<float *>(addend)[((int64_t)n * g.M + m) * g.tiles_img + r] = fmaxf(fmaxf(a0[0], a0[1]), fmaxf(a1[0], a1[1]));
+                const_cast<float *>(addend)[((int64_t)n * g.M + m) * g.tiles_img + r] = max_keep(max_keep(a0[0], a0[1]), max_keep(a1[0], a1[1]));
             } else if (addend != nullptr) {                          // (the fused skip gradient of an input-gradient launch: k_wg3<.., ADD>)
                 const f32x2 d0 = *reinterpret_cast<const f32x2 *>(addend + off), d1 = *reinterpret_cast<const f32x2 *>(addend + off + g.W);
                 a0[0] += d0[0], a0[1] += d0[1], a1[0] += d1[0], a1[1] += d1[1];

@@ -140,8 +140,14 @@ __device__ __forceinline__ float bn_xhat(float x, float mean, float invstd) { re
 __device__ __forceinline__ float bn_affine(float x, float mean, float invstd, float gamma, float beta) {
     return (x - mean) * invstd * gamma + beta;
 }
+// The ReLU and the maximum of every fused activation, ONE definition each.  Both KEEP a NaN, as torch.relu and max_pool2d do (fmaxf
+// returns the other operand, so fmaxf(v, 0) turned the NaN of an overflowed network into a clean 0): relu_keep(NaN) = NaN, max_keep
+// = NaN as soon as either operand is one.  On numbers they are fmaxf up to the sign of a zero.  include/cpg_hip.h, "Non-finite
+// values, zeros and ties".
+__device__ __forceinline__ float relu_keep(float v) { return v < 0.f ? 0.f : v; }
+__device__ __forceinline__ float max_keep(float a, float b) { return __builtin_isunordered(a, b) ? __builtin_nanf("") : fmaxf(a, b); }
 __device__ __forceinline__ float bn_relu_affine(float x, float mean, float invstd, float gamma, float beta) {
-    return fmaxf(bn_affine(x, mean, invstd, gamma, beta), 0.f);
+    return relu_keep(bn_affine(x, mean, invstd, gamma, beta));
 }
 template <bool RELU, bool TRAIN>
 __device__ __forceinline__ float bn_bwd_apply_one(float xv, float gv, float m, float is, float ga, float be, float mg, float mgx, float scale) {

@@ -424,7 +424,7 @@ __global__ __launch_bounds__(256, Cfg::MINW) void k_pw(PwGeom g, const float *__
                     if constexpr (BNE) {
                         v = fmaf(v, ss[r >> 1][2 * (r & 1)], ss[r >> 1][2 * (r & 1) + 1]);
                         if (ADD) v += av[e];
-                        if (bn.relu) v = fmaxf(v, 0.0f);
+                        if (bn.relu) v = relu_keep(v);
                     }
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), srd_y, voff, r * plane4, 0);
                     if (STATS) {

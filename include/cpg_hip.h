@@ -424,7 +424,19 @@ int cpg_bn_stats_finalize_count(const float *stats, int32_t tiles, int32_t N, in
  * tiles; a block also spans a pixel tile, so the count is a diagnostic, not a channel count)}; {0, 0} with CPG_NO_DEAD_SKIP.
  * One deliberate difference from the reference: a NaN or Inf in an input channel past the last live chunk, or in any input of an
  * output block with no live weight, does not reach the output (that work is skipped; the reference computes 0 * Inf = NaN).
- * CPG_NO_DEAD_SKIP=1 restores the propagation; skipped work otherwise only ever drops exact zeros. */
+ * CPG_NO_DEAD_SKIP=1 restores the propagation; skipped work otherwise only ever drops exact zeros.
+ *
+ * Non-finite values, zeros and ties.  Apart from that skip, every fused activation keeps what torch.relu, max_pool2d and F.prelu keep:
+ * the ReLU of a NaN is a NaN and a maximum over a window that holds a NaN is a NaN (relu_keep / max_keep of csrc/cpg_common.h -- ONE
+ * definition each, used by the BatchNorm passes, the pooled passes, the fused stem, the inference epilogues below and the window
+ * maxima of cpg_conv2d_fwd_attach_pool_max), +Inf and -Inf come out where and as torch puts them, and in training mode one NaN makes
+ * its channel's batch and running statistics -- and with them that channel, and no other -- NaN.  A network whose activations have
+ * overflowed therefore shows a NaN loss on the first bad step, fused or not.  Ties: a pooled gradient goes to the FIRST maximum of its
+ * window in row-major order (MaxPool2d(2, 2) and the overlapping windows of MaxPool2d(3, 2, 1) alike), a NaN counting as the maximum;
+ * relu'(0) = 0, so a gamma = 0, beta = 0 channel passes nothing back.  The signs of zeros are not specified (relu_keep(-0) = -0).
+ * The one difference in the BACKWARD passes: torch's threshold_backward lets gy through where the activation is NaN; these kernels
+ * mask by `activation > 0`, which is false for a NaN, so they pass 0 there -- gradients at, and parameter gradients summed over, a
+ * non-finite activation are not the reference's.  tests/test_special_values_gpu.py holds all of this to the stock modules in fp64. */
 int32_t cpg_conv2d_fwd_bn_eval_supported(const cpg_conv_desc *desc);
 int cpg_conv2d_fwd_bn_eval(const cpg_conv_desc *desc, const float *x, const float *w, const float *piggymask, float threshold,
                            const float *bias, const float *gamma, const float *beta, const float *running_mean,

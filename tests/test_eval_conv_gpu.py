@@ -308,9 +308,10 @@ def test_nonfinite_inputs_in_skipped_work_do_not_propagate(cid, libopt):
         assert bool(torch.isfinite(y).all()), (cid, relu)
         assert bool(((y.double() - ref).abs() <= E.GAMMA[fam] * conv_term + shift_term).all()), (cid, relu)
     libopt.set('CPG_NO_DEAD_SKIP', 1)
-    rc, y_full, _ = run_eval(_dev(xn), _dev(w), _dev(pm), _dev(b), bnd, 0)      # (relu = fmaxf(v, 0) would turn NaN into 0)
+    for relu in (0, 1):                         # (the epilogue's ReLU keeps a NaN, as torch.relu does)
+        rc, y_full, _ = run_eval(_dev(xn), _dev(w), _dev(pm), _dev(b), bnd, relu)
+        assert rc == 0 and bool(torch.isnan(y_full).any()), (cid, relu)
     libopt.set('CPG_NO_DEAD_SKIP', None)
-    assert rc == 0 and bool(torch.isnan(y_full).any()), cid
     # a NaN in a LIVE chunk reaches the live channels either way, but never the dead blocks while the skip is on
     xl = x.clone()
     xl[0, 0, H // 2, W // 2] = float('nan')
