@@ -64,13 +64,14 @@ __device__ __forceinline__ f32x4 ld_sv4(const float *sbase, unsigned byte_off) {
 // conv output is exactly 0, the epilogue still writes bias / BatchNorm of 0), and every block stops after the last live
 // input-channel chunk.  Whole channels die when a model that was GROWN for later tasks serves an earlier, narrower task
 // after apply_mask (every slot with owner > task is zero): the kernel then does the work of the cropped model.
-// The PReLU inference epilogue (k_c3_fwd<.., PRE>: y = prelu(acc + bias) [+ residual], cpg_common.h's prelu_one / prelu_sum) travels in the
-// same struct, so that no existing instance's arguments change: gamma = the slopes, relu = 1 for one slope per channel (0: one shared),
-// beta = the residual, dense and shaped like y, or null; mean / var unused.  `live` and the skip are the same.
+// One parameter block for both inference epilogues (cpg::EvalEpilogue, filled by c3_epilogue): the BatchNorm instances read the first name
+// of each pair, the PRE instances (y = prelu(acc + bias) [+ residual], cpg_common.h's prelu_one / prelu_sum) the second; `live` is common.
 struct C3BnEval {
-    const float *gamma, *beta, *mean, *var;
+    union { const float *gamma, *slope; };
+    union { const float *beta, *residual; };
+    const float *mean, *var;
     float eps;
-    int relu;
+    union { int relu, per_channel; };
     int *live;
 };
 
@@ -442,11 +443,11 @@ __global__ __launch_bounds__(256, Cfg::MINW) void k_c3_fwd(C3Geom g, const float
             }
             if constexpr (PRE) {                                            // inference PReLU (+ the unit's residual) in the epilogue (see C3BnEval)
                 float sl[16], rv[16];
-                const float *rin = bn.beta != nullptr ? bn.beta + (int64_t)(n + img) * g.M * HWo : nullptr;
+                const float *rin = bn.residual != nullptr ? bn.residual + (int64_t)(n + img) * g.M * HWo : nullptr;
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int co = m0 + (wm * Cfg::FM + fm) * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                    sl[e] = bn.gamma[bn.relu && co < g.M ? co : 0];
+                    sl[e] = bn.slope[bn.per_channel && co < g.M ? co : 0];
                     rv[e] = 0.0f;
                 }
                 if (rin != nullptr) {                   // one uniform branch per fragment, 16 loads issued together
@@ -1104,11 +1105,24 @@ inline size_t pack_bytes(int c_read, int m) { return (pack_floats(c_read, m) + l
 // What a forward / input-gradient call does besides y = conv(x).  Filled field by field; everything is optional.
 struct C3Extra {
     float *stats = nullptr;         // forward: [m][tiles][2] BatchNorm partial sums of y; with bb: the BatchNorm-backward partial sums
-    const C3BnEval *bn = nullptr;   // forward: eval-mode BatchNorm (+ ReLU) epilogue (its `live` is filled in from the workspace here)
-    bool live = false;              // ... with the dead-channel skip: the pack writes the workspace's liveness words, the kernel reads them
-    bool prelu = false;             // ... bn carries the PReLU inference epilogue instead (see C3BnEval): the PRE instances
+    const cpg::EvalEpilogue *eval = nullptr;    // forward: the inference epilogue (its kind picks the BatchNorm or the PRE instances)
+    const char *what = nullptr;     // ... and the public entry point that asked for it, for messages
+    bool skip = false;              // ... with the dead-channel skip: the pack writes the workspace's liveness words, the kernel reads them
+    int *live = nullptr;            // ... those words (run_fwd finds them in the workspace)
     const C3BnBwd *bb = nullptr;    // input gradient: BatchNorm-backward reduction of the layer below in the epilogue
 };
+
+// The kernels' parameter block from the descriptor (null: no inference epilogue) -- the one place that knows which name of a pair each kind fills.
+inline C3BnEval c3_epilogue(const cpg::EvalEpilogue *ep, int *live) {
+    C3BnEval bn{};
+    if (ep == nullptr) return bn;
+    if (ep->kind == cpg::EvalEpilogue::PRELU)
+        bn.slope = ep->slope, bn.residual = ep->residual, bn.per_channel = ep->per_channel;
+    else
+        bn.gamma = ep->gamma, bn.beta = ep->beta, bn.mean = ep->mean, bn.var = ep->var, bn.eps = ep->eps, bn.relu = ep->relu;
+    bn.live = live;
+    return bn;
+}
 
 // ... the same as far as the dispatch depends on it
 enum C3Want { C3_PLAIN, C3_STATS, C3_BN_EVAL, C3_BN_BWD };
@@ -1143,9 +1157,9 @@ C3Plan c3_direct(C3Tile tile, int ksplit, int N, int M, int OH, int OW) {
 template <class Cfg>
 int launch_fwd(C3Geom g, const float *x, const float *wp, const float *bias, float *y, hipStream_t stream, const char *what, const C3Extra &ex) {
     float *const stats = ex.stats;
-    const C3BnEval *const bnp = ex.bn;
+    const cpg::EvalEpilogue *const ep = ex.eval;
     const C3BnBwd *const bbp = ex.bb;
-    const C3BnEval bn = bnp ? *bnp : C3BnEval{nullptr, nullptr, nullptr, nullptr, 0.0f, 0, nullptr};
+    const C3BnEval bn = c3_epilogue(ep, ex.live);
     const C3BnBwd bb = bbp ? *bbp : C3BnBwd{nullptr, nullptr, nullptr, nullptr, nullptr};
     g.tiles_x = (g.OW + Cfg::TW - 1) / Cfg::TW;
     g.tiles_y = (g.OH + Cfg::TH - 1) / Cfg::TH;
@@ -1153,7 +1167,7 @@ int launch_fwd(C3Geom g, const float *x, const float *wp, const float *bias, flo
     const int64_t blocks = c3_blocks<Cfg>(g.N, g.M, g.OH, g.OW);
     if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "conv3x3: grid too large");
     if (g.ksplit > 1) {
-        if (stats != nullptr || bnp != nullptr || bbp != nullptr) return fail(CPG_E_UNSUPPORTED, "conv3x3: no fused epilogue on channel-split tiles");
+        if (stats != nullptr || ep != nullptr || bbp != nullptr) return fail(CPG_E_UNSUPPORTED, "conv3x3: no fused epilogue on channel-split tiles");
         hipError_t e = hipMemsetAsync(y, 0, (size_t)g.N * g.M * g.OH * g.OW * sizeof(float), stream);
         if (e != hipSuccess) return hip_status(e, what);
         if (g.dgrad)
@@ -1170,7 +1184,7 @@ int launch_fwd(C3Geom g, const float *x, const float *wp, const float *bias, flo
         hipLaunchKernelGGL((k_c3_fwd<Cfg, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, nullptr, bn, bb);
     else if (stats != nullptr)
         hipLaunchKernelGGL((k_c3_fwd<Cfg, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, stats, bn, bb);
-    else if (ex.prelu && bnp != nullptr)
+    else if (ep != nullptr && ep->kind == cpg::EvalEpilogue::PRELU)
         hipLaunchKernelGGL((k_c3_fwd<Cfg, false, false, false, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, nullptr, bn, bb);
     else
         hipLaunchKernelGGL((k_c3_fwd<Cfg, false>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, nullptr, bn, bb);
@@ -1230,21 +1244,18 @@ C3Plan plan_fwd(bool dgrad, int N, int c_read, int m, int H, int W, C3Want want)
 int run_fwd(bool dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
             float thr, const float *bias, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const C3Extra &extra = C3Extra()) {
     const char *what = dgrad ? "cpg_conv2d_dgrad(3x3)" : "cpg_conv2d_fwd(3x3)";
-    C3Extra ex = extra;             // (ex.bn is redirected to a copy with the workspace's liveness words below)
-    const C3Plan plan = plan_fwd(dgrad, N, c_read, m, H, W, ex.bb ? C3_BN_BWD : ex.bn ? C3_BN_EVAL : ex.stats ? C3_STATS : C3_PLAIN);
+    C3Extra ex = extra;             // (ex.live is filled in below)
+    const C3Plan plan = plan_fwd(dgrad, N, c_read, m, H, W, ex.bb ? C3_BN_BWD : ex.eval ? C3_BN_EVAL : ex.stats ? C3_STATS : C3_PLAIN);
     if (plan.route == C3_WINO)
         return cpg_conv3x3_wino_run(dgrad ? 1 : 0, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, ex.stats, ws, ws_bytes, stream);
     // Workspace layout of the Winograd inference forward:
-    // [the direct kernels' packed-weight region (unused) | liveness words, where cpg_conv3x3_fwd_bn_eval looks for them | U]
+    // [the direct kernels' packed-weight region (unused) | liveness words, where cpg_conv3x3_fwd_eval looks for them | U]
     if (plan.route == C3_WINO_EVAL) {
         const size_t off = (pack_bytes(c_read, m) + 15) / 16 * 16;
         if (ws == nullptr || ws_bytes < off) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, off);
-        int *live = ex.live ? reinterpret_cast<int *>((float *)ws + pack_floats(c_read, m)) : nullptr;
-        if (ex.prelu)
-            return cpg_conv3x3_wino_run_prelu_eval(N, c_read, m, H, W, x, w, pm, thr, bias, ex.bn->gamma, ex.bn->relu, ex.bn->beta, live, live_words(c_read, m), y,
-                                                   (char *)ws + off, ws_bytes - off, stream);
-        return cpg_conv3x3_wino_run_bn_eval(N, c_read, m, H, W, x, w, pm, thr, bias, ex.bn->gamma, ex.bn->beta, ex.bn->mean, ex.bn->var, ex.bn->eps, ex.bn->relu,
-                                            live, live_words(c_read, m), y, (char *)ws + off, ws_bytes - off, stream);
+        int *live = ex.skip ? reinterpret_cast<int *>((float *)ws + pack_floats(c_read, m)) : nullptr;
+        return cpg_conv3x3_wino_run_eval(N, c_read, m, H, W, x, w, pm, thr, bias, *ex.eval, live, live_words(c_read, m), y, (char *)ws + off,
+                                         ws_bytes - off, stream, ex.what);
     }
     if (plan.route == C3_STEM) return cpg_conv3x3_stem_run(N, c_read, m, H, W, x, w, pm, thr, bias, y, ex.stats, stream);
     float *wp = (float *)ws;
@@ -1252,20 +1263,13 @@ int run_fwd(bool dgrad, int N, int c_read, int m, int H, int W, int K, int C, co
     const size_t need = pack_bytes(c_read, m);
     if (ws == nullptr || ws_bytes < need) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
     CPG_REQUIRE((((uintptr_t)ws) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
-    int *live = nullptr;
-    if (ex.bn != nullptr && ex.live) {          // (the liveness words live in the workspace, behind the packed weights)
-        live = reinterpret_cast<int *>(wp + pack_floats(c_read, m));
-        hipError_t e = hipMemsetAsync(live, 0, live_words(c_read, m) * sizeof(int), stream);
+    if (ex.eval != nullptr && ex.skip) {        // (the liveness words live in the workspace, behind the packed weights)
+        ex.live = reinterpret_cast<int *>(wp + pack_floats(c_read, m));
+        hipError_t e = hipMemsetAsync(ex.live, 0, live_words(c_read, m) * sizeof(int), stream);
         if (e != hipSuccess) return hip_status(e, what);
     }
     hipLaunchKernelGGL(k_c3_pack, dim3(stream_grid((int64_t)rows_c * 9 * Mp, 256)), dim3(256), 0, stream, w, pm, thr, wp, K, C,
-                       rows_c, Mp, dgrad ? 1 : 0, live);
-    C3BnEval bn_local;
-    if (ex.bn != nullptr) {
-        bn_local = *ex.bn;
-        bn_local.live = live;
-        ex.bn = &bn_local;
-    }
+                       rows_c, Mp, dgrad ? 1 : 0, ex.live);
     C3Geom g{N, c_read, H, W, m, Mp, 0, 0, 0, H, W, dgrad ? 1 : 0, plan.ksplit};
     switch (plan.tile) {
         case TILE_M128: return launch_fwd<CfgM128>(g, x, wp, bias, y, stream, what, ex);
@@ -1314,14 +1318,30 @@ int cpg_conv3x3_fwd_bnstats(const cpg_conv_desc *d, const float *x, const float 
     return run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, x, w, pm, thr, bias, y, ws, ws_bytes, stream, ex);
 }
 
-// the inference forward: bn's epilogue (eval-mode BatchNorm, or the PReLU one) and the dead-channel skip; skip_stats (may be null): 2 device words
-static int run_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, const C3BnEval &bn,
-                        bool prelu, float *y, int32_t *skip_stats, void *ws, size_t ws_bytes, hipStream_t stream, const char *what) {
+// 1: the inference epilogues (cpg_conv3x3_fwd_eval) have a launch for this shape under the current option table -- the
+// plan of the call itself, asked without running it.  The channel-split 14 x 14 tile (CPG_C3_FORCE=8) has no fused epilogue.
+int cpg_conv3x3_eval_epilogue_ok(const cpg_conv_desc *d) {
+    const C3Plan plan = plan_fwd(false, d->N, d->C, d->K, d->H, d->W, C3_BN_EVAL);
+    if (plan.route == C3_WINO_EVAL) return 1;
+    return plan.route == C3_DIRECT && plan.ksplit == 1 && plan.blocks <= 0x7FFFFFFFll ? 1 : 0;
+}
+
+// the inference forward (Manager.validate's path, SphereNet's units): ep in the epilogue, and the dead-channel skip
+int cpg_conv3x3_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                         const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what) {
+    if (ep.kind == cpg::EvalEpilogue::PRELU) {
+        CPG_REQUIRE(x && w && y && ep.slope, "%s: null pointer", what);
+        if (!cpg_conv3x3_eval_epilogue_ok(d)) return fail(CPG_E_UNSUPPORTED, "%s: no fused epilogue on channel-split tiles", what);
+    } else {
+        CPG_REQUIRE(x && w && y && ep.gamma && ep.beta && ep.mean && ep.var, "%s: null pointer", what);
+        if (ep.residual != nullptr) return fail(CPG_E_UNSUPPORTED, "%s: the 3x3 kernels add no residual behind the BatchNorm", what);
+    }
     const bool skip = !opt_on(OPT_NO_DEAD_SKIP);
+    int32_t *const skip_stats = ep.skip_stats;
     C3Extra ex;
-    ex.bn = &bn;
-    ex.live = skip;
-    ex.prelu = prelu;
+    ex.eval = &ep;
+    ex.what = what;
+    ex.skip = skip;
     int rc = run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, x, w, pm, thr, bias, y, ws, ws_bytes, stream, ex);
     if (rc == CPG_OK && skip_stats != nullptr) {
         // {4 * (input chunks up to the last live one), output blocks skipped}: device-to-device copy of the two words behind live[Mp]
@@ -1335,33 +1355,6 @@ static int run_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, 
         }
     }
     return rc;
-}
-
-// forward with the inference-mode BatchNorm (+ ReLU) that follows the conv folded into the epilogue (Manager.validate's path)
-int cpg_conv3x3_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                            const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu, float *y,
-                            int32_t *skip_stats, void *ws, size_t ws_bytes, hipStream_t stream) {
-    CPG_REQUIRE(x && w && y && gamma && beta && mean && var, "cpg_conv2d_fwd_bn_eval: null pointer");
-    const C3BnEval bn{gamma, beta, mean, var, eps, relu, nullptr};
-    return run_fwd_eval(d, x, w, pm, thr, bias, bn, false, y, skip_stats, ws, ws_bytes, stream, "cpg_conv2d_fwd_bn_eval");
-}
-
-// 1: the inference epilogues (cpg_conv3x3_fwd_bn_eval / _prelu_eval) have a launch for this shape under the current option table -- the
-// plan of the call itself, asked without running it.  The channel-split 14 x 14 tile (CPG_C3_FORCE=8) has no fused epilogue.
-int cpg_conv3x3_eval_epilogue_ok(const cpg_conv_desc *d) {
-    const C3Plan plan = plan_fwd(false, d->N, d->C, d->K, d->H, d->W, C3_BN_EVAL);
-    if (plan.route == C3_WINO_EVAL) return 1;
-    return plan.route == C3_DIRECT && plan.ksplit == 1 && plan.blocks <= 0x7FFFFFFFll ? 1 : 0;
-}
-
-// ... with bias, PReLU and the unit's residual folded in instead: y = prelu(conv + bias) [+ residual], the same plan and the same skip
-int cpg_conv3x3_fwd_prelu_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                               const float *slope, int per_channel, const float *residual, float *y, int32_t *skip_stats, void *ws,
-                               size_t ws_bytes, hipStream_t stream) {
-    CPG_REQUIRE(x && w && y && slope, "cpg_conv2d_fwd_prelu_eval: null pointer");
-    if (!cpg_conv3x3_eval_epilogue_ok(d)) return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_prelu_eval: no fused epilogue on channel-split tiles");
-    const C3BnEval bn{slope, residual, nullptr, nullptr, 0.0f, per_channel, nullptr};
-    return run_fwd_eval(d, x, w, pm, thr, bias, bn, true, y, skip_stats, ws, ws_bytes, stream, "cpg_conv2d_fwd_prelu_eval");
 }
 
 // the packed operand a caller may hand to the forward (dgrad = 0) or the input gradient: the Winograd launch's, where the pass runs there
@@ -1520,7 +1513,8 @@ using S2G128 = C3Cfg<128, 4, 32, 2, 2, 4, 2, 1, 0, 1>;  // anything else
 using S2G64 = C3Cfg<64, 8, 32, 1, 4, 4, 2, 1, 0, 1>;    // ... with <= 64 output channels
 
 template <class Cfg>
-int launch_fwd_s2(C3Geom g, const float *x, const float *wp, const float *bias, float *y, float *stats, const C3BnEval &bn, bool prelu, hipStream_t stream) {
+int launch_fwd_s2(C3Geom g, const float *x, const float *wp, const float *bias, float *y, float *stats, const cpg::EvalEpilogue *ep, hipStream_t stream) {
+    const C3BnEval bn = c3_epilogue(ep, nullptr);      // (no liveness words: the strided tiles skip nothing)
     const C3BnBwd bb{nullptr, nullptr, nullptr, nullptr, nullptr};
     g.tiles_x = (g.OW + Cfg::TW - 1) / Cfg::TW;
     g.tiles_y = (g.OH + Cfg::TH - 1) / Cfg::TH;
@@ -1529,7 +1523,7 @@ int launch_fwd_s2(C3Geom g, const float *x, const float *wp, const float *bias, 
     if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "conv3x3 s2: grid too large");
     if (stats != nullptr)
         hipLaunchKernelGGL((k_c3_fwd<Cfg, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, stats, bn, bb);
-    else if (prelu)
+    else if (ep != nullptr && ep->kind == cpg::EvalEpilogue::PRELU)
         hipLaunchKernelGGL((k_c3_fwd<Cfg, false, false, false, false, true>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, nullptr, bn, bb);
     else
         hipLaunchKernelGGL((k_c3_fwd<Cfg, false>), dim3((unsigned)blocks), dim3(256), 0, stream, g, x, wp, bias, y, nullptr, bn, bb);
@@ -1549,13 +1543,11 @@ C3Plan plan_fwd_s2(const cpg_conv_desc *d) {
     return c3_direct<S2G128>(TILE_S2G128, 1, N, K, OH, OW);
 }
 
-// bn (may be null; not together with stats): the eval-mode BatchNorm (+ ReLU) epilogue, with live == nullptr -- the strided tiles skip nothing;
-// prelu: bn carries the PReLU epilogue instead (see C3BnEval)
+// ep (may be null; not together with stats): the inference epilogue
 int run_fwd_s2(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y, float *stats,
-               const C3BnEval *bnp, void *ws, size_t ws_bytes, hipStream_t stream, bool prelu = false) {
+               const cpg::EvalEpilogue *ep, void *ws, size_t ws_bytes, hipStream_t stream) {
     const char *what = "cpg_conv2d_fwd(3x3 s2)";
-    if (prelu && (bnp == nullptr || stats != nullptr)) return fail(CPG_E_INVALID, "%s: the PReLU epilogue needs its slopes and takes no statistics", what);
-    const C3BnEval bn = bnp ? *bnp : C3BnEval{nullptr, nullptr, nullptr, nullptr, 0.0f, 0, nullptr};
+    if (ep != nullptr && stats != nullptr) return fail(CPG_E_INVALID, "%s: an inference epilogue takes no statistics", what);
     float *wp = (float *)ws;
     const int rows_c = pad_to(d->C, 4), Mp = pad_to(d->K, 128);
     const size_t need = pack_bytes(d->C, d->K);
@@ -1565,11 +1557,11 @@ int run_fwd_s2(const cpg_conv_desc *d, const float *x, const float *w, const flo
                        rows_c, Mp, 0, (int *)nullptr);
     C3Geom g{d->N, d->C, d->H, d->W, d->K, Mp, 0, 0, 0, s2_out(d->H), s2_out(d->W), 0, 1};
     switch (plan_fwd_s2(d).tile) {
-        case TILE_S2P28: return launch_fwd_s2<S2P28>(g, x, wp, bias, y, stats, bn, prelu, stream);
-        case TILE_S2M8: return launch_fwd_s2<S2M8>(g, x, wp, bias, y, stats, bn, prelu, stream);
-        case TILE_S2S16: return launch_fwd_s2<S2S16>(g, x, wp, bias, y, stats, bn, prelu, stream);
-        case TILE_S2G64: return launch_fwd_s2<S2G64>(g, x, wp, bias, y, stats, bn, prelu, stream);
-        case TILE_S2G128: return launch_fwd_s2<S2G128>(g, x, wp, bias, y, stats, bn, prelu, stream);
+        case TILE_S2P28: return launch_fwd_s2<S2P28>(g, x, wp, bias, y, stats, ep, stream);
+        case TILE_S2M8: return launch_fwd_s2<S2M8>(g, x, wp, bias, y, stats, ep, stream);
+        case TILE_S2S16: return launch_fwd_s2<S2S16>(g, x, wp, bias, y, stats, ep, stream);
+        case TILE_S2G64: return launch_fwd_s2<S2G64>(g, x, wp, bias, y, stats, ep, stream);
+        case TILE_S2G128: return launch_fwd_s2<S2G128>(g, x, wp, bias, y, stats, ep, stream);
         default: return fail(CPG_E_INVALID, "%s: not a stride-2 tile", what);
     }
 }
@@ -1612,20 +1604,17 @@ int cpg_conv3x3s2_fwd(const cpg_conv_desc *d, const float *x, const float *w, co
     CPG_REQUIRE(x && w && y, "cpg_conv2d_fwd: null pointer");
     return run_fwd_s2(d, x, w, pm, thr, bias, y, stats, nullptr, ws, ws_bytes, stream);
 }
-int cpg_conv3x3s2_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                              const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu, float *y,
-                              void *ws, size_t ws_bytes, hipStream_t stream) {
-    CPG_REQUIRE(x && w && y && gamma && beta && mean && var, "cpg_conv2d_fwd_bn_eval: null pointer");
-    const C3BnEval bn{gamma, beta, mean, var, eps, relu, nullptr};
-    return run_fwd_s2(d, x, w, pm, thr, bias, y, nullptr, &bn, ws, ws_bytes, stream);
-}
-// ... with bias and PReLU folded in: y = prelu(conv + bias).  No residual: a strided conv opens a stage, nothing of its output's shape exists yet.
-int cpg_conv3x3s2_fwd_prelu_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                                 const float *slope, int per_channel, float *y, void *ws, size_t ws_bytes, hipStream_t stream) {
-    CPG_REQUIRE(x && w && y && slope, "cpg_conv2d_fwd_prelu_eval: null pointer");
-    if (plan_fwd_s2(d).blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_prelu_eval: grid too large");
-    const C3BnEval bn{slope, nullptr, nullptr, nullptr, 0.0f, per_channel, nullptr};
-    return run_fwd_s2(d, x, w, pm, thr, bias, y, nullptr, &bn, ws, ws_bytes, stream, true);
+// ... with ep folded into the epilogue.  No residual: a strided conv opens a stage, nothing of its output's shape exists yet.
+int cpg_conv3x3s2_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                           const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what) {
+    if (ep.residual != nullptr) return fail(CPG_E_UNSUPPORTED, "%s: the strided 3x3 kernels add no residual", what);
+    if (ep.kind == cpg::EvalEpilogue::PRELU) {
+        CPG_REQUIRE(x && w && y && ep.slope, "%s: null pointer", what);
+        if (plan_fwd_s2(d).blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "%s: grid too large", what);
+    } else {
+        CPG_REQUIRE(x && w && y && ep.gamma && ep.beta && ep.mean && ep.var, "%s: null pointer", what);
+    }
+    return run_fwd_s2(d, x, w, pm, thr, bias, y, nullptr, &ep, ws, ws_bytes, stream);
 }
 int cpg_conv3x3s2_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                         size_t ws_bytes, hipStream_t stream) {

@@ -589,15 +589,19 @@ __global__ __launch_bounds__(256) void k_pack_jobs(const PackArgs a, const PackA
 // `live` (may be null) are the flags k_wg1_pack wrote, same layout as k_c3_pack's (live[m]: output channel m has a non-zero
 // weight; live[Mp + 4 + q]: input chunk q has one; live[Mp] receives 4 x the chunks up to the last live one, live[Mp + 1] counts
 // the waves that skipped their MFMA loop).
-// The PReLU inference epilogue (the PRE instances: y = prelu(conv + bias) [+ residual], cpg_common.h's prelu_one / prelu_sum) travels in the
-// same struct, as in conv3x3.hip: gamma = the slopes, relu = 1 for one slope per channel (0: one shared), beta = the residual, dense and
-// shaped like y, or null; mean / var unused.  `live` and the skip are the same.
+// One parameter block for both inference epilogues (cpg::EvalEpilogue, filled by wg_epilogue): the BNE instances read the members, the PRE
+// instances (y = prelu(conv + bias) [+ residual], cpg_common.h's prelu_one / prelu_sum) slope(), residual() and per_channel(); `live`, Mp
+// are common.  (Accessors, where conv3x3.hip's C3BnEval has unions: a read through a union member loses its struct-path alias
+// information, and k_wg3<ODD, PRE> then compiles to other code -- tools/build_digest.py.)
 struct WgBnEval {
     const float *gamma, *beta, *mean, *var;
     float eps;
     int relu;
     int *live;
     int Mp;
+    __host__ __device__ const float *slope() const { return gamma; }
+    __host__ __device__ const float *residual() const { return beta; }
+    __host__ __device__ int per_channel() const { return relu; }
 };
 
 // -DWG_TIMING (development builds only, tools/attic/diag_wg_timing.py): every wave of k_wg1 leaves the constant-clock time of its
@@ -885,8 +889,8 @@ void k_wg1(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
     float s1[16], s2[16];
     // (PRE) the residual, at the store's own address + the uniform distance between the two tensors: nothing new for the compiler to keep
     // per lane across the main loop (this kernel's loop owns all 256 vector registers)
-    const bool has_res = PRE && bn.beta != nullptr;
-    const intptr_t rdelta = has_res ? reinterpret_cast<intptr_t>(bn.beta) - reinterpret_cast<intptr_t>(y) : 0;
+    const bool has_res = PRE && bn.residual() != nullptr;
+    const intptr_t rdelta = has_res ? reinterpret_cast<intptr_t>(bn.residual()) - reinterpret_cast<intptr_t>(y) : 0;
     // hb: with / without a conv bias, decided ONCE outside (the two epilogues are separate code).  With the bias load behind a
     // branch inside the per-channel code the compiler's s_waitcnt vmcnt(0) for it sat in the common path: every channel waited for
     // the previous channel's stores to be acknowledged, 16 round trips = 3.9 us of a 29 us unit on the 64-channel layers
@@ -904,7 +908,7 @@ void k_wg1(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
         float v00 = r_[0][0] + r_[1][0] + r_[2][0] + bv, v01 = r_[0][1] + r_[1][1] + r_[2][1] + bv;
         float v10 = r_[1][0] - r_[2][0] - r_[3][0] + bv, v11 = r_[1][1] - r_[2][1] - r_[3][1] + bv;
         if constexpr (PRE) {                   // y = prelu(conv + bias) [+ residual]
-            const float a = bn.gamma[bn.relu && co < g.M ? co : 0];
+            const float a = bn.slope()[bn.per_channel() && co < g.M ? co : 0];
             v00 = prelu_one(v00, a), v01 = prelu_one(v01, a), v10 = prelu_one(v10, a), v11 = prelu_one(v11, a);
             if (has_res && tv && co < g.M) {
                 const char *rp = reinterpret_cast<const char *>(yout + (int64_t)co * HW) + rdelta;
@@ -1187,10 +1191,10 @@ void k_wg2(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
             v0 += bv, v1 += bv;
         }
         if constexpr (PRE) {                   // y = prelu(conv + bias) [+ residual]
-            const float a = bn.gamma[bn.relu && co < g.M ? co : 0];
+            const float a = bn.slope()[bn.per_channel() && co < g.M ? co : 0];
             v0 = prelu_one(v0, a), v1 = prelu_one(v1, a);
-            if (bn.beta != nullptr && tv && co < g.M) {
-                const f32x2 rr = *reinterpret_cast<const f32x2 *>(bn.beta + (yout - y) + (int64_t)co * HW);
+            if (bn.residual() != nullptr && tv && co < g.M) {
+                const f32x2 rr = *reinterpret_cast<const f32x2 *>(bn.residual() + (yout - y) + (int64_t)co * HW);
                 v0 = prelu_sum(v0, rr[0]), v1 = prelu_sum(v1, rr[1]);
             }
         } else if (BNE) {                      // y = [max(0,] (conv + bias - mean) * invstd * gamma + beta [)]
@@ -1269,7 +1273,7 @@ struct Bop {                                  // k_wg3's B operands of one chann
 // across the stores.  E comes in through the `bias` parameter (such a launch has no bias), as the addend does under ADD.
 // PRE (inference launches, with BNE: the same skip): y = prelu(conv + bias) [+ residual] instead of the BatchNorm expression (see WgBnEval).
 // The residual is fetched as ADD fetches its addend -- on the fast path four channels' worth with the group's exchange reads, at y's own
-// offsets -- but from bn.beta: the bias slot holds the conv's bias here.
+// offsets -- but from bn.residual(): the bias slot holds the conv's bias here.
 template <bool DGRAD, bool STATS, bool BNE = false, bool ODD = false, bool SH = false, bool SPLIT = false, bool ADD = false, bool PMAX = false,
           bool PRE = false>
 __global__ __launch_bounds__(SH ? 256 : 128) __attribute__((amdgpu_waves_per_eu(1, 1)))
@@ -1701,9 +1705,9 @@ void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
     const char *abase = reinterpret_cast<const char *>(bias + (ADD ? (int64_t)n0 * g.M * HW : 0));
     const float *aout = bias + (ADD ? ((int64_t)n * g.M) * HW + (2 * ty + ph) * g.W + 2 * tx : 0);
     // (PRE) the residual at the same offsets as y; null: none (a wave-uniform test)
-    const bool has_res = PRE && bn.beta != nullptr;
-    const char *rbase = reinterpret_cast<const char *>(bn.beta + (has_res ? (int64_t)n0 * g.M * HW : 0));
-    const float *rout = bn.beta + (has_res ? ((int64_t)n * g.M) * HW + (2 * ty + ph) * g.W + 2 * tx : 0);
+    const bool has_res = PRE && bn.residual() != nullptr;
+    const char *rbase = reinterpret_cast<const char *>(bn.residual() + (has_res ? (int64_t)n0 * g.M * HW : 0));
+    const float *rout = bn.residual() + (has_res ? ((int64_t)n * g.M) * HW + (2 * ty + ph) * g.W + 2 * tx : 0);
     const unsigned yoff = (unsigned)(((nrel * g.M + kb * 64 + 4 * lh_e) * HW + (2 * ty + ph) * g.W + 2 * tx) * 4);
     // (the scalar channel offsets are a running sum behind an opaque barrier: as multiples of HW they are invariant in the persistent
     //  loop, the compiler would compute all 32 in front of it and spill scalar registers into vector lanes)
@@ -1763,7 +1767,7 @@ void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
             }
         }
         if constexpr (PRE) {                   // y = prelu(conv + bias) [+ residual]
-            const float a = bn.gamma[bn.relu && co < g.M ? co : 0];
+            const float a = bn.slope()[bn.per_channel() && co < g.M ? co : 0];
             v0 = prelu_one(v0, a), v1 = prelu_one(v1, a);
             if (has_res) {
                 if constexpr (FAST) {
@@ -2142,9 +2146,22 @@ static int wino_run_block(int dgrad, int N, int c_read, int m, int H, int W, int
 
 // y[N][m][H][W] = conv3x3(x[N][c_read][H][W], W .* bin(pm)) (+ bias); dgrad: x = gy, the filter transposed and flipped.
 // w is the layer's [K][C][3][3] weight.  stats (forward only, may be null): [m][tiles][2] partial sums for the BatchNorm.
+// ep (forward only, may be null): the inference epilogue, with live (may be null), the liveness words of its dead-channel skip.
 static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
-                    float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream, const WgBnEval *bne,
-                    const float *addend = nullptr, bool prelu = false);
+                    float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream,
+                    const cpg::EvalEpilogue *ep, const float *addend = nullptr, int *live = nullptr);
+
+// The kernels' parameter block from the descriptor (null: no inference epilogue) -- the one place that knows which name of a pair each kind fills.
+static WgBnEval wg_epilogue(const cpg::EvalEpilogue *ep, int *live, int m) {
+    WgBnEval bn{};
+    if (ep == nullptr) return bn;
+    if (ep->kind == cpg::EvalEpilogue::PRELU)      // (the slots behind slope(), residual() and per_channel())
+        bn.gamma = ep->slope, bn.beta = ep->residual, bn.relu = ep->per_channel ? 1 : 0;
+    else
+        bn.gamma = ep->gamma, bn.beta = ep->beta, bn.mean = ep->mean, bn.var = ep->var, bn.eps = ep->eps, bn.relu = ep->relu;
+    bn.live = live, bn.Mp = pad_to(m, 128);
+    return bn;
+}
 
 extern "C" int cpg_conv3x3_wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x,
                                     const float *w, const float *pm, float thr, const float *bias, float *y, float *stats,
@@ -2176,40 +2193,28 @@ extern "C" int cpg_conv3x3_wino_eval_ok(int N, int c_read, int m, int H, int W) 
     return wino_variant(c_read, m) != WV_BLOCK && cpg_conv3x3_wino_ok(N, c_read, m, H, W);
 }
 
-// forward with eval-mode BatchNorm (+ ReLU) in the epilogue; live (may be null): live_words ints, zeroed here, layout of k_c3_pack
-extern "C" int cpg_conv3x3_wino_run_bn_eval(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr,
-                                            const float *bias, const float *gamma, const float *beta, const float *mean, const float *var,
-                                            float eps, int relu, int *live, size_t live_words, float *y, void *ws, size_t ws_bytes,
-                                            hipStream_t stream) {
+// forward with ep in the epilogue (eval-mode BatchNorm (+ ReLU), or bias, PReLU (+ residual)); live (may be null): live_words ints, zeroed
+// here, layout of k_c3_pack
+int cpg_conv3x3_wino_run_eval(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                              const cpg::EvalEpilogue &ep, int *live, size_t live_words, float *y, void *ws, size_t ws_bytes, hipStream_t stream,
+                              const char *what) {
+    if (ep.kind == cpg::EvalEpilogue::PRELU && ep.slope == nullptr) return fail(CPG_E_INVALID, "%s(winograd): null slope", what);
+    if (ep.kind == cpg::EvalEpilogue::BN_EVAL && ep.residual != nullptr)
+        return fail(CPG_E_UNSUPPORTED, "%s(winograd): no residual behind the BatchNorm", what);
     if (live != nullptr) {
         hipError_t e = hipMemsetAsync(live, 0, live_words * sizeof(int), stream);
-        if (e != hipSuccess) return hip_status(e, "cpg_conv2d_fwd_bn_eval(winograd)");
+        if (e != hipSuccess) return hip_status(e, what);
     }
-    const WgBnEval bne{gamma, beta, mean, var, eps, relu, live, pad_to(K, 128)};
-    return wino_run(0, N, C, K, H, W, K, C, x, w, pm, thr, bias, y, nullptr, ws, ws_bytes, stream, &bne);
-}
-
-// ... with bias, PReLU (+ residual) in the epilogue instead (bne = null is refused: the mode is an inference mode)
-extern "C" int cpg_conv3x3_wino_run_prelu_eval(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr,
-                                               const float *bias, const float *slope, int per_channel, const float *residual, int *live,
-                                               size_t live_words, float *y, void *ws, size_t ws_bytes, hipStream_t stream) {
-    if (slope == nullptr) return fail(CPG_E_INVALID, "cpg_conv2d_fwd_prelu_eval(winograd): null slope");
-    if (live != nullptr) {
-        hipError_t e = hipMemsetAsync(live, 0, live_words * sizeof(int), stream);
-        if (e != hipSuccess) return hip_status(e, "cpg_conv2d_fwd_prelu_eval(winograd)");
-    }
-    const WgBnEval pre{slope, residual, nullptr, nullptr, 0.0f, per_channel ? 1 : 0, live, pad_to(K, 128)};
-    return wino_run(0, N, C, K, H, W, K, C, x, w, pm, thr, bias, y, nullptr, ws, ws_bytes, stream, &pre, nullptr, true);
+    return wino_run(0, N, C, K, H, W, K, C, x, w, pm, thr, bias, y, nullptr, ws, ws_bytes, stream, &ep, nullptr, live);
 }
 
 static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
-                    float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream, const WgBnEval *bne,
-                    const float *addend, bool prelu) {
-    if (prelu && bne == nullptr) return fail(CPG_E_INVALID, "cpg_conv2d_fwd(winograd): the PReLU epilogue needs its slopes");
+                    float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream,
+                    const cpg::EvalEpilogue *ep, const float *addend, int *live) {
     const char *what = dgrad ? "cpg_conv2d_dgrad(winograd)" : "cpg_conv2d_fwd(winograd)";
     // addend (input-gradient launches of the two-wave kernel only: cpg_conv3x3_wino_dgrad_add_ok): added to the result in the epilogue
     // (k_wg3<.., ADD>; the tail pieces' share in k_wg_tail_reduce)
-    if (addend != nullptr && (!dgrad || bias != nullptr || bne != nullptr || stats != nullptr))
+    if (addend != nullptr && (!dgrad || bias != nullptr || ep != nullptr || stats != nullptr))
         return fail(CPG_E_INVALID, "%s: an addend rides in plain input-gradient launches only", what);
     const size_t need = cpg_conv3x3_wino_pack_bytes(c_read, m);
     if (ws == nullptr || ws_bytes < need) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
@@ -2220,9 +2225,9 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
         WgGeom g;
         wino_geom(g, N, c_read, m, H, W);
         float *up = (float *)ws;
-        const WgBnEval none{nullptr, nullptr, nullptr, nullptr, 0.0f, 0, nullptr, 0};
+        const WgBnEval none{}, bne = wg_epilogue(ep, live, m);
         const float *pre = nullptr;
-        if (bne == nullptr) {      // (the inference epilogue's pack also writes the liveness flags: never taken from a caller's operand)
+        if (ep == nullptr) {       // (the inference epilogue's pack also writes the liveness flags: never taken from a caller's operand)
             if (const int rc = cpg::take_packed(need, &pre, what)) return rc;
         }
         if (pre != nullptr) {
@@ -2230,11 +2235,11 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
         } else {
             const cpg::PackJob job = wino_pack_job(dgrad, c_read, m, K, C);
             hipLaunchKernelGGL(k_wg1_pack, dim3(stream_grid(job.total, 256)), dim3(256), 0, stream, w, pm, thr, up, K, C, m, c_read, job.c,
-                               job.d, bne ? bne->live : nullptr, bne ? bne->Mp : 0);
+                               job.d, bne.live, bne.Mp);
         }
         const int64_t runs = (g.tiles_total + W1_T - 1) / W1_T;
         const bool persist = wino_persist();
-        WgMode mode = bne != nullptr ? (prelu ? WG_FWD_PRE : WG_FWD_BNE) : dgrad ? (addend != nullptr ? WG_DGRAD_ADD : WG_DGRAD) : stats != nullptr ? WG_FWD_STATS : WG_FWD;
+        WgMode mode = ep != nullptr ? (ep->kind == cpg::EvalEpilogue::PRELU ? WG_FWD_PRE : WG_FWD_BNE) : dgrad ? (addend != nullptr ? WG_DGRAD_ADD : WG_DGRAD) : stats != nullptr ? WG_FWD_STATS : WG_FWD;
         // the window maxima a caller attached (cpg_conv2d_fwd_attach_pool_max; cpg_conv2d_fwd_bnstats has checked the buffer's size)
         float *pool_e = nullptr;
         if (cpg::PoolMaxCtx &pc = cpg::pool_max_ctx(); pc.armed && mode == WG_FWD_STATS) {
@@ -2244,7 +2249,7 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
             pool_e = pc.E, pc.armed = false;
             mode = WG_FWD_STATS_PMAX;
         }
-        const WgLaunch whole{g, x, up, mode == WG_DGRAD_ADD ? addend : pool_e != nullptr ? pool_e : bias, y, stats, bne != nullptr ? *bne : none, stream};
+        const WgLaunch whole{g, x, up, mode == WG_DGRAD_ADD ? addend : pool_e != nullptr ? pool_e : bias, y, stats, bne, stream};
         int rc;
         if (variant == WV_PAIR64) {
             int64_t blocks = runs * ((g.nkb + 1) / 2);
@@ -2258,10 +2263,10 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
             }
             // The leftover units of the last round (k_wg3<.., SPLIT>): the full rounds run as before on logical blocks 0 .. first_lb - 1, the rest
             // as pieces of the channel loop into the workspace behind the packed filter, k_wg_tail_reduce adds the pieces (+ bias) into y.
-            const bool sh = bne == nullptr && wino_sh(g);
+            const bool sh = ep == nullptr && wino_sh(g);
             WgTail tail{};
             const size_t tail_off = (need + 255) / 256 * 256;
-            if (bne == nullptr) tail = wino_tail_plan(g, g.nblocks, sh);      // (with the BatchNorm statistics too: k_wg_tail_reduce<true> sums them)
+            if (ep == nullptr) tail = wino_tail_plan(g, g.nblocks, sh);      // (with the BatchNorm statistics too: k_wg_tail_reduce<true> sums them)
             if (tail.on && ws_bytes < tail_off + tail.bytes) tail.on = false;       // (a caller with the round-4 workspace: one launch, as before)
             WgGeom gt = g;
             float *part0 = nullptr;
@@ -2319,7 +2324,7 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
         CPG_CHECK_LAUNCH(what);
         return CPG_OK;
     }
-    if (bne != nullptr) return fail(CPG_E_UNSUPPORTED, "%s: the block kernels have no inference epilogue", what);
+    if (ep != nullptr) return fail(CPG_E_UNSUPPORTED, "%s: the block kernels have no inference epilogue", what);
     return wino_run_block(dgrad, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, stats, ws, stream, what);
 }
 

@@ -6,6 +6,28 @@
 #pragma once
 #include "igemm_core.h"
 
+// ---- the inference epilogue: everything an inference forward does behind the conv, named once --------------------------------------------------
+// BN_EVAL: y = [relu(] bn(conv + bias) [+ residual] [)] with an eval-mode BatchNorm2d (gamma, beta, mean, var: K floats each).
+// PRELU:   y = prelu(conv + bias) [+ residual]; slope: K floats, or one shared (per_channel = 0).
+// residual (may be null): dense, shaped like y.  skip_stats (may be null): 2 device words that receive the dead-channel skip's
+// {4 * (input chunks up to the last live one), output blocks skipped}: written by cpg_conv3x3_fwd_eval, the only class that skips;
+// igemm_conv.hip's fwd_eval zeroes them behind the others.
+// Built by igemm_conv.hip's public entry points, read by one cpg_*_eval entry per kernel family, each of which refuses what its kernels
+// lack.  One place per file maps these names onto the kernels' parameter struct (c3_epilogue, wg_epilogue, cpg_conv1x1_fwd_eval's PwBn).
+// what: the public entry point the caller used, for messages.
+namespace cpg {
+struct EvalEpilogue {
+    enum Kind { BN_EVAL, PRELU } kind;
+    const float *gamma, *beta, *mean, *var;     // BN_EVAL
+    float eps;
+    int relu;
+    const float *slope;                         // PRELU
+    int per_channel;
+    const float *residual;
+    int32_t *skip_stats;
+};
+}  // namespace cpg
+
 // ---- conv3x3.hip: 3x3 / stride 1 / pad 1 -----------------------------------------------------------------------------------------------
 // 1: the specialised 3x3 kernels take this shape (CPG_DISABLE_CONV3X3: never)
 extern "C" int cpg_conv3x3_supported(const cpg_conv_desc *d);
@@ -17,17 +39,12 @@ int cpg_conv3x3_fwd(const cpg_conv_desc *d, const float *x, const float *w, cons
 int cpg_conv3x3_bnstats_tiles(const cpg_conv_desc *d);
 int cpg_conv3x3_fwd_bnstats(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                             float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream);
-// forward with the inference-mode BatchNorm (+ ReLU) folded into the epilogue; skip_stats (may be null): 2 device words
-int cpg_conv3x3_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                            const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu, float *y,
-                            int32_t *skip_stats, void *ws, size_t ws_bytes, hipStream_t stream);
 // 1: the inference epilogues have a launch for this shape under the current option table (the planner's answer; 0: the channel-split tile)
 int cpg_conv3x3_eval_epilogue_ok(const cpg_conv_desc *d);
-// forward with bias, PReLU and the unit's residual folded into the epilogue: y = prelu(conv + bias) [+ residual]; the plan, the workspace
-// and the dead-channel skip of cpg_conv3x3_fwd_bn_eval.  per_channel: K slopes (0: one shared); residual (may be null): dense, shaped like y
-int cpg_conv3x3_fwd_prelu_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                               const float *slope, int per_channel, const float *residual, float *y, int32_t *skip_stats, void *ws,
-                               size_t ws_bytes, hipStream_t stream);
+// forward with ep folded into the epilogue, and the dead-channel skip.  Refused: BN_EVAL with a residual; PRELU where cpg_conv3x3_eval_epilogue_ok
+// answers 0 (the channel-split tile)
+int cpg_conv3x3_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                         const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what);
 int cpg_conv3x3_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                       size_t ws_bytes, hipStream_t stream);
 // the packed operand cpg_conv3x3_fwd / _fwd_bnstats (dgrad = 0) or cpg_conv3x3_dgrad streams and a caller may hand in (cpg_conv2d_use_packed);
@@ -51,13 +68,9 @@ int cpg_conv3x3s2_bnstats_tiles(const cpg_conv_desc *d);
 // stats (may be null): [K][tiles][2] BatchNorm partial sums
 int cpg_conv3x3s2_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y,
                       float *stats, void *ws, size_t ws_bytes, hipStream_t stream);
-// forward with the inference-mode BatchNorm (+ ReLU) folded into the epilogue (no dead-channel skip on the strided tiles)
-int cpg_conv3x3s2_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                              const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu, float *y,
-                              void *ws, size_t ws_bytes, hipStream_t stream);
-// forward with bias and PReLU folded into the epilogue (no residual, no dead-channel skip on the strided tiles)
-int cpg_conv3x3s2_fwd_prelu_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                                 const float *slope, int per_channel, float *y, void *ws, size_t ws_bytes, hipStream_t stream);
+// forward with ep folded into the epilogue.  Refused: a residual (a strided conv opens a stage).  The strided tiles skip nothing
+int cpg_conv3x3s2_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                           const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what);
 int cpg_conv3x3s2_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                         size_t ws_bytes, hipStream_t stream);
 size_t cpg_conv3x3s2_wgrad_workspace(const cpg_conv_desc *d);
@@ -86,15 +99,11 @@ extern "C" int cpg_conv3x3_wino_run(int dgrad, int N, int c_read, int m, int H, 
 extern "C" int cpg_conv3x3_wino_pool_max_ok(int N, int c_read, int m, int H, int W);
 // 1: the inference epilogue is available on the Winograd kernels (not on the cooperative block kernel)
 extern "C" int cpg_conv3x3_wino_eval_ok(int N, int c_read, int m, int H, int W);
-// forward with eval-mode BatchNorm (+ ReLU) in the epilogue; live (may be null): live_words ints, zeroed here, layout of k_c3_pack
-extern "C" int cpg_conv3x3_wino_run_bn_eval(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr,
-                                            const float *bias, const float *gamma, const float *beta, const float *mean, const float *var,
-                                            float eps, int relu, int *live, size_t live_words, float *y, void *ws, size_t ws_bytes,
-                                            hipStream_t stream);
-// forward with bias, PReLU (+ residual) in the epilogue: the same launch plan, liveness words and skip, the PRE instances
-extern "C" int cpg_conv3x3_wino_run_prelu_eval(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr,
-                                               const float *bias, const float *slope, int per_channel, const float *residual, int *live,
-                                               size_t live_words, float *y, void *ws, size_t ws_bytes, hipStream_t stream);
+// forward with ep in the epilogue (BN_EVAL without a residual, or PRELU; a null slope is refused) and the dead-channel skip;
+// live (may be null): live_words ints, zeroed here, layout of k_c3_pack (cpg_conv3x3_fwd_eval copies ep.skip_stats out of them)
+int cpg_conv3x3_wino_run_eval(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                              const cpg::EvalEpilogue &ep, int *live, size_t live_words, float *y, void *ws, size_t ws_bytes, hipStream_t stream,
+                              const char *what);
 // input gradient + addend (gx = dgrad(gy) + addend): the two-wave kernel's launches (>= 64 channels on both sides, or an odd map)
 extern "C" int cpg_conv3x3_wino_dgrad_add_ok(int N, int c_read, int m, int H, int W);
 extern "C" int cpg_conv3x3_wino_dgrad_add(int N, int c_read, int m, int H, int W, int K, int C, const float *gy, const float *w, const float *pm,
@@ -150,10 +159,9 @@ cpg::PackJob cpg_conv1x1_pack_job(const cpg_conv_desc *d, int dgrad);
 int cpg_conv1x1_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                     float *y, void *ws, size_t ws_bytes, hipStream_t stream, float *stats = nullptr);
 int cpg_conv1x1_bnstats_tiles(const cpg_conv_desc *d);
-// forward with the inference-mode BatchNorm (+ residual) (+ ReLU) folded into the epilogue; residual (may be null): dense, shaped like y
-int cpg_conv1x1_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                            const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu,
-                            const float *residual, float *y, void *ws, size_t ws_bytes, hipStream_t stream);
+// forward with ep folded into the epilogue: BN_EVAL only (PRELU is refused), with or without a residual.  Nothing is skipped
+int cpg_conv1x1_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                         const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what);
 // addend (may be null; stride 1 only): gx = dgrad(gy) + addend
 int cpg_conv1x1_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
                       size_t ws_bytes, hipStream_t stream, const float *addend = nullptr);

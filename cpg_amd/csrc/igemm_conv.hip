@@ -738,6 +738,30 @@ extern "C" int32_t cpg_conv2d_winograd(const cpg_conv_desc *d, int32_t dgrad) {
     return dgrad ? cpg_conv3x3_wino_ok(d->N, d->K, d->C, d->H, d->W) : cpg_conv3x3_wino_ok(d->N, d->C, d->K, d->H, d->W);
 }
 
+// The inference forwards: conv and what follows it in one kernel, described by one cpg::EvalEpilogue and run by one entry per kernel
+// family.  fwd_eval is the frame the three public entry points below share: the descriptor's verdict, the route cpg_conv2d_fwd takes,
+// the entry point's own checks (`admit`: a status for the route, in the order it has always made them), the family's entry -- under a
+// PackScope where the launch can take a caller's packed operand -- and zeroed skip_stats from the classes that skip nothing.
+template <class Admit>
+static int fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                    const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what, Admit admit) {
+    ConvGeom g;
+    int rc = make_geom(d, g);
+    if (rc) return rc;
+    const ConvRoute route = fwd_route(d);
+    if ((rc = admit(route)) != CPG_OK) return rc;
+    if (route == ROUTE_C3) return cpg_conv3x3_fwd_eval(d, x, w, pm, thr, bias, ep, y, ws, ws_bytes, stream, what);      // (reports its own skip)
+    if (route != ROUTE_C1 && route != ROUTE_C3S2) return fail(CPG_E_UNSUPPORTED, "%s: no kernel of this class fuses the epilogue", what);
+    PackScope scope;            // (the pointwise launch takes a packed operand as cpg_conv2d_fwd does)
+    rc = route == ROUTE_C1 ? cpg_conv1x1_fwd_eval(d, x, w, pm, thr, bias, ep, y, ws, ws_bytes, stream, what)
+                           : cpg_conv3x3s2_fwd_eval(d, x, w, pm, thr, bias, ep, y, ws, ws_bytes, stream, what);
+    if (rc == CPG_OK && ep.skip_stats != nullptr) {     // these classes skip nothing: what CPG_NO_DEAD_SKIP reports
+        hipError_t e = hipMemsetAsync(ep.skip_stats, 0, 2 * sizeof(int32_t), stream);
+        if (e != hipSuccess) return hip_status(e, what);
+    }
+    return rc;
+}
+
 // conv -> eval-mode BatchNorm2d (-> ReLU) in one kernel; 0 from the _supported query: use cpg_conv2d_fwd + cpg_bn_relu_fwd_eval.
 // The classes with such an epilogue, by the route cpg_conv2d_fwd takes: 3x3 s1 p1 (with the dead-channel skip), pointwise, 3x3 s2.
 extern "C" int32_t cpg_conv2d_fwd_bn_eval_supported(const cpg_conv_desc *d) {
@@ -750,25 +774,12 @@ extern "C" int cpg_conv2d_fwd_bn_eval(const cpg_conv_desc *d, const float *x, co
                                       const float *bias, const float *gamma, const float *beta, const float *running_mean,
                                       const float *running_var, float eps, int32_t relu, float *y, int32_t *skip_stats, void *ws,
                                       size_t ws_bytes, void *stream) {
-    ConvGeom g;
-    int rc = make_geom(d, g);
-    if (rc) return rc;
-    const ConvRoute route = fwd_route(d);
-    if (route == ROUTE_C3)
-        return cpg_conv3x3_fwd_bn_eval(d, x, w, pm, thr, bias, gamma, beta, running_mean, running_var, eps, relu, y, skip_stats, ws,
-                                       ws_bytes, (hipStream_t)stream);
-    if (route != ROUTE_C1 && route != ROUTE_C3S2)
-        return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_bn_eval: only the 3x3 s1 p1, the pointwise and the 3x3 s2 kernels fuse the epilogue");
-    PackScope scope;            // (the pointwise launch takes a packed operand as cpg_conv2d_fwd does)
-    rc = route == ROUTE_C1 ? cpg_conv1x1_fwd_bn_eval(d, x, w, pm, thr, bias, gamma, beta, running_mean, running_var, eps, relu, nullptr, y, ws,
-                                                     ws_bytes, (hipStream_t)stream)
-                           : cpg_conv3x3s2_fwd_bn_eval(d, x, w, pm, thr, bias, gamma, beta, running_mean, running_var, eps, relu, y, ws, ws_bytes,
-                                                       (hipStream_t)stream);
-    if (rc == CPG_OK && skip_stats != nullptr) {        // these classes skip nothing: what CPG_NO_DEAD_SKIP reports
-        hipError_t e = hipMemsetAsync(skip_stats, 0, 2 * sizeof(int32_t), (hipStream_t)stream);
-        if (e != hipSuccess) return hip_status(e, "cpg_conv2d_fwd_bn_eval");
-    }
-    return rc;
+    const cpg::EvalEpilogue ep{cpg::EvalEpilogue::BN_EVAL, gamma, beta, running_mean, running_var, eps, relu, nullptr, 0, nullptr, skip_stats};
+    return fwd_eval(d, x, w, pm, thr, bias, ep, y, ws, ws_bytes, (hipStream_t)stream, "cpg_conv2d_fwd_bn_eval", [](ConvRoute route) {
+        if (route != ROUTE_C3 && route != ROUTE_C1 && route != ROUTE_C3S2)
+            return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_bn_eval: only the 3x3 s1 p1, the pointwise and the 3x3 s2 kernels fuse the epilogue");
+        return CPG_OK;
+    });
 }
 
 // ... and the residual block's tail, conv -> eval-mode BatchNorm2d -> + residual (-> ReLU), on the pointwise kernels
@@ -780,14 +791,13 @@ extern "C" int cpg_conv2d_fwd_bn_eval_add(const cpg_conv_desc *d, const float *x
                                           const float *bias, const float *gamma, const float *beta, const float *running_mean,
                                           const float *running_var, float eps, const float *residual, int32_t relu, float *y, void *ws,
                                           size_t ws_bytes, void *stream) {
-    PackScope scope;
-    ConvGeom g;
-    int rc = make_geom(d, g);
-    if (rc) return rc;
-    if (fwd_route(d) != ROUTE_C1) return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_bn_eval_add: only the pointwise kernels add the residual");
-    CPG_REQUIRE(residual != nullptr, "cpg_conv2d_fwd_bn_eval_add: null residual");
-    return cpg_conv1x1_fwd_bn_eval(d, x, w, pm, thr, bias, gamma, beta, running_mean, running_var, eps, relu, residual, y, ws, ws_bytes,
-                                   (hipStream_t)stream);
+    PackScope scope;            // (a refused call, too, uses up the packed operand a caller armed)
+    const cpg::EvalEpilogue ep{cpg::EvalEpilogue::BN_EVAL, gamma, beta, running_mean, running_var, eps, relu, nullptr, 0, residual, nullptr};
+    return fwd_eval(d, x, w, pm, thr, bias, ep, y, ws, ws_bytes, (hipStream_t)stream, "cpg_conv2d_fwd_bn_eval_add", [&](ConvRoute route) {
+        if (route != ROUTE_C1) return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_bn_eval_add: only the pointwise kernels add the residual");
+        CPG_REQUIRE(residual != nullptr, "cpg_conv2d_fwd_bn_eval_add: null residual");
+        return CPG_OK;
+    });
 }
 
 // SphereNet's inference: conv -> (+ bias) -> PReLU (-> + the unit's residual) in one kernel, y = prelu(conv + bias) [+ residual].  The
@@ -803,25 +813,16 @@ extern "C" int32_t cpg_conv2d_fwd_prelu_eval_supported(const cpg_conv_desc *d, i
 extern "C" int cpg_conv2d_fwd_prelu_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr,
                                          const float *bias, const float *slope, int32_t n_slopes, const float *residual, float *y,
                                          int32_t *skip_stats, void *ws, size_t ws_bytes, void *stream) {
-    ConvGeom g;
-    int rc = make_geom(d, g);
-    if (rc) return rc;
-    CPG_REQUIRE(x && w && y && slope, "cpg_conv2d_fwd_prelu_eval: null pointer");
-    CPG_REQUIRE(n_slopes == d->K || n_slopes == 1, "cpg_conv2d_fwd_prelu_eval: n_slopes must be K or 1");
-    if (!cpg_conv2d_fwd_prelu_eval_supported(d, residual != nullptr ? 1 : 0))
-        return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_prelu_eval: only the 3x3 s1 p1 kernels (and, without a residual, the 3x3 s2 kernels) "
-                                       "fuse the epilogue; not on channel-split tiles");
-    // (K == 1: one slope either way -- read as per-channel, index 0)
-    const int per_channel = n_slopes == d->K ? 1 : 0;
-    if (fwd_route(d) == ROUTE_C3)
-        return cpg_conv3x3_fwd_prelu_eval(d, x, w, pm, thr, bias, slope, per_channel, residual, y, skip_stats, ws, ws_bytes, (hipStream_t)stream);
-    PackScope scope;
-    rc = cpg_conv3x3s2_fwd_prelu_eval(d, x, w, pm, thr, bias, slope, per_channel, y, ws, ws_bytes, (hipStream_t)stream);
-    if (rc == CPG_OK && skip_stats != nullptr) {        // the strided tiles skip nothing: what CPG_NO_DEAD_SKIP reports
-        hipError_t e = hipMemsetAsync(skip_stats, 0, 2 * sizeof(int32_t), (hipStream_t)stream);
-        if (e != hipSuccess) return hip_status(e, "cpg_conv2d_fwd_prelu_eval");
-    }
-    return rc;
+    // (per_channel: n_slopes == K once the count is admitted; K == 1 is one slope either way, index 0)
+    const cpg::EvalEpilogue ep{cpg::EvalEpilogue::PRELU, nullptr, nullptr, nullptr, nullptr, 0.0f, 0, slope, n_slopes != 1, residual, skip_stats};
+    return fwd_eval(d, x, w, pm, thr, bias, ep, y, ws, ws_bytes, (hipStream_t)stream, "cpg_conv2d_fwd_prelu_eval", [&](ConvRoute) {
+        CPG_REQUIRE(x && w && y && slope, "cpg_conv2d_fwd_prelu_eval: null pointer");
+        CPG_REQUIRE(n_slopes == d->K || n_slopes == 1, "cpg_conv2d_fwd_prelu_eval: n_slopes must be K or 1");
+        if (!cpg_conv2d_fwd_prelu_eval_supported(d, residual != nullptr ? 1 : 0))
+            return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_prelu_eval: only the 3x3 s1 p1 kernels (and, without a residual, the 3x3 s2 kernels) "
+                                           "fuse the epilogue; not on channel-split tiles");
+        return CPG_OK;
+    });
 }
 
 // input gradient + the BatchNorm-backward reduction of the layer below in its epilogue (3x3 s1 p1 kernels only)

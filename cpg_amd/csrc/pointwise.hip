@@ -910,13 +910,12 @@ int cpg_conv1x1_fwd(const cpg_conv_desc *d, const float *x, const float *w, cons
 }
 
 // inference: y = [max(0,] bn(conv + bias) [+ residual] [)] in one launch (k_pw's BNE instances); residual: dense, shaped like y, or null
-int cpg_conv1x1_fwd_bn_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                            const float *gamma, const float *beta, const float *mean, const float *var, float eps, int relu,
-                            const float *residual, float *y, void *ws, size_t ws_bytes, hipStream_t stream) {
-    const char *what = residual ? "cpg_conv2d_fwd_bn_eval_add(1x1)" : "cpg_conv2d_fwd_bn_eval(1x1)";
-    CPG_REQUIRE(x && w && y && gamma && beta && mean && var, "%s: null pointer", what);
-    const PwBn bn{gamma, beta, mean, var, eps, relu};
-    return pw_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, stream, nullptr, &bn, residual, what);
+int cpg_conv1x1_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
+                         const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what) {
+    if (ep.kind != cpg::EvalEpilogue::BN_EVAL) return fail(CPG_E_UNSUPPORTED, "%s(1x1): the pointwise kernels have the BatchNorm epilogue only", what);
+    CPG_REQUIRE(x && w && y && ep.gamma && ep.beta && ep.mean && ep.var, "%s(1x1): null pointer", what);
+    const PwBn bn{ep.gamma, ep.beta, ep.mean, ep.var, ep.eps, ep.relu};
+    return pw_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, stream, nullptr, &bn, ep.residual, what);
 }
 
 int cpg_conv1x1_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,

@@ -84,6 +84,16 @@ def _out_hw(d):
     return oh, ow
 
 
+def _bn_eval_args(bn):
+    """gamma, beta, running_mean, running_var, eps of an eval-mode nn.BatchNorm2d, as the inference entry points take them."""
+    return (_lib.dptr(bn.weight, name='bn.weight'), _lib.dptr(bn.bias, name='bn.bias'), _lib.dptr(bn.running_mean, name='running_mean'),
+            _lib.dptr(bn.running_var, name='running_var'), float(bn.eps))
+
+
+def _skip_stats_ptr(skip_stats):
+    return None if skip_stats is None else ctypes.c_void_p(skip_stats.data_ptr())
+
+
 # CPG_PACK_CACHE=0: every conv call packs its own weight operand (the behaviour up to round 5; A/B switch)
 PACK_CACHE = os.environ.get('CPG_PACK_CACHE', '1') not in ('0', '')
 
@@ -549,7 +559,7 @@ class SharableConv2d(_Sharable):
         return getattr(self, 'math', None) or CONV_MATH
 
     def forward_with_bn_stats(self, input, bn_hint=None, pool_sink=None):
-        """(Shared with packnet_models.layers.PlainConv2d, which borrows this method, forward_with_skip, forward_bn_eval, forward_bn_eval_add and forward_prelu_eval: they may read
+        """(Shared with packnet_models.layers.PlainConv2d, which borrows this method, forward_with_skip, forward_bn_eval, forward_bn_eval_add, forward_prelu_eval and their frame _forward_eval: they may read
         only piggymask, info['threshold'], _math(), groups, stride, padding, dilation, weight and bias, and call forward();
         tests/test_packnet_host.py and tests/test_packnet_nets_host.py check that.)
         (y, stats): forward plus the BatchNorm partial sums of y from the same kernel; stats is None when this shape
@@ -571,56 +581,50 @@ class SharableConv2d(_Sharable):
                                                    self.stride, self.padding, self.dilation, self.groups, self._math(), bias_sink, want_stats)
         return y, (stats if stats.numel() else None), skip
 
+    def _forward_eval(self, input, entry, query_args, own):
+        """The frame forward_bn_eval, forward_bn_eval_add and forward_prelu_eval share (borrowed with them by PlainConv2d, under the same
+        rule).  Refuses (None) grad mode, a malformed input and the arithmetics and groups without such kernels; makes the contiguous
+        copies and the descriptor; asks `entry`_supported(descriptor, *query_args); lets the caller check what is its own --
+        own(output shape) returns None to refuse, or (the arguments between bias and y, those between y and the workspace); then allocates
+        the output and the workspace and makes the call."""
+        if (torch.is_grad_enabled() or input.dim() != 4 or input.shape[0] == 0 or input.shape[1] != self.weight.shape[1] * self.groups
+                or self._math() != 'fp32' or self.groups != 1):
+            return None
+        x = input.contiguous()
+        w = self.weight.contiguous()
+        p = None if self.piggymask is None else self.piggymask.contiguous()
+        d = _conv_desc(x.shape, w.shape, self.stride, self.padding, self.dilation, self.groups)
+        L = _lib.lib()
+        if not getattr(L, entry + '_supported')(ctypes.byref(d), *query_args):
+            return None
+        shape = (d.N, d.K) + tuple(_out_hw(d))
+        args = own(shape)
+        if args is None:
+            return None
+        y = torch.empty(shape, dtype=torch.float32, device=x.device)
+        ws, nbytes = _lib.workspace(L.cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
+        _lib.call(entry, ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'), _lib.dptr(p, name='piggymask'),
+                  float(self.info['threshold']), _lib.dptr(self.bias, name='bias'), *args[0], _lib.dptr(y), *args[1], _lib.dptr(ws), nbytes,
+                  _lib.stream_ptr())
+        return y
+
     def forward_bn_eval(self, input, bn, relu=True, skip_stats=None):
         """relu(bn(conv(input))) with `bn` an eval-mode nn.BatchNorm2d, as ONE kernel (cpg_conv2d_fwd_bn_eval): the path of
         Manager.validate.  Inference only -- call it under torch.no_grad(); returns None when this shape has no fused
         kernel (the caller then runs the layers one by one).  skip_stats: optional int32[2] device tensor that receives
         {4 * (4-channel input chunks up to the last live one), output blocks skipped} (dead-channel skip, see include/cpg_hip.h)."""
-        if (torch.is_grad_enabled() or input.dim() != 4 or input.shape[0] == 0 or input.shape[1] != self.weight.shape[1] * self.groups
-                or self._math() != 'fp32' or self.groups != 1):
-            return None
-        x = input.contiguous()
-        w = self.weight.contiguous()
-        p = None if self.piggymask is None else self.piggymask.contiguous()
-        d = _conv_desc(x.shape, w.shape, self.stride, self.padding, self.dilation, self.groups)
-        L = _lib.lib()
-        if not L.cpg_conv2d_fwd_bn_eval_supported(ctypes.byref(d)):
-            return None
-        oh, ow = _out_hw(d)
-        y = torch.empty((d.N, d.K, oh, ow), dtype=torch.float32, device=x.device)
-        ws, nbytes = _lib.workspace(L.cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
-        _lib.call('cpg_conv2d_fwd_bn_eval', ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'),
-                  _lib.dptr(p, name='piggymask'), float(self.info['threshold']), _lib.dptr(self.bias, name='bias'),
-                  _lib.dptr(bn.weight, name='bn.weight'), _lib.dptr(bn.bias, name='bn.bias'), _lib.dptr(bn.running_mean, name='running_mean'),
-                  _lib.dptr(bn.running_var, name='running_var'), float(bn.eps), int(bool(relu)), _lib.dptr(y),
-                  None if skip_stats is None else ctypes.c_void_p(skip_stats.data_ptr()), _lib.dptr(ws), nbytes, _lib.stream_ptr())
-        return y
+        return self._forward_eval(input, 'cpg_conv2d_fwd_bn_eval', (),
+                                  lambda shape: (_bn_eval_args(bn) + (int(bool(relu)),), (_skip_stats_ptr(skip_stats),)))
 
     def forward_bn_eval_add(self, input, bn, res, relu=True):
         """relu(bn(conv(input)) + res), the tail of a residual block (models/resnet.py:94-104), with `bn` an eval-mode nn.BatchNorm2d, as
         ONE kernel (cpg_conv2d_fwd_bn_eval_add: the pointwise shapes).  Inference only, like forward_bn_eval; returns None when this
         shape has no such kernel or `res` is not a dense fp32 device tensor shaped like the output."""
-        if (torch.is_grad_enabled() or input.dim() != 4 or input.shape[0] == 0 or input.shape[1] != self.weight.shape[1] * self.groups
-                or self._math() != 'fp32' or self.groups != 1):
-            return None
-        x = input.contiguous()
-        w = self.weight.contiguous()
-        p = None if self.piggymask is None else self.piggymask.contiguous()
-        d = _conv_desc(x.shape, w.shape, self.stride, self.padding, self.dilation, self.groups)
-        L = _lib.lib()
-        if not L.cpg_conv2d_fwd_bn_eval_add_supported(ctypes.byref(d)):
-            return None
-        oh, ow = _out_hw(d)
-        if tuple(res.shape) != (d.N, d.K, oh, ow) or res.dtype != torch.float32 or not res.is_cuda:
-            return None
-        y = torch.empty((d.N, d.K, oh, ow), dtype=torch.float32, device=x.device)
-        ws, nbytes = _lib.workspace(L.cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
-        _lib.call('cpg_conv2d_fwd_bn_eval_add', ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'),
-                  _lib.dptr(p, name='piggymask'), float(self.info['threshold']), _lib.dptr(self.bias, name='bias'),
-                  _lib.dptr(bn.weight, name='bn.weight'), _lib.dptr(bn.bias, name='bn.bias'), _lib.dptr(bn.running_mean, name='running_mean'),
-                  _lib.dptr(bn.running_var, name='running_var'), float(bn.eps), _lib.dptr(res.contiguous(), name='residual'),
-                  int(bool(relu)), _lib.dptr(y), _lib.dptr(ws), nbytes, _lib.stream_ptr())
-        return y
+        def own(shape):
+            if tuple(res.shape) != shape or res.dtype != torch.float32 or not res.is_cuda:
+                return None
+            return _bn_eval_args(bn) + (_lib.dptr(res.contiguous(), name='residual'), int(bool(relu))), ()
+        return self._forward_eval(input, 'cpg_conv2d_fwd_bn_eval_add', (), own)
 
     def forward_prelu_eval(self, input, prelu, res=None, skip_stats=None):
         """prelu(conv(input)) [+ res] -- a conv of models/spherenet.py with the nn.PReLU behind it and, at the end of a unit, the unit's
@@ -630,30 +634,17 @@ class SharableConv2d(_Sharable):
         is not a dense fp32 device tensor shaped like the output."""
         if torch.is_grad_enabled() or type(prelu) is not torch.nn.PReLU or prelu.weight.numel() not in (1, self.weight.shape[0]):
             return None
-        if (input.dim() != 4 or input.shape[0] == 0 or input.shape[1] != self.weight.shape[1] * self.groups
-                or self._math() != 'fp32' or self.groups != 1):
-            return None
-        x = input.contiguous()
-        w = self.weight.contiguous()
-        p = None if self.piggymask is None else self.piggymask.contiguous()
-        d = _conv_desc(x.shape, w.shape, self.stride, self.padding, self.dilation, self.groups)
-        L = _lib.lib()
-        if not L.cpg_conv2d_fwd_prelu_eval_supported(ctypes.byref(d), 0 if res is None else 1):
-            return None
-        oh, ow = _out_hw(d)
-        if res is not None and (tuple(res.shape) != (d.N, d.K, oh, ow) or res.dtype != torch.float32 or not res.is_cuda
-                                or not res.is_contiguous() or res.data_ptr() % 16):
-            return None
-        slope = prelu.weight
-        if slope.dtype != torch.float32 or not slope.is_cuda:
-            return None
-        y = torch.empty((d.N, d.K, oh, ow), dtype=torch.float32, device=x.device)
-        ws, nbytes = _lib.workspace(L.cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
-        _lib.call('cpg_conv2d_fwd_prelu_eval', ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'),
-                  _lib.dptr(p, name='piggymask'), float(self.info['threshold']), _lib.dptr(self.bias, name='bias'),
-                  _lib.dptr(slope.contiguous(), name='prelu.weight'), slope.numel(), _lib.dptr(res, name='residual'), _lib.dptr(y),
-                  None if skip_stats is None else ctypes.c_void_p(skip_stats.data_ptr()), _lib.dptr(ws), nbytes, _lib.stream_ptr())
-        return y
+
+        def own(shape):
+            if res is not None and (tuple(res.shape) != shape or res.dtype != torch.float32 or not res.is_cuda
+                                    or not res.is_contiguous() or res.data_ptr() % 16):
+                return None
+            slope = prelu.weight
+            if slope.dtype != torch.float32 or not slope.is_cuda:
+                return None
+            return ((_lib.dptr(slope.contiguous(), name='prelu.weight'), slope.numel(), _lib.dptr(res, name='residual')),
+                    (_skip_stats_ptr(skip_stats),))
+        return self._forward_eval(input, 'cpg_conv2d_fwd_prelu_eval', (0 if res is None else 1,), own)
 
     def extra_repr(self):
         s = '{in_channels}, {out_channels}, kernel_size={kernel_size}, stride={stride}'

@@ -147,8 +147,11 @@ def test_plain_conv_borrows_the_tail_method():
     from cpg_amd.models.layers import SharableConv2d
     from cpg_amd.packnet_models.layers import PlainConv2d
     assert PlainConv2d.forward_bn_eval_add is SharableConv2d.forward_bn_eval_add
+    assert PlainConv2d._forward_eval is SharableConv2d._forward_eval          # the frame the method runs in: the same function on both
     conv = PlainConv2d(16, 32, 1, bias=False)
     names = set(re.findall(r'self\.(\w+)', inspect.getsource(SharableConv2d.forward_bn_eval_add)))
+    assert '_forward_eval' in names
+    names |= set(re.findall(r'self\.(\w+)', inspect.getsource(SharableConv2d._forward_eval)))
     assert {'weight', 'piggymask', 'info', 'stride', 'groups'} <= names
     for name in names:
         assert hasattr(conv, name), name

@@ -105,15 +105,17 @@ def test_nan_cutoff_case_releases_nothing_and_still_zeroes(ops):
 
 
 def test_plain_conv_offers_what_the_borrowed_methods_read():
-    """PlainConv2d borrows forward_with_bn_stats / forward_bn_eval from SharableConv2d: every attribute they read must exist on it, and
-    its shared `info` cannot be written."""
+    """PlainConv2d borrows forward_with_bn_stats / forward_bn_eval (and the frame the inference methods share, _forward_eval) from
+    SharableConv2d: every attribute they read must exist on it, and its shared `info` cannot be written."""
     import inspect
     import re
     from cpg_amd.models.layers import SharableConv2d
     from cpg_amd.packnet_models.layers import PlainConv2d
     conv = PlainConv2d(3, 8, 3, padding=1)
     assert PlainConv2d.forward_with_bn_stats is SharableConv2d.forward_with_bn_stats and PlainConv2d.forward_bn_eval is SharableConv2d.forward_bn_eval
-    for fn in (SharableConv2d.forward_with_bn_stats, SharableConv2d.forward_bn_eval):
+    assert PlainConv2d._forward_eval is SharableConv2d._forward_eval
+    assert '_forward_eval' in set(re.findall(r'self\.(\w+)', inspect.getsource(SharableConv2d.forward_bn_eval)))
+    for fn in (SharableConv2d.forward_with_bn_stats, SharableConv2d.forward_bn_eval, SharableConv2d._forward_eval):
         for name in set(re.findall(r'self\.(\w+)', inspect.getsource(fn))):
             assert hasattr(conv, name), name
     assert conv.piggymask is None and conv.info['threshold'] == 0.0 and conv._math() == 'fp32'

@@ -59,10 +59,13 @@ def test_refused_before_any_library_call(conv, monkeypatch):
 def test_plain_conv_borrows_the_method():
     """PlainConv2d.forward_prelu_eval IS SharableConv2d's, and it reads only what a PlainConv2d has (the rule of tests/test_packnet_host.py)."""
     assert PlainConv2d.forward_prelu_eval is SharableConv2d.forward_prelu_eval
+    assert PlainConv2d._forward_eval is SharableConv2d._forward_eval          # the frame the method runs in: the same function on both
     conv = PlainConv2d(16, 32, 3, padding=1)
     names = set(re.findall(r'self\.(\w+)', inspect.getsource(SharableConv2d.forward_prelu_eval)))
+    assert '_forward_eval' in names
+    names |= set(re.findall(r'self\.(\w+)', inspect.getsource(SharableConv2d._forward_eval)))
     assert {'weight', 'piggymask', 'info', 'stride', 'groups', 'bias'} <= names
-    allowed = {'piggymask', 'info', '_math', 'groups', 'stride', 'padding', 'dilation', 'weight', 'bias', 'forward'}
+    allowed = {'piggymask', 'info', '_math', 'groups', 'stride', 'padding', 'dilation', 'weight', 'bias', 'forward', '_forward_eval'}
     assert names <= allowed, names - allowed
     for name in names:
         assert hasattr(conv, name), name
