@@ -23,17 +23,11 @@ from cpg_amd.utils import Optimizers             # noqa: E402
 from cpg_amd.utils.prune import SparsePruner     # noqa: E402
 from oracle import ops                           # noqa: E402  (checker only)
 
+import _parity_cases as PC                       # noqa: E402  (the bodies shared with tests/test_guard_bands_gpu.py)
+from _parity_cases import T, TinyNet, Wrap, close, make_pruner    # noqa: E402,F401
+
 DEV = 'cuda:0'
 VGG_CFG = [64, 64, 'M', 128, 128, 'M', 256, 256, 256, 'M', 512, 512, 512, 'M', 512, 512, 512, 'M']
-
-
-def T(a, dtype=torch.float32):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV, dtype)
-
-
-def close(got, want, rtol=1e-4, atol=1e-5, msg=''):
-    got = got.detach().cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
-    np.testing.assert_allclose(got, want, rtol=rtol, atol=atol, err_msg=msg)
 
 
 # --------------------------------------------------------------------------- binarizer
@@ -100,183 +94,27 @@ def test_linear_golden(name):
 
 
 # --------------------------------------------------------------------------- conv / linear vs oracle, larger
-@pytest.mark.parametrize('N,C,H,W,K,k,s,p,bias,pm', [
-    (4, 64, 56, 56, 128, 3, 1, 1, False, False),     # VGG mid layer (3x3 s1 p1), several tiles
-    (3, 3, 224, 224, 64, 3, 1, 1, False, False),     # VGG first layer, Cin = 3
-    (2, 128, 28, 28, 256, 3, 1, 1, False, True),     # with piggymask
-    (5, 512, 14, 14, 512, 3, 1, 1, False, False),    # deep K (4608), small spatial
-    (2, 64, 33, 47, 70, 3, 1, 1, True, True),        # ragged everything
-    (2, 20, 15, 14, 130, 3, 1, 1, False, True),      # small-map config (<=16 wide), ragged rows, 2 channel tiles
-    (1, 70, 30, 56, 64, 3, 1, 1, True, False),       # <=64-channel config, partial 32-wide tiles
-    (3, 32, 14, 14, 96, 3, 1, 1, False, False),      # whole-image tiles; wgrad 7x14 units
-    (2, 17, 10, 40, 33, 3, 1, 1, False, True),       # channel counts not multiples of the chunk / fragment
-    (2, 24, 11, 56, 130, 3, 1, 1, True, False),      # 56-wide tiles (7 fragments), ragged rows, 2 channel tiles
-    (1, 40, 9, 112, 48, 3, 1, 1, False, True),       # 56-wide tiles, <= 64 output channels; wgrad 2x28 units
-    (3, 2, 13, 37, 70, 3, 1, 1, False, True),        # stem weight-gradient kernel (C <= 3), ragged tiles, 2 co blocks
-    (5, 160, 28, 28, 136, 3, 1, 1, False, False),    # two-image 4x28 tiles with an odd image count
-    (2, 32, 12, 28, 128, 3, 1, 1, True, True),       # two-image tiles, bias + piggymask
-    (4, 16, 14, 14, 72, 3, 1, 1, True, True),        # 14x14 maps: channel-split virtual-row tiles (atomic accumulation), bias on one half
-    (6, 32, 7, 7, 160, 3, 1, 1, False, True),        # 7x7 maps: virtual-row tiles over 6 images (fwd + dgrad), 7x8 wgrad units
-    (37, 16, 7, 7, 24, 3, 1, 1, True, False),        # 7x7 maps, image count not a multiple of the tile, bias, <= 64 channels
-    (5, 12, 6, 8, 20, 3, 1, 1, False, False),        # 6x8 maps: 7x8 wgrad units with a missing row
-    (2, 4, 1, 1, 8, 3, 1, 1, True, True),            # 1x1 map: every tap but the centre is padding
-    (1, 16, 2, 3, 16, 3, 1, 1, False, False),        # 2x3 map, single image
-    (3, 16, 1, 1, 32, 1, 1, 0, False, True),         # pointwise on 1x1 maps (a linear layer in disguise)
-    (2, 3, 64, 64, 16, 7, 2, 3, False, False),       # ResNet stem
-    (3, 64, 28, 28, 256, 1, 1, 0, False, True),      # ResNet 1x1
-    (3, 256, 28, 28, 512, 1, 2, 0, False, False),    # ResNet downsample
-    (5, 32, 7, 7, 48, 1, 1, 0, False, True),         # pointwise kernel, 7x7 maps: scalar staging, tiles span 5 images
-    (9, 48, 14, 14, 80, 1, 1, 0, True, False),       # pointwise kernel, float4 staging, tiles straddle images, bias
-    (2, 16, 15, 15, 32, 1, 2, 0, False, True),       # pointwise stride 2 on an odd map (scatter + zero fill in dgrad)
-    (2, 24, 8, 8, 16, 1, 1, 0, False, False),        # 1x1 with C % 16 != 0 -> generic kernel
-    (2, 20, 15, 17, 24, 3, 2, 1, False, True),       # strided dgrad by residue classes, odd map
-    (1, 8, 20, 20, 8, 5, 3, 2, True, False),         # stride 3, 5x5: nine residue classes with 1..4 taps
-    (2, 8, 9, 9, 8, 1, 2, 0, False, False),          # 1x1 s2 on the generic kernel: three classes have no taps (zero fill)
-    (2, 130, 12, 12, 70, 3, 2, 1, False, False),     # strided dgrad, > 64 input channels (128-wide tile), ragged channels
-    (2, 64, 56, 56, 64, 3, 2, 1, True, False),       # SphereNet stride-2 with bias: <= 64-channel strided tiles, 28-wide class grid
-    (3, 128, 56, 56, 128, 3, 2, 1, False, True),     # ResNet layer2 stride-2: two-image 4x28 output strips (odd image count), piggymask
-    (5, 96, 28, 28, 136, 3, 2, 1, True, False),      # 14x14 outputs: whole-image strided tile, two-image class-grid tiles, bias
-    (9, 64, 14, 14, 160, 3, 2, 1, False, True),      # 7x7 outputs: two-image 8x8 tiles; class grid: one row of eight images (9 images)
-    (3, 160, 14, 14, 72, 3, 2, 1, False, False),     # the same with > 64 input channels in the input gradient
-    (2, 32, 33, 70, 200, 3, 2, 1, True, True),       # odd map, 35-wide outputs: the general strided tiles
-    (1, 16, 2, 2, 16, 3, 2, 1, False, False),        # 2x2 -> 1x1
-    (3, 3, 64, 70, 64, 7, 2, 3, False, True),        # ResNet stem on the strided stem kernels: ragged tiles, piggymask
-    (2, 3, 37, 45, 64, 7, 2, 3, True, False),        # ... odd map, bias
-    (5, 3, 30, 64, 64, 3, 2, 1, True, False),        # SphereNet stem (3x3 s2 from 3 channels, bias)
-    (2, 2, 16, 18, 64, 3, 2, 1, False, True),        # ... two input channels
-    (1, 3, 224, 224, 64, 7, 2, 3, False, False),     # the ResNet stem's own map: 4 x 32 tiles, several tiles per wave
-    # the GROWN VGG16 of configs[1] (raw multiplier 1.5 -> sqrt -> int(v * 1.2247): 78 / 156 / 313 / 627 channels,
-    # CPG_cifar100_main_normal.py:115-116 + models/vgg.py:124-154): channel counts that are no multiple of the Winograd kernels' chunk (4) /
-    # block (32): the last chunk / block overlaps its neighbour (wg_chunk_base, k0 / c0 in k_wgw)
-    (1, 3, 224, 224, 78, 3, 1, 1, False, False),     # features.0 of the grown net (the 64-output stem kernel does not apply)
-    (1, 78, 224, 224, 78, 3, 1, 1, False, True),     # features.3
-    (2, 78, 112, 112, 156, 3, 1, 1, False, False),   # features.7
-    (2, 156, 56, 56, 313, 3, 1, 1, False, True),     # features.14
-    (3, 313, 28, 28, 627, 3, 1, 1, False, False),    # features.24
-    (5, 627, 14, 14, 627, 3, 1, 1, False, True),     # features.34 (the narrow weight-gradient stages: image pairs, odd image count)
-    (2, 33, 28, 28, 35, 3, 1, 1, True, True),        # one channel past the block on both sides, bias
-    (2, 67, 14, 14, 61, 3, 1, 1, False, False),      # C % 4 = 3, K < 64 (k_wg1), narrow weight-gradient stages
-    (3, 18, 12, 20, 19, 3, 1, 1, True, False),       # C % 4 = 2 just above the Winograd minimum (16)
-])
+@pytest.mark.parametrize('N,C,H,W,K,k,s,p,bias,pm', PC.CONV_ORACLE_CASES)
 def test_conv_oracle(N, C, H, W, K, k, s, p, bias, pm):
-    g = torch.Generator().manual_seed(N * 1000 + C + K)
-    x = torch.randn(N, C, H, W, generator=g)
-    w = torch.randn(K, C, k, k, generator=g) * (2.0 / (C * k * k)) ** 0.5
-    b = torch.randn(K, generator=g) * 0.1 if bias else None
-    pmv = torch.rand(K, C, k, k, generator=g) * 0.012 if pm else None
-    layer = nl.SharableConv2d(C, K, k, stride=s, padding=p, bias=bias).to(DEV)
-    layer.weight.data.copy_(w)
-    if bias:
-        layer.bias.data.copy_(b)
-    if pm:
-        layer.piggymask = nn.Parameter(pmv.to(DEV))
-    xd = x.to(DEV).requires_grad_(True)
-    y = layer(xd)
-    want = ops.conv2d_forward(x.numpy(), w.numpy(), None if pmv is None else pmv.numpy(), None if b is None else b.numpy(), s, p)
-    close(y, want, rtol=1e-4, atol=2e-5, msg='y')
-    gy = torch.randn(y.shape, generator=g)
-    y.backward(gy.to(DEV))
-    r = ops.conv2d_backward(x.numpy(), w.numpy(), gy.numpy(), None if pmv is None else pmv.numpy(), bias, s, p)
-    scale = float(np.abs(r['gw']).max())
-    close(xd.grad, r['gx'], rtol=1e-4, atol=2e-5, msg='gx')
-    close(layer.weight.grad, r['gw'], rtol=1e-4, atol=1e-5 * max(scale, 1.0), msg='gw')
-    if pm:
-        close(layer.piggymask.grad, r['gpm'], rtol=1e-4, atol=1e-5 * max(scale, 1.0), msg='gpm')
-    if bias:
-        close(layer.bias.grad, r['gb'], rtol=1e-4, atol=1e-3, msg='gb')
+    PC.conv_oracle(N, C, H, W, K, k, s, p, bias, pm)
 
 
-@pytest.mark.parametrize('N,C,K,H,W,k,s,p,G,bias,pm', [
-    (3, 32, 64, 14, 14, 3, 1, 1, 4, False, True),      # ResNeXt-style 3x3: 4 groups of 8 -> 16 channels (generic kernels: < 16 channels a group)
-    (2, 64, 64, 12, 12, 3, 1, 1, 2, True, False),      # two groups of 32 -> 32 (Winograd kernels per group), bias
-    (2, 32, 32, 9, 9, 1, 1, 0, 4, True, True),         # grouped pointwise
-    (2, 48, 96, 10, 10, 3, 2, 1, 3, False, False),     # strided, 3 groups
-])
+@pytest.mark.parametrize('N,C,K,H,W,k,s,p,G,bias,pm', PC.GROUPED_CONV_CASES)
 def test_grouped_conv_vs_oracle(N, C, K, H, W, k, s, p, G, bias, pm):
     """groups > 1 (models/layers.py:108-109; no CPG configuration uses it): one launch of the groups == 1 kernels per group.  Output and
     all gradients against the oracle's F.conv2d(groups=G) restatement."""
-    g = torch.Generator().manual_seed(N + C + K + G)
-    x = torch.randn(N, C, H, W, generator=g)
-    w = torch.randn(K, C // G, k, k, generator=g) * 0.2
-    b = torch.randn(K, generator=g) * 0.1 if bias else None
-    pmv = torch.rand(K, C // G, k, k, generator=g) * 0.012 if pm else None
-    layer = nl.SharableConv2d(C, K, k, stride=s, padding=p, groups=G, bias=bias).to(DEV)
-    layer.weight.data.copy_(w)
-    if bias:
-        layer.bias.data.copy_(b)
-    if pm:
-        layer.piggymask = nn.Parameter(pmv.to(DEV))
-    xd = x.to(DEV).requires_grad_(True)
-    y = layer(xd)
-    want = ops.conv2d_forward(x.numpy(), w.numpy(), None if pmv is None else pmv.numpy(), None if b is None else b.numpy(), s, p, 1, G)
-    close(y, want, rtol=1e-4, atol=2e-5, msg='y')
-    gy = torch.randn(y.shape, generator=g)
-    y.backward(gy.to(DEV))
-    r = ops.conv2d_backward(x.numpy(), w.numpy(), gy.numpy(), None if pmv is None else pmv.numpy(), bias, s, p, 1, G)
-    scale = float(np.abs(r['gw']).max())
-    close(xd.grad, r['gx'], rtol=1e-4, atol=2e-5, msg='gx')
-    close(layer.weight.grad, r['gw'], rtol=1e-4, atol=1e-5 * max(scale, 1.0), msg='gw')
-    if pm:
-        close(layer.piggymask.grad, r['gpm'], rtol=1e-4, atol=1e-5 * max(scale, 1.0), msg='gpm')
-    if bias:
-        close(layer.bias.grad, r['gb'], rtol=1e-4, atol=1e-3, msg='gb')
-    with torch.no_grad():
-        y2, st = layer.forward_with_bn_stats(x.to(DEV))
-    assert st is None and torch.equal(y2, y.detach())
+    PC.grouped_conv_vs_oracle(N, C, K, H, W, k, s, p, G, bias, pm)
 
 
 # K: 64 = the width-1.0 stem; 78 = the grown VGG16's (int(64 sqrt(1.5)): the three-block instance with a partial last block), 65 / 96 its extremes
-@pytest.mark.parametrize('K', [64, 78, 65, 96])
+@pytest.mark.parametrize('K', PC.FUSED_STEM_K)
 @pytest.mark.parametrize('wgrad_in_pass', [True, False])
-@pytest.mark.parametrize('N,C,H,W,pm', [(3, 3, 40, 70, False), (2, 3, 224, 224, True), (5, 1, 17, 33, False), (4, 2, 64, 64, True)])
+@pytest.mark.parametrize('N,C,H,W,pm', PC.FUSED_STEM_SHAPES)
 def test_fused_stem_conv_bn_relu_matches_unfused(N, C, H, W, pm, wgrad_in_pass, K, monkeypatch):
     """The stem fused with its BatchNorm2d -> ReLU (cpg_stem_bn_*: the conv output is recomputed in every pass instead of stored)
     against the unfused chain (stem conv with the statistics epilogue, fused BatchNorm kernels) and against torch in fp64: output,
     running statistics, and the gradients of the weight, the piggymask and the BatchNorm's affine parameters."""
-    from cpg_amd.models import fused_bn as fb
-    monkeypatch.setattr(fb, 'FUSE_STEM_WGRAD', wgrad_in_pass)      # the weight gradient inside the apply pass, or gy written + cpg_conv2d_wgrad
-    g = torch.Generator().manual_seed(7 * N + H)
-    x = torch.randn(N, C, H, W, generator=g)
-    w0 = torch.randn(K, C, 3, 3, generator=g) * 0.3
-    pm0 = torch.rand(K, C, 3, 3, generator=g) * 0.012 if pm else None
-    gam, bet = torch.rand(K, generator=g) + 0.5, torch.randn(K, generator=g) * 0.2
-    gz = torch.randn(N, K, H, W, generator=g)
-    res = {}
-    for fused in (True, False):
-        seq = fb.FusedSequential(nl.SharableConv2d(C, K, 3, padding=1, bias=False), nn.BatchNorm2d(K), nn.ReLU(inplace=True)).to(DEV)
-        seq[0].weight.data.copy_(w0)
-        if pm:
-            seq[0].piggymask = nn.Parameter(pm0.clone().to(DEV))
-        seq[1].weight.data.copy_(gam)
-        seq[1].bias.data.copy_(bet)
-        seq.train()
-        old = fb.FUSE_STEM
-        fb.FUSE_STEM = fused
-        try:
-            z = seq(x.to(DEV))
-            z.backward(gz.to(DEV))
-        finally:
-            fb.FUSE_STEM = old
-        res[fused] = [z.detach().clone(), seq[0].weight.grad.clone(), seq[1].weight.grad.clone(), seq[1].bias.grad.clone(),
-                      seq[1].running_mean.clone(), seq[1].running_var.clone(), seq[1].num_batches_tracked.clone()]
-        if pm:
-            res[fused].append(seq[0].piggymask.grad.clone())
-        if fused:
-            assert type(z.grad_fn).__name__ == '_StemConvBnReluFnBackward', type(z.grad_fn).__name__     # the fused path really ran
-    for a, b in zip(res[True], res[False]):
-        sc = float(b.double().abs().max()) + 1e-12
-        assert float((a.double() - b.double()).abs().max()) <= 2e-5 * sc, (float((a.double() - b.double()).abs().max()), sc)
-    assert torch.equal(res[True][0], res[False][0])                # same statistics tiles, same arithmetic: the output is bit-identical
-    # fp64 torch reference of the whole triple
-    xd = x.double().to(DEV)
-    weff = (w0 * ((pm0 > 5e-3).float() if pm else 1.0)).double().to(DEV).requires_grad_(True)
-    gd, bd = gam.double().to(DEV).requires_grad_(True), bet.double().to(DEV).requires_grad_(True)
-    zr = torch.relu(torch.nn.functional.batch_norm(torch.nn.functional.conv2d(xd, weff, padding=1), None, None, gd, bd, True, 0.1, 1e-5))
-    zr.backward(gz.double().to(DEV))
-    assert float((res[True][0].double() - zr.detach()).abs().max()) <= 2e-5 * float(zr.detach().abs().max())
-    gw_ref = weff.grad * ((pm0 > 5e-3).double().to(DEV) if pm else 1.0)
-    for got, want in ((res[True][1], gw_ref), (res[True][2], gd.grad), (res[True][3], bd.grad)):
-        assert float((got.double() - want).abs().max()) <= 1e-4 * (float(want.abs().max()) + 1e-9)
+    PC.fused_stem_conv_bn_relu_matches_unfused(N, C, H, W, pm, wgrad_in_pass, K, monkeypatch)
 
 
 def test_pointwise_random_shapes_vs_torch():
@@ -635,78 +473,12 @@ def test_winograd_wgrad_shared_chip_hint_full_batch(C, K, H):
     assert float((g1 - g0).abs().max()) < 1e-5 * sc and not torch.equal(g1, g0)
 
 
-@pytest.mark.parametrize('N,C,K,H,bias', [(256, 256, 256, 14, True),      # SphereNet-20 conv3_x: 784 four-wave blocks = 3.06 rounds (16 left: 16 pieces each)
-                                          (256, 512, 512, 14, False),     # VGG16 features.34: 6.125 rounds (32 blocks left: 8 pieces)
-                                          (200, 192, 192, 14, True),      # two-wave blocks (three 64-channel blocks): 921 blocks = 1.8 rounds -> no tail
-                                          (29, 250, 192, 28, True),       # two-wave blocks, 534 = 1.04 rounds; ragged channels (250 read: the last chunk overlaps)
-                                          (11, 96, 128, 56, False)])      # 270 four-wave blocks; the tail starts in the middle of image 10
+@pytest.mark.parametrize('N,C,K,H,bias', PC.WINOGRAD_TAIL_CASES)
 def test_winograd_tail_pieces_equal_the_single_launch(N, C, K, H, bias, libopt):
     """k_wg3<.., SPLIT> + k_wg_tail_reduce (the leftover units of a Winograd launch's last round, cut along the channel loop) against the
     same launch without the tail (CPG_WINO_TAIL=0, round 4's plan): forward and input gradient agree to fp32 round-off of a different
     association of the channel sum, the tail path repeats bit for bit, and the images of the full rounds keep their bits.  Sampled entries are recomputed from the definition in fp64 (they fall in the tail: the LAST images of the batch)."""
-    import ctypes
-    from cpg_amd import _lib
-    lib = _lib.lib()
-    g = torch.Generator(device=DEV).manual_seed(N + C + K + H)
-    x = torch.randn(N, C, H, H, generator=g, device=DEV)
-    w = torch.randn(K, C, 3, 3, generator=g, device=DEV) * (2.0 / (C * 9)) ** 0.5
-    b = torch.randn(K, generator=g, device=DEV) * 0.1 if bias else None
-    gy = torch.randn(N, K, H, H, generator=g, device=DEV)
-    layer = nl.SharableConv2d(C, K, 3, padding=1, bias=bias).to(DEV)
-    layer.weight.data.copy_(w)
-    if bias:
-        layer.bias.data.copy_(b)
-    d = nl._conv_desc(x.shape, w.shape, (1, 1), (1, 1), (1, 1), 1)
-
-    def run():
-        xd = x.clone().requires_grad_(True)
-        y = layer(xd)
-        y.backward(gy)
-        return y.detach().clone(), xd.grad.clone()
-    y1, gx1 = run()
-    y1b, gx1b = run()
-    assert torch.equal(y1, y1b) and torch.equal(gx1, gx1b)                 # fixed-order sum of the pieces
-    libopt.set('CPG_WINO_TAIL', 0)
-    y0, gx0 = run()
-    libopt.set('CPG_WINO_TAIL', None)
-    has_tail = (N, C, K, H) != (200, 192, 192, 14)                         # (1.8 rounds: the leftover is more than half a round -- one launch)
-    for a, ref in ((y1, y0), (gx1, gx0)):
-        sc = float(ref.abs().max())
-        assert float((a - ref).abs().max()) <= 2e-6 * sc
-    if not has_tail:
-        assert torch.equal(y1, y0) and torch.equal(gx1, gx0)
-    else:
-        # another association of the channel sum: the tail really ran (in the forward, the input gradient or both: they are planned apart)
-        assert not (torch.equal(y1, y0) and torch.equal(gx1, gx0))
-        head = max(1, N // 2)
-        assert torch.equal(y1[:head], y0[:head]) and torch.equal(gx1[:head], gx0[:head])       # the full rounds are untouched
-    if not bias:
-        # ... and the forward WITH the BatchNorm statistics epilogue: the tail's statistics come from k_wg_tail_reduce<true>
-        with torch.no_grad():
-            ys1, st1 = layer.forward_with_bn_stats(x)
-            ys1b, st1b = layer.forward_with_bn_stats(x)
-            libopt.set('CPG_WINO_TAIL', 0)
-            ys0, st0 = layer.forward_with_bn_stats(x)
-            libopt.set('CPG_WINO_TAIL', None)
-        assert torch.equal(ys1, ys1b) and torch.equal(st1, st1b) and st1.shape == st0.shape
-        assert float((ys1 - ys0).abs().max()) <= 2e-6 * float(ys0.abs().max())
-        # per channel: sum and sum of squares over all statistics tiles (the tiles' own sums differ in association only)
-        t1, t0 = st1.double().sum(1), st0.double().sum(1)
-        assert float((t1 - t0).abs().max()) <= 1e-5 * float(t0.abs().max())
-        want = torch.stack([ys0.double().sum((0, 2, 3)), (ys0.double() ** 2).sum((0, 2, 3))], 1)
-        assert float((t1 - want).abs().max()) <= 1e-5 * float(want.abs().max())
-        assert float((st1 - st0).abs().max()) <= 1e-4 * float(st0.abs().max())
-    rs = np.random.RandomState(N + H)
-    xp = torch.nn.functional.pad(x, (1, 1, 1, 1)).double()
-    gyp = torch.nn.functional.pad(gy, (1, 1, 1, 1)).double()
-    wd = w.double()
-    for _ in range(24):
-        n, k, c = N - 1 - rs.randint(min(N, 3)), rs.randint(K), rs.randint(C)
-        h, ww = rs.randint(H), rs.randint(H)
-        want = float((xp[n, :, h:h + 3, ww:ww + 3] * wd[k]).sum()) + (float(b[k]) if bias else 0.0)
-        assert abs(float(y1[n, k, h, ww]) - want) <= 1e-4 * abs(want) + 2e-5
-        want = float((gyp[n, :, h:h + 3, ww:ww + 3].flip(-1, -2) * wd[:, c]).sum())
-        assert abs(float(gx1[n, c, h, ww]) - want) <= 1e-4 * abs(want) + 2e-5
+    PC.winograd_tail_pieces_equal_the_single_launch(N, C, K, H, bias, libopt)
 
 
 
@@ -778,42 +550,9 @@ def test_direct_weight_gradients_under_the_shared_chip_hint(N, C, K, H, ks, stri
     assert float((g0 - ref).abs().max()) < 1e-5 * sc and float((g1 - ref).abs().max()) < 1e-5 * sc
 
 
-@pytest.mark.parametrize('B,I,O,pm', [(32, 25088, 512, False), (256, 4096, 4096, True), (7, 513, 129, True), (1, 64, 5, False),
-                                      (256, 4096, 4096, False), (100, 1024, 256, False), (48, 260, 384, False),
-                                      # features.45 of config 2 at its own shape (89 % of all masked weights), both mask modes,
-                                      # and at the per-GPU batch of the 8-GPU reference configuration / the validate batch
-                                      (256, 25088, 4096, False), (256, 25088, 4096, True), (32, 25088, 4096, True), (100, 25088, 4096, False),
-                                      # the grown network's FC layers (raw multiplier 1.5: 627 * 49 -> int(4096 * sqrt(1.5)) = 5016; odd row length)
-                                      (32, 30723, 5016, True), (16, 5016, 5016, False),
-                                      # <= 64 rows (the reference's own 256 / 8 split): the weight-streaming input gradient and the 32- / 64-row forward
-                                      # tiles -- ragged column tiles, row counts that leave waves without work, one and two row fragments
-                                      (32, 25088, 4096, False), (64, 4096, 4096, True), (33, 4100, 1000, False), (8, 132, 18, True), (64, 1028, 50, False)])
+@pytest.mark.parametrize('B,I,O,pm', PC.LINEAR_ORACLE_CASES)
 def test_linear_oracle(B, I, O, pm):
-    g = torch.Generator().manual_seed(B + I + O)
-    x = torch.randn(B, I, generator=g)
-    w = torch.randn(O, I, generator=g) * I ** -0.5
-    b = torch.randn(O, generator=g) * 0.1
-    pmv = torch.rand(O, I, generator=g) * 0.012 if pm else None
-    layer = nl.SharableLinear(I, O).to(DEV)
-    layer.weight.data.copy_(w)
-    layer.bias.data.copy_(b)
-    if pm:
-        layer.piggymask = nn.Parameter(pmv.to(DEV))
-    xd = x.to(DEV).requires_grad_(True)
-    y = layer(xd)
-    close(y, ops.linear_forward(x.numpy(), w.numpy(), None if pmv is None else pmv.numpy(), b.numpy()), rtol=1e-4, atol=2e-5)
-    gy = torch.randn(B, O, generator=g)
-    y.backward(gy.to(DEV))
-    r = ops.linear_backward(x.numpy(), w.numpy(), gy.numpy(), None if pmv is None else pmv.numpy())
-    # absolute floor = 1e-5 of the tensor's scale: an element that is a near-cancelling sum of B (or I) terms carries the
-    # round-off of its addends, not of its own magnitude
-    def floor(a):
-        return max(2e-5, 1e-5 * float(np.abs(a).max()))
-    close(xd.grad, r['gx'], rtol=1e-4, atol=floor(r['gx']), msg='gx')
-    close(layer.weight.grad, r['gw'], rtol=1e-4, atol=floor(r['gw']), msg='gw')
-    close(layer.bias.grad, r['gb'], rtol=1e-4, atol=1e-4, msg='gb')
-    if pm:
-        close(layer.piggymask.grad, r['gpm'], rtol=1e-4, atol=floor(r['gpm']), msg='gpm')
+    PC.linear_oracle(B, I, O, pm)
 
 
 # --------------------------------------------------------------------------- opt-in bf16 MFMA path
@@ -947,39 +686,6 @@ def test_conv_math_switch_is_opt_in():
 
 
 # --------------------------------------------------------------------------- pruner pieces vs golden
-class TinyNet(nn.Module):
-    def __init__(self, datasets):
-        super().__init__()
-        self.datasets = datasets
-        self.conv = nl.SharableConv2d(3, 4, 3, padding=1, bias=False)
-        self.fc = nl.SharableLinear(6, 5)
-
-
-class Wrap(nn.Module):
-    def __init__(self, m):
-        super().__init__()
-        self.module = m
-
-    def forward(self, x):
-        return self.module(x)
-
-
-def make_pruner(mode, datasets, dataset, owners, weights, begin=0, end=100, freq=10, initial=0.0, target=0.1, wd=4e-5,
-                width=1.0, finetune_again=False, piggymasks=None):
-    net = TinyNet(list(datasets)).to(DEV)
-    net.conv.weight.data.copy_(T(weights['conv']))
-    net.fc.weight.data.copy_(T(weights['fc']))
-    net.fc.bias.data.zero_()
-    if piggymasks is not None:
-        net.conv.piggymask = nn.Parameter(T(piggymasks['conv']))
-        net.fc.piggymask = nn.Parameter(T(piggymasks['fc']))
-    model = Wrap(net)
-    masks = {'module.conv': T(owners['conv'], torch.uint8), 'module.fc': T(owners['fc'], torch.uint8)}
-    args = types.SimpleNamespace(mode=mode, dataset=dataset, finetune_again=finetune_again, target_sparsity=target,
-                                 initial_sparsity=initial, pruning_frequency=freq, weight_decay=wd, network_width_multiplier=width)
-    return SparsePruner(model, masks, args, begin, end, list(datasets).index(dataset) + 1), model, masks
-
-
 ROUTE = {'finetune_t3': ('finetune', ['a', 'b', 'c'], 'c', False), 'prune_t2': ('prune', ['a', 'b', 'c'], 'b', False),
          'finetune_again_t2': ('finetune', ['a', 'b', 'c'], 'b', True), 'prune_t1_nopm': ('prune', ['a'], 'a', False),
          'finetune_t1_nopm': ('finetune', ['a'], 'a', False)}
@@ -1095,70 +801,16 @@ def test_stats_and_mask_ops_golden():
 
 def test_mask_kernels_ragged_sizes_vs_oracle():
     """odd lengths / unaligned tails through every elementwise kernel"""
-    for n in (1, 3, 5, 17, 255, 1025, 4099, 70001):
-        g = torch.Generator().manual_seed(n)
-        w = torch.randn(n, generator=g)
-        gw = torch.randn(n, generator=g)
-        gpm = torch.randn(n, generator=g)
-        owner = torch.randint(0, 5, (n,), generator=g, dtype=torch.uint8)
-        pm = torch.rand(n, generator=g) * 0.012
-        conv = {'conv': w.numpy().reshape(1, 1, 1, n) * 0 if False else np.zeros((4, 3, 3, 3), np.float32), 'fc': np.zeros((5, 6), np.float32)}
-        zo = {'conv': np.zeros((4, 3, 3, 3), np.uint8), 'fc': np.zeros((5, 6), np.uint8)}
-        pruner, model, masks = make_pruner('finetune', ['a', 'b', 'c'], 'c', zo, conv)
-        # swap the conv layer's tensors for 1-D ones of length n
-        mod = model.module.conv
-        mod.weight = nn.Parameter(w.to(DEV))
-        mod.piggymask = nn.Parameter(pm.to(DEV))
-        mod.weight.grad = gw.to(DEV)
-        mod.piggymask.grad = gpm.to(DEV)
-        model.module.fc.piggymask = nn.Parameter(torch.zeros(5, 6, device=DEV))
-        masks['module.conv'] = owner.to(DEV)
-        pruner.current_dataset_idx = 3
-        pruner.do_weight_decay_and_make_grads_zero()
-        wg, wp = ops.route_grads(gw.numpy(), w.numpy(), owner.numpy(), 3, 4e-5, gpm.numpy(), 'finetune')
-        np.testing.assert_allclose(mod.weight.grad.cpu().numpy(), wg, rtol=3e-7, atol=0)
-        np.testing.assert_array_equal(mod.piggymask.grad.cpu().numpy(), wp)
-        owners = [owner.numpy(), zo['fc']]
-        assert pruner.calculate_sparsity() == ops.sparsity(owners, 3)
-        assert pruner.calculate_shared_part_ratio() == ops.shared_part_ratio(owners, [pm.numpy(), np.zeros((5, 6), np.float32)], 3)
-        pruner.inference_dataset_idx = 2
-        pruner.apply_mask()
-        np.testing.assert_array_equal(mod.weight.data.cpu().numpy(), ops.apply_mask(w.numpy(), owner.numpy(), 2))
-        pruner.current_dataset_idx = 3
-        pruner.make_finetuning_mask()
-        np.testing.assert_array_equal(masks['module.conv'].cpu().numpy(), ops.claim_free(owner.numpy(), 4))
+    for n in PC.MASK_KERNEL_SIZES:
+        PC.mask_kernels_ragged_size_vs_oracle(n)
 
 
-@pytest.mark.parametrize('n', [1, 3, 1023, 1024, 1025, 70_001, 3_000_001])
+@pytest.mark.parametrize('n', PC.PACK_UNPACK_SIZES)
 @pytest.mark.parametrize('select', [0, 1])
 def test_gradient_pack_unpack_equals_boolean_indexing(n, select):
     """cpg_owned_block_counts / cpg_pack_owned / cpg_unpack_owned (the data-parallel payload compaction): packed ==
     g[selected] in natural order, the scatter restores exactly the selected slots and leaves the others alone."""
-    import ctypes
-    from cpg_amd import _lib as L
-    lib = L.lib()
-    g = torch.Generator().manual_seed(n + select)
-    owner = torch.randint(0, 4, (n,), generator=g, dtype=torch.uint8).to(DEV)
-    grad = torch.randn(n, generator=g).to(DEV)
-    cur = 2
-    sel = (owner == cur) if select == 0 else ((owner > 0) & (owner < cur))
-    nblk = int(lib.cpg_owned_num_blocks(n))
-    assert nblk == (n + 1023) // 1024
-    counts = torch.empty(nblk, dtype=torch.int32, device=DEV)
-    s = L.stream_ptr()
-    L.check('counts', lib.cpg_owned_block_counts(L.dptr(owner, torch.uint8), cur, select, n, ctypes.c_void_p(counts.data_ptr()), s))
-    want_counts = torch.nn.functional.pad(sel.int(), (0, nblk * 1024 - n)).view(nblk, 1024).sum(1).int()
-    assert torch.equal(counts, want_counts)
-    ends = torch.cumsum(counts, 0, dtype=torch.int64)
-    offs = (ends - counts).contiguous()
-    total = int(ends[-1])
-    assert total == int(sel.sum())
-    packed = torch.full((max(total, 1),), float('nan'), device=DEV)
-    L.check('pack', lib.cpg_pack_owned(L.dptr(grad), L.dptr(owner, torch.uint8), cur, select, n, ctypes.c_void_p(offs.data_ptr()), L.dptr(packed), s))
-    assert torch.equal(packed[:total], grad[sel])
-    out = torch.full((n,), -7.0, device=DEV)
-    L.check('unpack', lib.cpg_unpack_owned(L.dptr(packed * 2), L.dptr(owner, torch.uint8), cur, select, n, ctypes.c_void_p(offs.data_ptr()), L.dptr(out), s))
-    assert torch.equal(out[sel], grad[sel] * 2) and bool((out[~sel] == -7.0).all())
+    PC.gradient_pack_unpack_equals_boolean_indexing(n, select)
 
 
 def test_owner_id_uint8_extremes_vs_oracle():
@@ -1192,14 +844,7 @@ def test_owner_id_uint8_extremes_vs_oracle():
     np.testing.assert_array_equal(do.cpu().numpy(), ops.claim_free(owner.numpy(), 255))
     assert lib.cpg_claim_free(L.dptr(do, torch.uint8), 256, n, s) == -1          # not a uint8 owner id
     # rank prune for task 255
-    do = owner.to(DEV)
-    res = torch.zeros(4, dtype=torch.int64, device=DEV)
-    ws, nb = L.workspace(lib.cpg_rank_prune_workspace_bytes(), DEV)
-    assert lib.cpg_rank_prune(L.dptr(w.to(DEV)), L.dptr(do, torch.uint8), 255, 0.3, n, ctypes.c_void_p(res.data_ptr()), L.dptr(ws), nb, s) == 0
-    want, k, cutoff = ops.rank_prune(w.numpy(), owner.numpy(), 255, 0.3)
-    np.testing.assert_array_equal(do.cpu().numpy(), want)
-    rec = L.PruneResult.from_buffer_copy(res.cpu().numpy().tobytes())
-    assert rec.k == k and rec.cutoff == np.float32(cutoff) and rec.status == 0
+    PC.rank_prune_vs_oracle(w, owner, 255, 0.3)
 
 
 # --------------------------------------------------------------------------- whole networks vs golden
@@ -1768,34 +1413,11 @@ def test_linear_full_size_properties(B, I, O, pm_on):
         assert int(((layer.weight.grad != 0) & (keep == 0)).sum()) == 0
 
 
-@pytest.mark.parametrize('seed', range(12))
+@pytest.mark.parametrize('seed', PC.LINEAR_SMALL_BATCH_SEEDS)
 def test_linear_small_batch_random_shapes(seed):
     """Seeded random shapes at <= 64 rows (row lengths a multiple of 4: the weight-streaming input gradient; every output count: units
     that leave waves or whole splits without rows), with and without a piggymask: y, gx, gW, gPM against fp64."""
-    rs = np.random.RandomState(1000 + seed)
-    B, I, O, pm_on = int(rs.randint(1, 65)), 4 * int(rs.randint(1, 700)), int(rs.randint(1, 900)), bool(seed % 2)
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    x = torch.randn(B, I, generator=g, device=DEV, requires_grad=True)
-    w = torch.randn(O, I, generator=g, device=DEV) * I ** -0.5
-    gy = torch.randn(B, O, generator=g, device=DEV)
-    layer = nl.SharableLinear(I, O).to(DEV)
-    layer.weight.data.copy_(w)
-    layer.bias.data.zero_()
-    keep = 1.0
-    if pm_on:
-        pm = torch.rand(O, I, generator=g, device=DEV) * 0.012
-        layer.piggymask = nn.Parameter(pm.clone())
-        keep = (pm > 5e-3).double()
-    y = layer(x)
-    y.backward(gy)
-    weff = w.double() * keep
-    gweff = gy.double().t() @ x.detach().double()
-    checks = [(y.detach(), x.detach().double() @ weff.t(), 'y'), (x.grad, gy.double() @ weff, 'gx'), (layer.weight.grad, gweff * keep, 'gw')]
-    if pm_on:
-        checks.append((layer.piggymask.grad, gweff * w.double(), 'gpm'))
-    for got, want, name in checks:
-        sc = max(float(want.abs().max()), 1e-30)
-        assert float((got.double() - want).abs().max()) <= 1e-5 * sc, (name, B, I, O, pm_on)
+    PC.linear_small_batch_random_shapes(seed)
 
 
 @pytest.mark.parametrize('B,I,O', [(256, 25088, 512), (5, 33, 7), (32, 516, 10)])
@@ -1859,29 +1481,7 @@ def test_linear_small_batch_paths_equal_the_batch_256_paths(B, I, O, pm_on):
 
 
 # --------------------------------------------------------------------------- fused BatchNorm -> ReLU
-def _bn_relu_cases():
-    """(training, N, C, H, W, misaligned), with the ids of the two stacked parametrize decorators these cases grew out of."""
-    shapes = [(8, 64, 56, 56), (4, 16, 224, 224), (16, 512, 14, 14), (3, 5, 7, 9), (2, 3, 1, 1),
-              # planes of >= 16 * 256 items that are no multiple of 4: the scalar large-plane walk, and with 129 x 129 its 16-trip flush
-              (2, 3, 65, 65), (1, 2, 129, 129)]
-    cases = [(t,) + s + (False,) for s in shapes for t in (True, False)]
-    # one slice of >= 64 * 256 items of planes under 4096 items: the 64-visit flush of the flattened small-plane walk (134 MB a tensor)
-    cases.append((True, 34, 2048, 21, 23, False))
-    # input and incoming gradient 4 bytes off a 16-byte boundary: the scalar paths of apply, reduce and backward-apply at 4 | HW
-    cases += [(t, 2, 3, 8, 8, True) for t in (True, False)]
-    return [pytest.param(*c, id='%s-%d-%d-%d-%d' % c[:5] + ('-misaligned' if c[5] else '')) for c in cases]
-
-
-def _off_by_4_bytes(t):
-    """A copy of `t` on the device whose first element lies 4 bytes past a 16-byte boundary."""
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)
-    assert buf.data_ptr() % 16 == 0
-    v = buf[1:].view(t.shape)
-    v.copy_(t)
-    return v
-
-
-@pytest.mark.parametrize('training,N,C,H,W,misaligned', _bn_relu_cases())
+@pytest.mark.parametrize('training,N,C,H,W,misaligned', PC.bn_relu_cases())
 def test_fused_bn_relu_matches_torch(N, C, H, W, training, misaligned):
     """Fused BatchNorm2d -> ReLU against torch's fp32 modules: output, gradients, running statistics.
 
@@ -1891,146 +1491,30 @@ def test_fused_bn_relu_matches_torch(N, C, H, W, training, misaligned):
     (23 of 33282 outside, the largest by 1.07e-5), while torch's own kernel is within 4.8e-7 / 6.5e-7 of fp64 there and the fused pass
     within 3.5e-7 / 6.5e-7.  At 2x3x64x64 and 4x16x224x224 the library, torch's kernel and the fused pass are all within 1e-6 of fp64, torch's
     kernel never the farthest: the check asks no less at any shape."""
-    from cpg_amd.models.fused_bn import bn_relu
-    g = torch.Generator().manual_seed(N * C + H)
-    x = (torch.randn(N, C, H, W, generator=g) * 2.0 + 0.5)
-    gy = torch.randn(N, C, H, W, generator=g)
-    place = _off_by_4_bytes if misaligned else (lambda t: t.to(DEV))
-    ref_bn, bn = nn.BatchNorm2d(C).to(DEV), nn.BatchNorm2d(C).to(DEV)
-    for m in (ref_bn, bn):
-        m.weight.data.copy_(torch.linspace(0.5, 1.5, C))
-        m.bias.data.copy_(torch.linspace(-0.3, 0.3, C))
-        m.running_mean.copy_(torch.linspace(-0.1, 0.1, C))
-        m.running_var.copy_(torch.linspace(0.8, 1.2, C))
-        m.train(training)
-    if N * H * W == 1 and training:
-        pytest.skip('torch rejects a single value per channel in training mode')
-    xr = x.to(DEV).requires_grad_(True)
-    xf = place(x).requires_grad_(True)
-    with torch.backends.cudnn.flags(enabled=False):
-        yr = torch.relu(ref_bn(xr))
-    yf = bn_relu(xf, bn, relu=True)
-    close(yf, yr.detach().cpu().numpy(), rtol=1e-4, atol=1e-5, msg='y')
-    yr.backward(gy.to(DEV))
-    yf.backward(place(gy))
-    gscale = float(xr.grad.abs().max()) + 1e-12
-    close(xf.grad, xr.grad.cpu().numpy(), rtol=1e-3, atol=2e-5 * max(1.0, gscale), msg='gx')
-    close(bn.weight.grad, ref_bn.weight.grad.cpu().numpy(), rtol=1e-3, atol=1e-3, msg='dgamma')
-    close(bn.bias.grad, ref_bn.bias.grad.cpu().numpy(), rtol=1e-3, atol=1e-3, msg='dbeta')
-    close(bn.running_mean, ref_bn.running_mean.cpu().numpy(), rtol=1e-5, atol=1e-6, msg='running_mean')
-    close(bn.running_var, ref_bn.running_var.cpu().numpy(), rtol=1e-5, atol=1e-6, msg='running_var')
-    assert int(bn.num_batches_tracked) == int(ref_bn.num_batches_tracked)
+    PC.fused_bn_relu_matches_torch(N, C, H, W, training, misaligned)
 
 
 # (block-per-plane, wave-per-plane and the flattened small-plane walk of the backward passes)
-@pytest.mark.parametrize('N,C,H,W', [(4, 64, 56, 56), (2, 16, 224, 224), (8, 512, 14, 14), (3, 5, 6, 10), (2, 3, 2, 2), (2, 8, 112, 112),
-                                     (3, 7, 28, 28), (2, 5, 4, 8), (1, 2, 2, 4),
-                                     # 16 384 windows a plane: the 16-trip flush inside the large-plane walk of the reduction
-                                     (1, 2, 256, 256)])
+@pytest.mark.parametrize('N,C,H,W', PC.BN_RELU_POOL_SHAPES)
 @pytest.mark.parametrize('training', [True, False])
 def test_fused_bn_relu_pool_matches_torch(N, C, H, W, training):
-    from cpg_amd.models.fused_bn import bn_relu_pool
-    g = torch.Generator().manual_seed(N * C + H + 1)
-    x = (torch.randn(N, C, H, W, generator=g) * 2.0 + 0.3)
-    gy = torch.randn(N, C, H // 2, W // 2, generator=g)
-    ref_bn, bn = nn.BatchNorm2d(C).to(DEV), nn.BatchNorm2d(C).to(DEV)
-    for m in (ref_bn, bn):
-        m.weight.data.copy_(torch.linspace(0.5, 1.5, C))
-        m.bias.data.copy_(torch.linspace(-0.3, 0.3, C))
-        m.running_mean.copy_(torch.linspace(-0.1, 0.1, C))
-        m.running_var.copy_(torch.linspace(0.8, 1.2, C))
-        m.train(training)
-    xr = x.to(DEV).requires_grad_(True)
-    xf = x.to(DEV).requires_grad_(True)
-    yr = nn.functional.max_pool2d(torch.relu(ref_bn(xr)), 2, 2)
-    yf = bn_relu_pool(xf, bn)
-    close(yf, yr.detach().cpu().numpy(), rtol=1e-4, atol=1e-5, msg='y')
-    yr.backward(gy.to(DEV))
-    yf.backward(gy.to(DEV))
-    gscale = float(xr.grad.abs().max()) + 1e-12
-    close(xf.grad, xr.grad.cpu().numpy(), rtol=1e-3, atol=2e-5 * max(1.0, gscale), msg='gx')
-    close(bn.weight.grad, ref_bn.weight.grad.cpu().numpy(), rtol=1e-3, atol=1e-3, msg='dgamma')
-    close(bn.bias.grad, ref_bn.bias.grad.cpu().numpy(), rtol=1e-3, atol=1e-3, msg='dbeta')
-    close(bn.running_mean, ref_bn.running_mean.cpu().numpy(), rtol=1e-5, atol=1e-6, msg='running_mean')
-    close(bn.running_var, ref_bn.running_var.cpu().numpy(), rtol=1e-5, atol=1e-6, msg='running_var')
+    PC.fused_bn_relu_pool_matches_torch(N, C, H, W, training)
 
 
-@pytest.mark.parametrize('N,C,H,W', [(4, 16, 56, 56), (2, 64, 112, 112), (3, 5, 7, 9), (2, 3, 1, 1), (2, 8, 16, 15)])
+@pytest.mark.parametrize('N,C,H,W', PC.BN_RELU_POOL3_SHAPES)
 @pytest.mark.parametrize('training', [True, False])
 def test_fused_bn_relu_pool3_matches_torch(N, C, H, W, training):
     """BatchNorm2d -> ReLU -> MaxPool2d(3, 2, 1) (the ResNet stem's tail, models/resnet.py:127-129) as one forward and two backward
     kernels against the stock modules: pooled output, input gradient (arg-max routing with torch's first-maximum rule, also among
     the zeros ReLU produces), BatchNorm parameter gradients and running statistics."""
-    from cpg_amd.models import fused_bn
-    torch.manual_seed(N + C + H)
-    bn_a, bn_b = nn.BatchNorm2d(C).to(DEV), nn.BatchNorm2d(C).to(DEV)
-    with torch.no_grad():
-        bn_a.weight.uniform_(0.5, 1.5)
-        bn_a.bias.uniform_(-0.5, 0.5)
-        bn_a.running_mean.normal_(0, 0.3)
-        bn_a.running_var.uniform_(0.5, 2.0)
-    bn_b.load_state_dict(bn_a.state_dict())
-    bn_a.train(training)
-    bn_b.train(training)
-    pool, relu = nn.MaxPool2d(3, 2, 1), nn.ReLU(inplace=True)
-    x0 = torch.randn(N, C, H, W, device=DEV) * 1.5 + 0.2
-    xa, xb = x0.clone().requires_grad_(True), x0.clone().requires_grad_(True)
-    assert fused_bn._is_pool3(pool)
-    ya = fused_bn.conv_bn_act_pool(lambda t: t, bn_a, relu, pool, xa)
-    assert ya.grad_fn is not None and 'Pool3' in type(ya.grad_fn).__name__
-    yb = pool(relu(bn_b(xb)))
-    np.testing.assert_allclose(ya.detach().cpu().numpy(), yb.detach().cpu().numpy(), rtol=1e-5, atol=1e-6)
-    gy = torch.randn_like(yb)
-    ya.backward(gy)
-    yb.backward(gy)
-    sc = float(xb.grad.abs().max()) + 1e-12
-    np.testing.assert_allclose(xa.grad.cpu().numpy(), xb.grad.cpu().numpy(), rtol=1e-4, atol=2e-5 * sc + 2e-6)
-    for pa, pb in ((bn_a.weight, bn_b.weight), (bn_a.bias, bn_b.bias)):
-        sc = float(pb.grad.abs().max()) + 1e-12
-        np.testing.assert_allclose(pa.grad.cpu().numpy(), pb.grad.cpu().numpy(), rtol=1e-4, atol=1e-5 * sc)
-    np.testing.assert_allclose(bn_a.running_mean.cpu().numpy(), bn_b.running_mean.cpu().numpy(), rtol=1e-5, atol=1e-6)
-    np.testing.assert_allclose(bn_a.running_var.cpu().numpy(), bn_b.running_var.cpu().numpy(), rtol=1e-5, atol=1e-6)
+    PC.fused_bn_relu_pool3_matches_torch(N, C, H, W, training)
 
 
-@pytest.mark.parametrize('N,C,H,W,relu,add', [(4, 128, 4, 4, 1, 0), (4, 64, 4, 4, 1, 0), (4, 128, 2, 2, 1, 0), (4, 16, 16, 16, 1, 0),
-                                               (4, 32, 8, 8, 1, 0), (4, 256, 4, 4, 0, 0), (4, 256, 4, 4, 0, 1), (4, 512, 2, 2, 0, 1),
-                                               (8, 64, 56, 56, 1, 0)])
+@pytest.mark.parametrize('N,C,H,W,relu,add', PC.BN_SMALL_PLANES_CASES)
 def test_fused_bn_small_planes_fp64(N, C, H, W, relu, add):
     """The fused BatchNorm (+ReLU / +residual+ReLU) kernels on the small planes of the ResNet tail (16 ... 1024 samples per
     channel) against an fp64 torch reference: output, dx, dgamma, dbeta within 1e-6 of scale."""
-    from cpg_amd.models import fused_bn
-    g = torch.Generator().manual_seed(N * C + H + relu + 2 * add)
-    x = torch.randn(N, C, H, W, generator=g) * 2 + torch.randn(1, C, 1, 1, generator=g)
-    gy = torch.randn(N, C, H, W, generator=g)
-    res = torch.randn(N, C, H, W, generator=g) if add else None
-    bn = nn.BatchNorm2d(C)
-    bn.weight.data = torch.rand(C, generator=g) + 0.5
-    bn.bias.data = torch.randn(C, generator=g) * 0.3
-    bn64 = nn.BatchNorm2d(C).double()
-    bn64.load_state_dict({k: v.double() if v.dtype.is_floating_point else v for k, v in bn.state_dict().items()})
-    x64 = x.double().requires_grad_(True)
-    r64 = res.double().requires_grad_(True) if add else None
-    y64 = bn64(x64)
-    if add:
-        y64 = y64 + r64
-    if relu or add:
-        y64 = torch.relu(y64)
-    y64.backward(gy.double())
-    bnd = bn.to(DEV).train()
-    xd = x.to(DEV).requires_grad_(True)
-    rd = res.to(DEV).requires_grad_(True) if add else None
-    act = nn.ReLU(inplace=True)
-    yd = fused_bn.bn_add_act(bnd, act, xd, rd) if add else fused_bn.bn_act(bnd, act if relu else None, xd)
-    yd.backward(gy.to(DEV))
-
-    def rel(a, b):
-        return float((a.double().cpu() - b.double()).abs().max() / (b.double().abs().max() + 1e-30))
-    assert rel(yd.detach(), y64.detach()) < 1e-6
-    assert rel(xd.grad, x64.grad) < 1e-6
-    assert rel(bnd.weight.grad, bn64.weight.grad) < 1e-6 and rel(bnd.bias.grad, bn64.bias.grad) < 1e-6
-    if add:
-        assert rel(rd.grad, r64.grad) < 1e-6
-    np.testing.assert_allclose(bnd.running_var.cpu().numpy(), bn64.running_var.float().numpy(), rtol=1e-5)
+    PC.fused_bn_small_planes_fp64(N, C, H, W, relu, add)
 
 
 @pytest.mark.parametrize('algo', ['direct', 'winograd'])
@@ -2303,40 +1787,12 @@ def test_resnet_block_fused_bn_equals_stock_bn(block, stride):
         assert float(np.abs(g1[n] - g0[n]).max()) <= 1e-3 * sc, n
 
 
-@pytest.mark.parametrize('N,C,H,W', [(6, 24, 28, 28), (3, 16, 56, 56), (5, 8, 14, 14), (2, 8, 7, 7), (130, 4, 12, 20)])
+@pytest.mark.parametrize('N,C,H,W', PC.BN_ADD_RELU_MASK_SHAPES)
 def test_bn_add_relu_byte_mask_equals_reading_the_output(N, C, H, W, monkeypatch):
     """relu(bn(x) + res), the tail of a residual block: with the forward's byte mask (one byte per four outputs, round 4) the backward
     must produce what it produces from the saved output -- the same masked gradient bit for bit, the same BatchNorm sums; shapes whose
     plane is not a multiple of 4 (7 x 7) have no mask and take the old path."""
-    from cpg_amd.models import fused_bn
-    g = torch.Generator().manual_seed(N * C + H)
-    x = torch.randn(N, C, H, W, generator=g).to(DEV)
-    res = torch.randn(N, C, H, W, generator=g).to(DEV)
-    gy = torch.randn(N, C, H, W, generator=g).to(DEV)
-    outs = {}
-    for use_mask in (True, False):
-        monkeypatch.setattr(fused_bn, 'RELU_BYTE_MASK', use_mask)
-        bn = nn.BatchNorm2d(C).to(DEV).train()
-        with torch.no_grad():
-            bn.weight.copy_(torch.linspace(0.5, 1.5, C))
-            bn.bias.copy_(torch.linspace(-0.3, 0.3, C))
-        xd, rd = x.clone().requires_grad_(True), res.clone().requires_grad_(True)
-        y = fused_bn.bn_add_act(bn, nn.ReLU(), xd, rd)
-        y.backward(gy)
-        outs[use_mask] = (y.detach().clone(), xd.grad.clone(), rd.grad.clone(), bn.weight.grad.clone(), bn.bias.grad.clone())
-    # output and masked gradient: exactly equal; the BatchNorm sums run through differently compiled copies of the same expression
-    # (a select feeding a fused multiply-add): equal to the last bits
-    assert torch.equal(outs[True][0], outs[False][0]) and torch.equal(outs[True][2], outs[False][2])
-    for a, b in zip(outs[True], outs[False]):
-        assert float((a - b).abs().max()) <= 1e-6 * float(b.abs().max())
-    bn = nn.BatchNorm2d(C).to(DEV).train().double()
-    with torch.no_grad():
-        bn.weight.copy_(torch.linspace(0.5, 1.5, C))
-        bn.bias.copy_(torch.linspace(-0.3, 0.3, C))
-    yr = torch.relu(bn(x.double()) + res.double())
-    assert float((outs[True][0].double() - yr).abs().max()) <= 2e-5 * float(yr.abs().max())
-    # the residual's gradient is the masked gradient itself: exactly gy where the output is positive, exactly 0 elsewhere
-    assert torch.equal(outs[True][2], torch.where(outs[True][0] > 0, gy, torch.zeros_like(gy)))
+    PC.bn_add_relu_byte_mask_equals_reading_the_output(N, C, H, W, monkeypatch)
 
 
 def test_conv_prelu_bias_gradient_from_the_prelu_backward():
@@ -2487,39 +1943,10 @@ def test_skip_gradient_in_the_winograd_input_gradient_epilogue(N, C, K, H):
             assert abs(float(a1[1][n, c, h, w_]) - want) <= 1e-4 * abs(want) + 2e-5
 
 
-@pytest.mark.parametrize('N,C,H,W,shared', [(8, 64, 56, 56, False), (5, 12, 7, 9, False), (3, 16, 28, 28, True), (2, 3, 1, 1, False),
-                                            # a plane of >= 4096 items that is no multiple of 4: block-per-plane forward, scalar large-plane walk
-                                            (2, 3, 65, 65, False)])
+@pytest.mark.parametrize('N,C,H,W,shared', PC.PRELU_BACKWARD_CASES)
 def test_prelu_backward_matches_torch(N, C, H, W, shared):
     """cpg_prelu_bwd (one pass, deterministic slope reduction) against torch's PReLU backward."""
-    from cpg_amd.models import fused_bn
-    g = torch.Generator().manual_seed(N * 100 + C)
-    x = torch.randn(N, C, H, W, generator=g).to(DEV)
-    gy = torch.randn(N, C, H, W, generator=g).to(DEV)
-    mod = nn.PReLU(1 if shared else C).to(DEV)
-    with torch.no_grad():
-        mod.weight.copy_(torch.rand(mod.weight.shape, generator=g) - 0.3)
-    res0 = torch.randn(N, C, H, W, generator=g).to(DEV)
-    for with_res in (False, True):          # with_res: SphereNet's `x + relu(conv(y))` -- the residual add folded into the forward pass
-        out = {}
-        for enabled in (True, False):
-            fused_bn.ENABLED = enabled
-            try:
-                xi = x.clone().requires_grad_(True)
-                ri = res0.clone().requires_grad_(True)
-                mod.zero_grad()
-                y = fused_bn.prelu(mod, xi, res=ri if with_res else None)
-                y.backward(gy)
-            finally:
-                fused_bn.ENABLED = True
-            out[enabled] = (y.detach().cpu().numpy(), xi.grad.cpu().numpy(), mod.weight.grad.cpu().numpy(),
-                            ri.grad.cpu().numpy() if with_res else None)
-        np.testing.assert_allclose(out[True][0], out[False][0], rtol=0, atol=0 if not with_res else 1e-6)
-        np.testing.assert_array_equal(out[True][1], out[False][1])
-        sc = float(np.abs(out[False][2]).max()) + 1e-12
-        np.testing.assert_allclose(out[True][2], out[False][2], rtol=1e-4, atol=1e-5 * sc)
-        if with_res:
-            np.testing.assert_array_equal(out[True][3], out[False][3])
+    PC.prelu_backward_matches_torch(N, C, H, W, shared)
 
 
 @pytest.mark.parametrize('N,C,K,H,W,pool', [(4, 16, 64, 56, 56, False), (6, 64, 128, 28, 28, True), (5, 32, 160, 14, 14, True),
