@@ -708,6 +708,10 @@ extern "C" int cpg_conv2d_fwd_bnstats(const cpg_conv_desc *d, const float *x, co
                                       void *stream) {
     PackScope scope;
     PoolMaxScope pool_scope;
+    {   // the descriptor's verdict first, as in every entry point: a malformed one is CPG_E_INVALID, not "no fused kernel"
+        ConvGeom g;
+        if (const int rc = make_geom(d, g)) return rc;
+    }
     if (const cpg::PoolMaxCtx &pc = cpg::pool_max_ctx(); pc.armed) {
         if (bias != nullptr || !cpg_conv2d_fwd_pool_max_supported(d))
             return fail(CPG_E_INVALID, "cpg_conv2d_fwd_bnstats: window maxima are attached but this launch cannot write them "

@@ -153,7 +153,25 @@ int cpg_binarize_mask_weight(const float *w, const float *pm, float thr, float *
  *         and input gradient 1.2 - 3 x slower: per group those run the Winograd kernels) and for strided layers (input gradient
  *         2.5 - 4.6 x slower).  The library does not reroute these; a caller with such layers is better served by per-group calls,
  *         as cpg_amd's SharableConv2d does.
- * Every entry point validates the descriptor first, then the pointers (NULL: CPG_E_INVALID), then launches. */
+ * Every entry point validates the descriptor first, then the pointers (NULL: CPG_E_INVALID), then launches.
+ * Alignment, the general rule (the entries below state it only where they ask for more):
+ *   - ELEMENT alignment (4 bytes) is all the tensors of cpg_conv2d_fwd / _fwd_bnstats / _dgrad / _wgrad and of cpg_linear_fwd /
+ *     _dgrad / _wgrad need: x, w, pm, bias, y, gy, gx, gw, gpm, gb and the statistics buffer.  A batch slice of a tensor whose rows
+ *     are an odd number of floats long is a legal argument.  The kernels that can use 16-byte accesses (pointwise, grouped, the bias
+ *     gradient, the small-batch and GEMM-shaped linear kernels) test the pointer and the row length per call and take their
+ *     per-element flavour otherwise: the same contraction, the fp32 sums possibly in another order.  The Winograd, direct 3x3,
+ *     3x3 s2, stem and generic implicit-GEMM kernels test nothing and need nothing: the same bits on any element-aligned pointer.
+ *   - 16 BYTES are required, and checked, of `workspace` by every conv launch that uses it (CPG_E_INVALID; the linear
+ *     entry points take a kernel that needs no workspace instead), of the packed operands of cpg_conv2d_pack /
+ *     cpg_conv2d_use_packed, and of the four pointers of cpg_conv2d_wgrad_attach_bn_bwd.  One tensor among the first group can
+ *     ask for them: x of cpg_conv2d_fwd_bnstats on a pointwise layer under the wide tile (CPG_PW_TILE=1, A/B tooling, not the
+ *     default), whose statistics buffer is sized for that tile -- CPG_E_INVALID otherwise, nothing launched.
+ *   - Not covered by this rule: the residual / addend of the fused epilogues (cpg_conv2d_dgrad_add, _fwd_bn_eval_add,
+ *     _fwd_prelu_eval) and the BatchNorm, PReLU and loss-head entry points; pass those 16-byte aligned tensors.
+ *   tests/test_conv_descriptor_space_gpu.py runs the first group one and three floats off alignment: the inputs (x, gy, w, pm, bias)
+ *   through the layers, the outputs (y, the statistics buffer, gx, gw, gpm, gb) through direct calls of the conv entry points and of
+ *   cpg_linear_dgrad.  Not run there, so a promise from reading the code alone: y of cpg_linear_fwd and gw / gpm / gb of
+ *   cpg_linear_wgrad off alignment, and the linear layers' GEMM routes that need >= 192 output tiles. */
 size_t cpg_conv2d_workspace_bytes(const cpg_conv_desc *d);
 int cpg_conv2d_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm,
                    float thr, const float *bias, float *y, void *ws, size_t ws_bytes, void *stream);

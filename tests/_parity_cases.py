@@ -62,6 +62,55 @@ def close(got, want, rtol=1e-4, atol=1e-5, msg=''):
     np.testing.assert_allclose(got, want, rtol=rtol, atol=atol, err_msg=msg)
 
 
+def running_stats_close(got, want, msg=''):
+    """The bar for BatchNorm running statistics that come out of a conv epilogue's partial sums (test_conv_epilogue_bn_statistics
+    and the descriptor-space body of tests/_conv_space_cases.py): one definition."""
+    close(got, want, rtol=1e-5, atol=1e-6, msg=msg)
+
+
+def skip_gradient_fused_equals_plain(conv, x0, gy, gs):
+    """A conv whose input also feeds an identity branch: through forward_with_skip the two gradients of the input meet inside the
+    input-gradient kernel (cpg_conv2d_dgrad_add).  The fused entry point is really the one that runs, and y, gx and the parameter
+    gradients equal the plain composition's to 1e-6 of their scale.  conv, x0, gy, gs (the skip branch's gradient) on the device;
+    returns the fused run's (y, gx, gw[, gpm])."""
+    from cpg_amd import _lib
+    calls = []
+    L = _lib.lib()
+    raw = L.cpg_conv2d_dgrad_add
+
+    class Spy(object):
+        def __getattr__(self, name):
+            if name == 'cpg_conv2d_dgrad_add':
+                def f(*a):
+                    calls.append(1)
+                    return raw(*a)
+                return f
+            return getattr(L, name)
+    res = {}
+    for fused in (True, False):
+        conv.zero_grad()
+        x = x0.clone().requires_grad_(True)
+        if fused:
+            old, _lib._lib = _lib._lib, Spy()
+            try:
+                y, stats, skip = conv.forward_with_skip(x)
+                (y * gy).sum().backward(retain_graph=True, inputs=[conv.weight])       # conv branch alone first: no addend yet
+                conv.zero_grad()
+                ((y * gy).sum() + (skip * gs).sum()).backward()
+            finally:
+                _lib._lib = old
+        else:
+            y = conv(x)
+            ((y * gy).sum() + (x * gs).sum()).backward()
+        res[fused] = (y.detach().clone(), x.grad.clone(), conv.weight.grad.clone()) + (
+            () if conv.piggymask is None else (conv.piggymask.grad.clone(),))
+    assert calls, 'the fused input-gradient entry point did not run'
+    for a, b in zip(res[True], res[False]):
+        sc = float(b.abs().max())
+        assert float((a - b).abs().max()) <= 1e-6 * sc
+    return res[True]
+
+
 # --------------------------------------------------------------------------- conv / linear vs oracle
 CONV_ORACLE_CASES = [
     (4, 64, 56, 56, 128, 3, 1, 1, False, False),     # VGG mid layer (3x3 s1 p1), several tiles

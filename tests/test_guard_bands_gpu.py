@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import _conv_space_cases as CS
 import _eval_block_cases as EB
 import _eval_conv_cases as EC
 import _guarded as G
@@ -140,6 +141,19 @@ def test_grouped_conv_guarded(row):
     per_group = nl.SharableConv2d(C, K, k, stride=s, padding=p, groups=G)._per_group()       # one groups == 1 launch per group + torch.cat
     with guarding() as led:
         finish(led, PC.grouped_conv_vs_oracle(*row, buf=BUF), assembled_by_torch=per_group)
+
+
+@pytest.mark.parametrize('cid', list(CS.CASE_BY_ID))
+def test_conv_descriptor_space_guarded(cid):
+    """The hand table of tests/_conv_space_cases.py -- near misses of every fast class, the generic family's branches, degenerate
+    geometry, grouped layers off the templates -- between guard bands: a workspace query that under-sizes an unusual descriptor, or a
+    tile that assumes its class's geometry, writes outside its payload."""
+    from cpg_amd.models import layers as nl
+    c = CS.CASE_BY_ID[cid]
+    per_group = c.G > 1 and nl.SharableConv2d(c.C, c.K, (c.R, c.S), stride=(c.sh, c.sw), padding=(c.ph, c.pw), dilation=(c.dh, c.dw),
+                                              groups=c.G)._per_group()
+    with guarding() as led:
+        finish(led, CS.conv_space(c, buf=BUF), assembled_by_torch=per_group)
 
 
 def test_winograd_tail_guarded(libopt):
