@@ -215,6 +215,26 @@ def call(name, *args):
         check(name, rc)
 
 
+def call_armed(arms, name, *args):
+    """call() of ONE entry point with the calling thread armed first; arms: (attach entry point, its arguments) pairs, each made through
+    call() under its own name.  The library disarms itself inside the entry point that consumes a value; if anything raises on the way
+    there (a later arm that is refused, an interrupt) or in it, every channel of `arms` is disarmed again (NULL pointers and zeros, on
+    the library handle directly), so that no LATER call of this thread picks up a value that was not meant for it."""
+    try:
+        for arm, arm_args in arms:
+            call(arm, *arm_args)
+        call(name, *args)
+    except BaseException:
+        for arm, _ in arms:
+            getattr(lib(), arm)(*(None if t is _vp else 0 for t in _SIGNATURES[arm][1]))
+        raise
+
+
+def use_packed(pk):
+    """The arm of call_armed for a packed weight operand (None: no arm)."""
+    return () if pk is None else (('cpg_conv2d_use_packed', (dptr(pk), pk.numel() * 4)),)
+
+
 OPT_UNSET = -(1 << 31)
 _WINO_KERNEL = {'block': 0, 'wave': 1, 'pair': 2, '64': 3}
 

@@ -815,23 +815,19 @@ inline bool wave_windows(const PoolDims &p) { return p.wins < 1024; }
 }  // namespace
 
 // The window maxima E[N][C][H/2][W/2] of x that a caller attached for the next pooled call of its thread (cpg_bn_relu_pool_attach_max):
-// taken -- and the thread disarmed -- by cpg_bn_relu_pool_fwd / _bwd, whatever they return.  *E = null: nothing attached.
-static int take_pool_max(const char *what, int32_t N, int32_t C, int32_t H, int32_t W, const float **E) {
-    cpg::PoolMaxCtx &pc = cpg::bn_pool_max_ctx();
-    const cpg::PoolMaxCtx got = pc;
-    pc = cpg::PoolMaxCtx{};
-    *E = nullptr;
-    if (!got.armed) return CPG_OK;
+// taken (cpg_common.h, "side arguments") by cpg_bn_relu_pool_fwd / _bwd as their first act, so that nothing stays armed whatever they
+// return; this is the check that the buffer is the tensor's.  got.E = null: nothing was attached.
+static int pool_max_fits(const char *what, const cpg::PoolMax &got, int32_t N, int32_t C, int32_t H, int32_t W) {
+    if (got.E == nullptr) return CPG_OK;
     CPG_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && got.bytes >= (size_t)N * C * (H / 2) * (W / 2) * sizeof(float),
                 "%s: the window maxima attached (%zu bytes) are not this tensor's", what, got.bytes);
-    *E = got.E;
     return CPG_OK;
 }
 extern "C" int cpg_bn_relu_pool_attach_max(const float *E, size_t bytes) {
-    cpg::bn_pool_max_ctx() = cpg::PoolMaxCtx{};
-    if (E == nullptr) return CPG_OK;             // (disarms)
+    cpg::arm_bn_max({});                         // (NULL, and a refused attach, disarm)
+    if (E == nullptr) return CPG_OK;
     CPG_REQUIRE((((uintptr_t)E) & 3) == 0 && bytes > 0, "cpg_bn_relu_pool_attach_max: needs a 4-byte aligned, non-empty buffer");
-    cpg::bn_pool_max_ctx() = cpg::PoolMaxCtx{true, const_cast<float *>(E), bytes};
+    cpg::arm_bn_max({const_cast<float *>(E), bytes});
     return CPG_OK;
 }
 
@@ -865,9 +861,9 @@ extern "C" int cpg_bn_relu_pool_fwd(const float *x, const float *gamma, const fl
                                     float *running_mean, float *running_var, float *mean, float *invstd, float *y_pooled,
                                     int32_t N, int32_t C, int32_t H, int32_t W, int32_t train, void *ws, size_t ws_bytes,
                                     void *stream_v) {
-    const float *E;
-    if (const int rc = take_pool_max("cpg_bn_relu_pool_fwd", N, C, H, W, &E)) return rc;
-    return bnp_fwd("cpg_bn_relu_pool_fwd", x, E, nullptr, 0, gamma, beta, eps, momentum, running_mean, running_var, nullptr, mean, invstd, y_pooled,
+    const cpg::PoolMax got = cpg::take_bn_max();
+    if (const int rc = pool_max_fits("cpg_bn_relu_pool_fwd", got, N, C, H, W)) return rc;
+    return bnp_fwd("cpg_bn_relu_pool_fwd", x, got.E, nullptr, 0, gamma, beta, eps, momentum, running_mean, running_var, nullptr, mean, invstd, y_pooled,
                    N, C, H, W, train, ws, ws_bytes, stream_v);
 }
 
@@ -901,9 +897,9 @@ static int bnp_bwd(const char *what, const float *x, const float *E, const float
 extern "C" int cpg_bn_relu_pool_bwd(const float *x, const float *g_pooled, const float *gamma, const float *beta,
                                     const float *mean, const float *invstd, float *gx, float *dgamma, float *dbeta, int32_t N,
                                     int32_t C, int32_t H, int32_t W, int32_t train, void *ws, size_t ws_bytes, void *stream_v) {
-    const float *E;
-    if (const int rc = take_pool_max("cpg_bn_relu_pool_bwd", N, C, H, W, &E)) return rc;
-    return bnp_bwd("cpg_bn_relu_pool_bwd", x, E, g_pooled, gamma, beta, mean, invstd, gx, dgamma, dbeta, N, C, H, W, train, ws, ws_bytes, stream_v);
+    const cpg::PoolMax got = cpg::take_bn_max();
+    if (const int rc = pool_max_fits("cpg_bn_relu_pool_bwd", got, N, C, H, W)) return rc;
+    return bnp_bwd("cpg_bn_relu_pool_bwd", x, got.E, g_pooled, gamma, beta, mean, invstd, gx, dgamma, dbeta, N, C, H, W, train, ws, ws_bytes, stream_v);
 }
 
 // The same pair with the window maxima E[N][C][H/2][W/2] of x as an argument (the conv that produced x wrote them:

@@ -1104,12 +1104,14 @@ inline size_t pack_bytes(int c_read, int m) { return (pack_floats(c_read, m) + l
 
 // What a forward / input-gradient call does besides y = conv(x).  Filled field by field; everything is optional.
 struct C3Extra {
+    cpg::PackedOperand packed;      // the caller's packed operand, for the Winograd launch (every other route packs for itself)
     float *stats = nullptr;         // forward: [m][tiles][2] BatchNorm partial sums of y; with bb: the BatchNorm-backward partial sums
     const cpg::EvalEpilogue *eval = nullptr;    // forward: the inference epilogue (its kind picks the BatchNorm or the PRE instances)
     const char *what = nullptr;     // ... and the public entry point that asked for it, for messages
     bool skip = false;              // ... with the dead-channel skip: the pack writes the workspace's liveness words, the kernel reads them
     int *live = nullptr;            // ... those words (run_fwd finds them in the workspace)
     const C3BnBwd *bb = nullptr;    // input gradient: BatchNorm-backward reduction of the layer below in the epilogue
+    float *pool_max = nullptr;      // forward with stats: receives the 2x2 window maxima of y (the Winograd launch; cpg_conv2d_fwd_bnstats has checked it)
 };
 
 // The kernels' parameter block from the descriptor (null: no inference epilogue) -- the one place that knows which name of a pair each kind fills.
@@ -1247,7 +1249,7 @@ int run_fwd(bool dgrad, int N, int c_read, int m, int H, int W, int K, int C, co
     C3Extra ex = extra;             // (ex.live is filled in below)
     const C3Plan plan = plan_fwd(dgrad, N, c_read, m, H, W, ex.bb ? C3_BN_BWD : ex.eval ? C3_BN_EVAL : ex.stats ? C3_STATS : C3_PLAIN);
     if (plan.route == C3_WINO)
-        return cpg_conv3x3_wino_run(dgrad ? 1 : 0, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, ex.stats, ws, ws_bytes, stream);
+        return cpg_conv3x3_wino_run_side(dgrad ? 1 : 0, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, ex.stats, ws, ws_bytes, stream, ex.packed, ex.pool_max);
     // Workspace layout of the Winograd inference forward:
     // [the direct kernels' packed-weight region (unused) | liveness words, where cpg_conv3x3_fwd_eval looks for them | U]
     if (plan.route == C3_WINO_EVAL) {
@@ -1303,18 +1305,19 @@ size_t cpg_conv3x3_pack_workspace(const cpg_conv_desc *d) {
 }
 
 int cpg_conv3x3_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                    float *y, void *ws, size_t ws_bytes, hipStream_t stream) {
+                    float *y, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed) {
     CPG_REQUIRE(x && w && y, "cpg_conv2d_fwd: null pointer");
-    return run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, x, w, pm, thr, bias, y, ws, ws_bytes, stream);
+    return run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, x, w, pm, thr, bias, y, ws, ws_bytes, stream, C3Extra{packed});
 }
 
 // forward that also writes the per-(channel, pixel tile) BatchNorm partial sums; tiles = cpg_conv3x3_bnstats_tiles(d)
 int cpg_conv3x3_bnstats_tiles(const cpg_conv_desc *d) { return plan_fwd(false, d->N, d->C, d->K, d->H, d->W, C3_STATS).tiles; }
 int cpg_conv3x3_fwd_bnstats(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                            float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream) {
+                            float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed, float *pool_max) {
     CPG_REQUIRE(x && w && y && stats, "cpg_conv2d_fwd_bnstats: null pointer");
-    C3Extra ex;
+    C3Extra ex{packed};
     ex.stats = stats;
+    ex.pool_max = pool_max;
     return run_fwd(false, d->N, d->C, d->K, d->H, d->W, d->K, d->C, x, w, pm, thr, bias, y, ws, ws_bytes, stream, ex);
 }
 
@@ -1365,10 +1368,10 @@ bool cpg_conv3x3_pack_job(const cpg_conv_desc *d, int dgrad, cpg::PackJob *job) 
 }
 
 int cpg_conv3x3_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
-                      size_t ws_bytes, hipStream_t stream) {
+                      size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed) {
     CPG_REQUIRE(gy && w && gx, "cpg_conv2d_dgrad: null pointer");
     // reads gy (K channels), produces gx (C channels)
-    return run_fwd(true, d->N, d->K, d->C, d->H, d->W, d->K, d->C, gy, w, pm, thr, nullptr, gx, ws, ws_bytes, stream);
+    return run_fwd(true, d->N, d->K, d->C, d->H, d->W, d->K, d->C, gy, w, pm, thr, nullptr, gx, ws, ws_bytes, stream, C3Extra{packed});
 }
 
 // input gradient whose epilogue also does the BatchNorm-backward reduction of the layer below (see C3BnBwd).  tiles = 0: this
@@ -1481,9 +1484,9 @@ static int w3_launch(const cpg_conv_desc *d, const float *x, const float *gy, co
 }
 
 int cpg_conv3x3_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr,
-                      float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream) {
+                      float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::WgradRider &rider) {
     // Winograd F(2x2, 3x3) weight gradient (conv3x3_wino_wgrad.hip): maps 14 or a multiple of 28 wide, channel counts multiples of 32
-    if (cpg_conv3x3_wino_wgrad_ok(d)) return cpg_conv3x3_wino_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream);
+    if (cpg_conv3x3_wino_wgrad_ok(d)) return cpg_conv3x3_wino_wgrad_side(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream, rider);
     Epilogue ep{gw, nullptr, BIAS_NONE, 1, 1, pm, w, gpm, thr};
     if (d->C <= WSCfg::CMAX) {
         const WSPlan p = ws_plan(d);

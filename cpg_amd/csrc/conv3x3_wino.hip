@@ -2147,9 +2147,11 @@ static int wino_run_block(int dgrad, int N, int c_read, int m, int H, int W, int
 // y[N][m][H][W] = conv3x3(x[N][c_read][H][W], W .* bin(pm)) (+ bias); dgrad: x = gy, the filter transposed and flipped.
 // w is the layer's [K][C][3][3] weight.  stats (forward only, may be null): [m][tiles][2] partial sums for the BatchNorm.
 // ep (forward only, may be null): the inference epilogue, with live (may be null), the liveness words of its dead-channel skip.
+// packed: for the one- and two-wave launches without ep.  pool_max (may be null; cpg_conv2d_fwd_bnstats has checked it): receives the window maxima of y.
 static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
                     float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream,
-                    const cpg::EvalEpilogue *ep, const float *addend = nullptr, int *live = nullptr);
+                    const cpg::EvalEpilogue *ep, const cpg::PackedOperand &packed = cpg::PackedOperand(), float *pool_max = nullptr,
+                    const float *addend = nullptr, int *live = nullptr);
 
 // The kernels' parameter block from the descriptor (null: no inference epilogue) -- the one place that knows which name of a pair each kind fills.
 static WgBnEval wg_epilogue(const cpg::EvalEpilogue *ep, int *live, int m) {
@@ -2168,17 +2170,22 @@ extern "C" int cpg_conv3x3_wino_run(int dgrad, int N, int c_read, int m, int H, 
                                     void *ws, size_t ws_bytes, hipStream_t stream) {
     return wino_run(dgrad, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, stats, ws, ws_bytes, stream, nullptr);
 }
+int cpg_conv3x3_wino_run_side(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
+                              float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream,
+                              const cpg::PackedOperand &packed, float *pool_max) {
+    return wino_run(dgrad, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, stats, ws, ws_bytes, stream, nullptr, packed, pool_max);
+}
 
 // input gradient + addend (gx = dgrad(gy) + addend): the two-wave kernel's launches (>= 64 channels on both sides, or an odd map)
 extern "C" int cpg_conv3x3_wino_dgrad_add_ok(int N, int c_read, int m, int H, int W) {
     if (!cpg_conv3x3_wino_ok(N, c_read, m, H, W)) return 0;
     return (((H | W) & 1) || wino_variant(c_read, m, false) == WV_PAIR64) ? 1 : 0;
 }
-extern "C" int cpg_conv3x3_wino_dgrad_add(int N, int c_read, int m, int H, int W, int K, int C, const float *gy, const float *w, const float *pm,
-                                          float thr, const float *addend, float *gx, void *ws, size_t ws_bytes, hipStream_t stream) {
+int cpg_conv3x3_wino_dgrad_add(int N, int c_read, int m, int H, int W, int K, int C, const float *gy, const float *w, const float *pm, float thr,
+                               const float *addend, float *gx, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed) {
     if (!cpg_conv3x3_wino_dgrad_add_ok(N, c_read, m, H, W) || addend == nullptr)
         return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_dgrad_add(winograd): shape not supported");
-    return wino_run(1, N, c_read, m, H, W, K, C, gy, w, pm, thr, nullptr, gx, nullptr, ws, ws_bytes, stream, nullptr, addend);
+    return wino_run(1, N, c_read, m, H, W, K, C, gy, w, pm, thr, nullptr, gx, nullptr, ws, ws_bytes, stream, nullptr, packed, nullptr, addend);
 }
 
 // 1: a forward launch with statistics of this shape can also write the 2x2 window maxima of its output (k_wg3<.., PMAX>): the two-wave
@@ -2205,12 +2212,12 @@ int cpg_conv3x3_wino_run_eval(int N, int C, int K, int H, int W, const float *x,
         hipError_t e = hipMemsetAsync(live, 0, live_words * sizeof(int), stream);
         if (e != hipSuccess) return hip_status(e, what);
     }
-    return wino_run(0, N, C, K, H, W, K, C, x, w, pm, thr, bias, y, nullptr, ws, ws_bytes, stream, &ep, nullptr, live);
+    return wino_run(0, N, C, K, H, W, K, C, x, w, pm, thr, bias, y, nullptr, ws, ws_bytes, stream, &ep, cpg::PackedOperand(), nullptr, nullptr, live);
 }
 
 static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
                     float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream,
-                    const cpg::EvalEpilogue *ep, const float *addend, int *live) {
+                    const cpg::EvalEpilogue *ep, const cpg::PackedOperand &packed, float *pool_max, const float *addend, int *live) {
     const char *what = dgrad ? "cpg_conv2d_dgrad(winograd)" : "cpg_conv2d_fwd(winograd)";
     // addend (input-gradient launches of the two-wave kernel only: cpg_conv3x3_wino_dgrad_add_ok): added to the result in the epilogue
     // (k_wg3<.., ADD>; the tail pieces' share in k_wg_tail_reduce)
@@ -2226,12 +2233,11 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
         wino_geom(g, N, c_read, m, H, W);
         float *up = (float *)ws;
         const WgBnEval none{}, bne = wg_epilogue(ep, live, m);
-        const float *pre = nullptr;
-        if (ep == nullptr) {       // (the inference epilogue's pack also writes the liveness flags: never taken from a caller's operand)
-            if (const int rc = cpg::take_packed(need, &pre, what)) return rc;
-        }
-        if (pre != nullptr) {
-            up = const_cast<float *>(pre);
+        // (the inference epilogue's pack also writes the liveness flags: never taken from a caller's operand)
+        const cpg::PackedOperand pre = ep == nullptr ? packed : cpg::PackedOperand();
+        if (const int rc = cpg::packed_fits(pre, need, what)) return rc;
+        if (pre.data != nullptr) {
+            up = const_cast<float *>(pre.data);
         } else {
             const cpg::PackJob job = wino_pack_job(dgrad, c_read, m, K, C);
             hipLaunchKernelGGL(k_wg1_pack, dim3(stream_grid(job.total, 256)), dim3(256), 0, stream, w, pm, thr, up, K, C, m, c_read, job.c,
@@ -2240,15 +2246,9 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
         const int64_t runs = (g.tiles_total + W1_T - 1) / W1_T;
         const bool persist = wino_persist();
         WgMode mode = ep != nullptr ? (ep->kind == cpg::EvalEpilogue::PRELU ? WG_FWD_PRE : WG_FWD_BNE) : dgrad ? (addend != nullptr ? WG_DGRAD_ADD : WG_DGRAD) : stats != nullptr ? WG_FWD_STATS : WG_FWD;
-        // the window maxima a caller attached (cpg_conv2d_fwd_attach_pool_max; cpg_conv2d_fwd_bnstats has checked the buffer's size)
-        float *pool_e = nullptr;
-        if (cpg::PoolMaxCtx &pc = cpg::pool_max_ctx(); pc.armed && mode == WG_FWD_STATS) {
-            if (bias != nullptr || !cpg_conv3x3_wino_pool_max_ok(N, c_read, m, H, W) ||
-                pc.bytes < (size_t)N * m * (H / 2) * (W / 2) * sizeof(float))
-                return fail(CPG_E_INVALID, "%s: window maxima are attached but this launch cannot write them (cpg_conv2d_fwd_pool_max_supported, no bias)", what);
-            pool_e = pc.E, pc.armed = false;
-            mode = WG_FWD_STATS_PMAX;
-        }
+        // the window maxima a caller attached (cpg_conv2d_fwd_attach_pool_max): E rides in the bias slot of the PMAX instances
+        float *const pool_e = mode == WG_FWD_STATS ? pool_max : nullptr;
+        if (pool_e != nullptr) mode = WG_FWD_STATS_PMAX;
         const WgLaunch whole{g, x, up, mode == WG_DGRAD_ADD ? addend : pool_e != nullptr ? pool_e : bias, y, stats, bne, stream};
         int rc;
         if (variant == WV_PAIR64) {

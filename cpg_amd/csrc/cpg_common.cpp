@@ -3,6 +3,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
+#include <utility>
 
 namespace cpg {
 
@@ -18,25 +19,25 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
-static thread_local PackCtx g_pack = {};
-PackCtx &pack_ctx() { return g_pack; }
-static thread_local WgradRider g_rider = {};
-WgradRider &wgrad_rider() { return g_rider; }
-static thread_local PoolMaxCtx g_pool_max = {};
-PoolMaxCtx &pool_max_ctx() { return g_pool_max; }
-static thread_local PoolMaxCtx g_bn_pool_max = {};
-PoolMaxCtx &bn_pool_max_ctx() { return g_bn_pool_max; }
+// what the attach entry points armed on this thread (cpg_common.h, "side arguments")
+static thread_local struct {
+    PackedOperand operand;
+    PoolMax conv_max, bn_max;
+    WgradRider rider;
+} g_sides;
+void arm_operand(PackedOperand v) { g_sides.operand = v; }
+void arm_conv_max(PoolMax v) { g_sides.conv_max = v; }
+void arm_bn_max(PoolMax v) { g_sides.bn_max = v; }
+void arm_rider(const WgradRider &v) { g_sides.rider = v; }
+PackedOperand take_operand() { return std::exchange(g_sides.operand, {}); }
+PoolMax take_conv_max() { return std::exchange(g_sides.conv_max, {}); }
+PoolMax take_bn_max() { return std::exchange(g_sides.bn_max, {}); }
+WgradRider take_rider() { return std::exchange(g_sides.rider, {}); }
 
-int take_packed(size_t bytes, const float **pre, const char *what) {
-    PackCtx &c = g_pack;
-    *pre = nullptr;
-    if (!c.armed) return CPG_OK;
-    if (c.use == nullptr || c.use_bytes != bytes || (((uintptr_t)c.use) & 15) != 0)
-        return fail(CPG_E_INVALID, "%s: the packed operand handed in (%zu bytes) is not the one this launch streams (%zu bytes, 16-byte aligned)",
-                    what, c.use_bytes, bytes);
-    *pre = c.use;
-    c.armed = false;
-    return CPG_OK;
+int packed_fits(const PackedOperand &p, size_t bytes, const char *what) {
+    if (p.data == nullptr || (p.bytes == bytes && (((uintptr_t)p.data) & 15) == 0)) return CPG_OK;
+    return fail(CPG_E_INVALID, "%s: the packed operand handed in (%zu bytes) is not the one this launch streams (%zu bytes, 16-byte aligned)",
+                what, p.bytes, bytes);
 }
 
 // Process-wide: the weight-gradient planners that read it run inside autograd's backward, i.e. on the engine's per-device worker

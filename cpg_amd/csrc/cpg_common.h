@@ -64,9 +64,8 @@ inline int opt_or(Opt o, int dflt) { const int v = opt(o); return v == OPT_UNSET
 // ---- packed weight operands handed in by the caller (include/cpg_hip.h: cpg_conv2d_pack / cpg_conv2d_use_packed, ABI 3) ------------
 // The pointwise and the one-/two-wave Winograd kernels stream the effective weight W * bin(pm) from a packed copy that every call used
 // to produce into its own workspace first.  A caller may now produce it ONCE (and the forward's and the input gradient's in one launch)
-// and hand it to the calls that need it.  The plumbing is a per-THREAD one-shot context: cpg_conv2d_use_packed arms it, the next conv
-// entry point on that thread consumes (or drops) it.  What a call of a shape would pack is a pure function of the descriptor and the
-// option table (the *_pack_job planners of cpg_dispatch.h): cpg_conv2d_pack and cpg_conv2d_pack_bytes ask them and touch no context.
+// and hand it to the calls that need it (PackedOperand, below).  What a call of a shape would pack is a pure function of the descriptor
+// and the option table (the *_pack_job planners of cpg_dispatch.h): cpg_conv2d_pack and cpg_conv2d_pack_bytes ask them.
 struct PackJob {
     int family;               // 0 none, 1 pointwise (k_pw_pack's layout), 2 Winograd per-lane U (k_wg1_pack's layout)
     int K, C;                 // the layer's weight is [K][C][R][S]
@@ -74,41 +73,32 @@ struct PackJob {
     long long total;          // work items of the pack pass
     size_t bytes;             // size of the packed operand
 };
-struct PackCtx {
-    bool armed;               // cpg_conv2d_use_packed handed `use` in and no launch has taken it yet
-    const float *use;
-    size_t use_bytes;
-};
-PackCtx &pack_ctx();          // thread-local
-// Where a launch is about to pack `bytes` of operand into its workspace: *pre = the operand the caller armed (skip the pack), or null
-// (pack as always).  < 0: the caller's operand does not fit this launch (status to return).
-int take_packed(size_t bytes, const float **pre, const char *what);
 // one launch that carries out up to two jobs (conv3x3_wino.hip)
 int pack_jobs_launch(const PackJob *ja, float *dst_a, const PackJob *jb, float *dst_b, const float *w, const float *pm, float thr,
                      hipStream_t stream);
 
-// ---- BatchNorm backward apply riding in the Winograd weight-gradient kernel (include/cpg_hip.h: cpg_conv2d_wgrad_attach_bn_bwd) ------
-// Same plumbing as the packed operands: a per-THREAD one-shot context that cpg_conv2d_wgrad_attach_bn_bwd arms and the next
-// cpg_conv2d_wgrad on that thread consumes.  table: [C][8] = {mean, invstd, gamma, beta, mean(g), mean(g xhat), invstd * gamma, 0}.
-struct WgradRider {
-    bool armed;
-    const float *y, *gz, *table;
-    float *gy;
-    int N, C, HW;
+// ---- side arguments: what the attach form of the C ABI lets a caller hand to the NEXT call of its thread -----------------------------
+// cpg_conv2d_use_packed, cpg_conv2d_fwd_attach_pool_max, cpg_conv2d_wgrad_attach_bn_bwd and cpg_bn_relu_pool_attach_max arm the calling
+// thread (include/cpg_hip.h says which entry points consume what).  The armed values live in ONE private per-thread struct in
+// cpg_common.cpp and nothing hands out a reference to it: the attach entry points arm_*() after their own checks, the consuming PUBLIC
+// entry points take_*() -- the value and the disarming in one step, so nothing stays armed whatever the call then returns -- and what
+// they call receives it as an ordinary parameter (cpg_dispatch.h).  Each channel is per thread, one-shot and independent of the others.
+// A null first pointer means "none"; arming with a default value disarms.
+struct PackedOperand { const float *data = nullptr; size_t bytes = 0; };     // the caller's packed weight operand
+struct PoolMax { float *E = nullptr; size_t bytes = 0; };                    // E[N][K][H/2][W/2]: 2x2 window maxima of a conv output
+struct WgradRider {           // the BatchNorm backward apply pass that rides in the Winograd weight-gradient kernel (the attach's argument order)
+    const float *y = nullptr, *gz = nullptr;
+    float *gy = nullptr;
+    const float *table = nullptr;      // [C][8] = {mean, invstd, gamma, beta, mean(g), mean(g xhat), invstd * gamma, 0}
+    int N = 0, C = 0, HW = 0;
 };
-WgradRider &wgrad_rider();    // thread-local
-
-// ---- 2x2 window maxima of the conv output from the Winograd forward's epilogue (include/cpg_hip.h: cpg_conv2d_fwd_attach_pool_max) ------
-// Same plumbing again: cpg_conv2d_fwd_attach_pool_max arms the calling thread, the next cpg_conv2d_fwd_bnstats on it consumes (or
-// refuses) the buffer and disarms.  E: [N][K][H/2][W/2].
-struct PoolMaxCtx {
-    bool armed;
-    float *E;
-    size_t bytes;
-};
-PoolMaxCtx &pool_max_ctx();   // thread-local
-// ... and the same buffer on its way into the pooled BatchNorm passes (cpg_bn_relu_pool_attach_max -> cpg_bn_relu_pool_fwd / _bwd)
-PoolMaxCtx &bn_pool_max_ctx();   // thread-local
+void arm_operand(PackedOperand v);   PackedOperand take_operand();
+void arm_conv_max(PoolMax v);        PoolMax take_conv_max();         // cpg_conv2d_fwd_attach_pool_max -> cpg_conv2d_fwd_bnstats
+void arm_bn_max(PoolMax v);          PoolMax take_bn_max();           // cpg_bn_relu_pool_attach_max -> cpg_bn_relu_pool_fwd / _bwd
+void arm_rider(const WgradRider &v); WgradRider take_rider();
+// A launch that is about to stream `bytes` of packed operand: CPG_OK when `p` is none (the launch packs for itself) or is that operand,
+// else the status to return.  Reads no state.
+int packed_fits(const PackedOperand &p, size_t bytes, const char *what);
 
 inline int hip_status(hipError_t e, const char *what) {
     if (e == hipSuccess) return CPG_OK;

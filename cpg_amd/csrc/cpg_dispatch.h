@@ -1,6 +1,8 @@
 // Every function of libcpg_hip.so that one translation unit defines and another calls, declared ONCE (the C ABI itself is
 // include/cpg_hip.h).  The defining file includes this header too, so a definition that drifts from its declaration is a compile
 // error (extern "C") or a link error (mangled) instead of a call with its arguments in the wrong slots.  Default arguments live here only.
+// Side arguments (cpg_common.h: what a public entry point took from the calling thread) are parameters like any other.  packed: the operand
+// a launch may stream instead of packing (none: it packs; not this launch's: CPG_E_INVALID before a launch); families without one stream none.
 // The extern "C" helpers are reachable in a CPG_EXPORT_ALL=1 build (tools/wino_bench.py, tools/wino_wgrad_bench.py); the normal
 // build exports none of them.  Only the conv / linear translation units include this header: it pulls in igemm_core.h's kernels.
 #pragma once
@@ -34,11 +36,12 @@ extern "C" int cpg_conv3x3_supported(const cpg_conv_desc *d);
 // workspace of the forward / input gradient: packed weights of either direction + the Winograd filter + its tail pieces
 size_t cpg_conv3x3_pack_workspace(const cpg_conv_desc *d);
 int cpg_conv3x3_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                    float *y, void *ws, size_t ws_bytes, hipStream_t stream);
-// forward that also writes stats[K][tiles][2], the per-(channel, pixel tile) BatchNorm partial sums; tiles = 0: not available
+                    float *y, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed);
+// forward that also writes stats[K][tiles][2], the per-(channel, pixel tile) BatchNorm partial sums; tiles = 0: not available.
+// pool_max (may be null): receives the 2x2 window maxima of y; the caller has checked cpg_conv2d_fwd_pool_max_supported, no bias, its size
 int cpg_conv3x3_bnstats_tiles(const cpg_conv_desc *d);
 int cpg_conv3x3_fwd_bnstats(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                            float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream);
+                            float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed, float *pool_max);
 // 1: the inference epilogues have a launch for this shape under the current option table (the planner's answer; 0: the channel-split tile)
 int cpg_conv3x3_eval_epilogue_ok(const cpg_conv_desc *d);
 // forward with ep folded into the epilogue, and the dead-channel skip.  Refused: BN_EVAL with a residual; PRELU where cpg_conv3x3_eval_epilogue_ok
@@ -46,7 +49,7 @@ int cpg_conv3x3_eval_epilogue_ok(const cpg_conv_desc *d);
 int cpg_conv3x3_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                          const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what);
 int cpg_conv3x3_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
-                      size_t ws_bytes, hipStream_t stream);
+                      size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed);
 // the packed operand cpg_conv3x3_fwd / _fwd_bnstats (dgrad = 0) or cpg_conv3x3_dgrad streams and a caller may hand in (cpg_conv2d_use_packed);
 // false: none (the pass runs a direct kernel, or a Winograd kernel that packs for itself)
 bool cpg_conv3x3_pack_job(const cpg_conv_desc *d, int dgrad, cpg::PackJob *job);
@@ -55,10 +58,10 @@ int cpg_conv3x3_dgrad_bnbwd_tiles(const cpg_conv_desc *d);
 int cpg_conv3x3_dgrad_bnbwd(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, const float *ypre,
                             const float *gamma, const float *beta, const float *mean, const float *invstd, float *gx, float *partials,
                             void *ws, size_t ws_bytes, hipStream_t stream);
-// weight gradient: Winograd, the <= 3-channel stem kernel or k_c3_wgrad's 64-wide input-channel tile (4..15 channels: the generic kernel)
+// weight gradient: Winograd (which alone takes a rider), the <= 3-channel stem kernel or k_c3_wgrad's 64-wide input-channel tile (4..15 channels: the generic kernel)
 size_t cpg_conv3x3_wgrad_workspace(const cpg_conv_desc *d);
 int cpg_conv3x3_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr,
-                      float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
+                      float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::WgradRider &rider);
 
 // ---- conv3x3.hip: 3x3 / stride 2 / pad 1, >= 16 channels on both sides (k_c3_fwd's strided tiles, k_c3s2_dgrad, k_c3_wgrad's strided units) ----
 // 1: ... take this shape (CPG_DISABLE_CONV3X3, CPG_NO_S2: never)
@@ -94,8 +97,12 @@ bool cpg_conv3x3_wino_pack_job(int dgrad, int N, int c_read, int m, int H, int W
 extern "C" int cpg_conv3x3_wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w,
                                     const float *pm, float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes,
                                     hipStream_t stream);
-// 1: a forward launch with statistics of this shape can also write the 2x2 window maxima of its output, to the buffer armed with
-// cpg_conv2d_fwd_attach_pool_max (the two-wave kernel on an even map, m a multiple of 64; CPG_NO_POOL_MAX: never)
+// ... with side arguments.  pool_max (may be null): receives the window maxima of y; needs stats, no bias and cpg_conv3x3_wino_pool_max_ok
+int cpg_conv3x3_wino_run_side(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
+                              float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream,
+                              const cpg::PackedOperand &packed, float *pool_max);
+// 1: a forward launch with statistics of this shape can also write the 2x2 window maxima of its output, to the buffer a caller attached
+// with cpg_conv2d_fwd_attach_pool_max (the two-wave kernel on an even map, m a multiple of 64; CPG_NO_POOL_MAX: never)
 extern "C" int cpg_conv3x3_wino_pool_max_ok(int N, int c_read, int m, int H, int W);
 // 1: the inference epilogue is available on the Winograd kernels (not on the cooperative block kernel)
 extern "C" int cpg_conv3x3_wino_eval_ok(int N, int c_read, int m, int H, int W);
@@ -106,8 +113,8 @@ int cpg_conv3x3_wino_run_eval(int N, int C, int K, int H, int W, const float *x,
                               const char *what);
 // input gradient + addend (gx = dgrad(gy) + addend): the two-wave kernel's launches (>= 64 channels on both sides, or an odd map)
 extern "C" int cpg_conv3x3_wino_dgrad_add_ok(int N, int c_read, int m, int H, int W);
-extern "C" int cpg_conv3x3_wino_dgrad_add(int N, int c_read, int m, int H, int W, int K, int C, const float *gy, const float *w, const float *pm,
-                                          float thr, const float *addend, float *gx, void *ws, size_t ws_bytes, hipStream_t stream);
+int cpg_conv3x3_wino_dgrad_add(int N, int c_read, int m, int H, int W, int K, int C, const float *gy, const float *w, const float *pm, float thr,
+                               const float *addend, float *gx, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed);
 
 // ---- conv3x3_wino_wgrad.hip: Winograd F(2x2, 3x3) weight gradient (maps 14 or a multiple of 28 wide, channel counts multiples of 32) -------
 extern "C" int cpg_conv3x3_wino_wgrad_ok(const cpg_conv_desc *d);
@@ -116,6 +123,9 @@ extern "C" int cpg_conv3x3_wino_wgrad_rider_ok(const cpg_conv_desc *d);
 extern "C" size_t cpg_conv3x3_wino_wgrad_workspace(const cpg_conv_desc *d);
 extern "C" int cpg_conv3x3_wino_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr,
                                       float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
+// ... with the rider (none: the launch above); refused where cpg_conv3x3_wino_wgrad_rider_ok says 0
+int cpg_conv3x3_wino_wgrad_side(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr,
+                                float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::WgradRider &rider);
 
 // ---- conv3x3_stem.hip: the <= 3-channel 3x3 s1 p1 stem (one persistent wave per tile, weights in registers, HBM-bound) ---------------------
 // 1: cpg_conv2d_fwd / cpg_conv2d_fwd_bnstats run this layer on the stem kernel (CPG_NO_STEM: never)
@@ -157,14 +167,14 @@ size_t cpg_conv1x1_pack_workspace(const cpg_conv_desc *d);
 cpg::PackJob cpg_conv1x1_pack_job(const cpg_conv_desc *d, int dgrad);
 // stats (may be null): [K][tiles][2] BatchNorm partial sums, tiles = cpg_conv1x1_bnstats_tiles(d)
 int cpg_conv1x1_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                    float *y, void *ws, size_t ws_bytes, hipStream_t stream, float *stats = nullptr);
+                    float *y, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed, float *stats = nullptr);
 int cpg_conv1x1_bnstats_tiles(const cpg_conv_desc *d);
 // forward with ep folded into the epilogue: BN_EVAL only (PRELU is refused), with or without a residual.  Nothing is skipped
 int cpg_conv1x1_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                         const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what);
+                         const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed, const char *what);
 // addend (may be null; stride 1 only): gx = dgrad(gy) + addend
 int cpg_conv1x1_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
-                      size_t ws_bytes, hipStream_t stream, const float *addend = nullptr);
+                      size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed, const float *addend = nullptr);
 // dense pointwise layers whose activations can be staged as aligned float4 and addressed with 31-bit byte offsets
 extern "C" int cpg_conv1x1_wgrad_supported(const cpg_conv_desc *d);
 size_t cpg_conv1x1_wgrad_workspace(const cpg_conv_desc *d);

@@ -646,20 +646,14 @@ extern "C" int cpg_conv2d_dgrad_generic(const cpg_conv_desc *d, const float *gy,
     return CPG_OK;
 }
 
-// Drops the calling thread's packed-operand context when a conv entry point returns, whether or not the launch consumed it
-// (cpg_conv2d_use_packed is one-shot).
-namespace {
-struct PackScope {
-    ~PackScope() { cpg::pack_ctx() = cpg::PackCtx{}; }
-};
-}  // namespace
-
+// The public conv entry points take what the attach form armed on the calling thread as their first statement (cpg_common.h, "side
+// arguments": taken is disarmed, so nothing survives the call whatever it returns) and pass it to the routes that can use it.
 extern "C" int cpg_conv2d_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr,
                               const float *bias, float *y, void *ws, size_t ws_bytes, void *stream) {
-    PackScope scope;
+    const cpg::PackedOperand packed = cpg::take_operand();
     const ConvRoute route = fwd_route(d);
-    if (route == ROUTE_C3) return cpg_conv3x3_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream);
-    if (route == ROUTE_C1) return cpg_conv1x1_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream);
+    if (route == ROUTE_C3) return cpg_conv3x3_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream, packed);
+    if (route == ROUTE_C1) return cpg_conv1x1_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream, packed);
     if (route == ROUTE_C3S2) return cpg_conv3x3s2_fwd(d, x, w, pm, thr, bias, y, nullptr, ws, ws_bytes, (hipStream_t)stream);
     if (route == ROUTE_STEM2) return cpg_conv_stem2_fwd(d, x, w, pm, thr, bias, y, nullptr, (hipStream_t)stream);
     if (route == ROUTE_GROUPED) {
@@ -691,28 +685,23 @@ extern "C" int32_t cpg_conv2d_fwd_pool_max_supported(const cpg_conv_desc *d) {
     return cpg_conv3x3_wino_pool_max_ok(d->N, d->C, d->K, d->H, d->W) ? 1 : 0;
 }
 extern "C" int cpg_conv2d_fwd_attach_pool_max(float *E, size_t bytes) {
-    cpg::pool_max_ctx() = cpg::PoolMaxCtx{};
-    if (E == nullptr) return CPG_OK;             // (disarms)
+    cpg::arm_conv_max({});                       // (NULL, and a refused attach, disarm)
+    if (E == nullptr) return CPG_OK;
     CPG_REQUIRE((((uintptr_t)E) & 3) == 0 && bytes > 0, "cpg_conv2d_fwd_attach_pool_max: needs a 4-byte aligned, non-empty buffer");
-    cpg::pool_max_ctx() = cpg::PoolMaxCtx{true, E, bytes};
+    cpg::arm_conv_max({E, bytes});
     return CPG_OK;
 }
-namespace {
-struct PoolMaxScope {        // one-shot, like PackScope
-    ~PoolMaxScope() { cpg::pool_max_ctx() = cpg::PoolMaxCtx{}; }
-};
-}  // namespace
 
 extern "C" int cpg_conv2d_fwd_bnstats(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr,
                                       const float *bias, float *y, float *stats, size_t stats_bytes, void *ws, size_t ws_bytes,
                                       void *stream) {
-    PackScope scope;
-    PoolMaxScope pool_scope;
+    const cpg::PackedOperand packed = cpg::take_operand();
+    const cpg::PoolMax pc = cpg::take_conv_max();
     {   // the descriptor's verdict first, as in every entry point: a malformed one is CPG_E_INVALID, not "no fused kernel"
         ConvGeom g;
         if (const int rc = make_geom(d, g)) return rc;
     }
-    if (const cpg::PoolMaxCtx &pc = cpg::pool_max_ctx(); pc.armed) {
+    if (pc.E != nullptr) {
         if (bias != nullptr || !cpg_conv2d_fwd_pool_max_supported(d))
             return fail(CPG_E_INVALID, "cpg_conv2d_fwd_bnstats: window maxima are attached but this launch cannot write them "
                                        "(cpg_conv2d_fwd_pool_max_supported, no bias)");
@@ -726,8 +715,8 @@ extern "C" int cpg_conv2d_fwd_bnstats(const cpg_conv_desc *d, const float *x, co
     if (stats == nullptr || stats_bytes < need)
         return fail(CPG_E_WORKSPACE, "cpg_conv2d_fwd_bnstats: statistics buffer %zu < %zu bytes", stats_bytes, need);
     switch (route) {
-        case ROUTE_C3: return cpg_conv3x3_fwd_bnstats(d, x, w, pm, thr, bias, y, stats, ws, ws_bytes, (hipStream_t)stream);
-        case ROUTE_C1: return cpg_conv1x1_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream, stats);
+        case ROUTE_C3: return cpg_conv3x3_fwd_bnstats(d, x, w, pm, thr, bias, y, stats, ws, ws_bytes, (hipStream_t)stream, packed, pc.E);
+        case ROUTE_C1: return cpg_conv1x1_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, (hipStream_t)stream, packed, stats);
         default: break;
     }
     if (route == ROUTE_C3S2) return cpg_conv3x3s2_fwd(d, x, w, pm, thr, bias, y, stats, ws, ws_bytes, (hipStream_t)stream);
@@ -744,11 +733,14 @@ extern "C" int32_t cpg_conv2d_winograd(const cpg_conv_desc *d, int32_t dgrad) {
 
 // The inference forwards: conv and what follows it in one kernel, described by one cpg::EvalEpilogue and run by one entry per kernel
 // family.  fwd_eval is the frame the three public entry points below share: the descriptor's verdict, the route cpg_conv2d_fwd takes,
-// the entry point's own checks (`admit`: a status for the route, in the order it has always made them), the family's entry -- under a
-// PackScope where the launch can take a caller's packed operand -- and zeroed skip_stats from the classes that skip nothing.
+// the entry point's own checks (`admit`: a status for the route, in the order it has always made them), the family's entry and zeroed
+// skip_stats from the classes that skip nothing.  packed: the caller's variable, read AFTER admit -- cpg_conv2d_fwd_bn_eval and _prelu_eval
+// take the thread's packed operand as the last act of their admit, and not on the 3x3 s1 p1 route: there, and when refused earlier, it
+// stays armed for the next call (include/cpg_hip.h).
 template <class Admit>
 static int fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                    const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what, Admit admit) {
+                    const cpg::EvalEpilogue &ep, const cpg::PackedOperand &packed, float *y, void *ws, size_t ws_bytes, hipStream_t stream,
+                    const char *what, Admit admit) {
     ConvGeom g;
     int rc = make_geom(d, g);
     if (rc) return rc;
@@ -756,8 +748,8 @@ static int fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, cons
     if ((rc = admit(route)) != CPG_OK) return rc;
     if (route == ROUTE_C3) return cpg_conv3x3_fwd_eval(d, x, w, pm, thr, bias, ep, y, ws, ws_bytes, stream, what);      // (reports its own skip)
     if (route != ROUTE_C1 && route != ROUTE_C3S2) return fail(CPG_E_UNSUPPORTED, "%s: no kernel of this class fuses the epilogue", what);
-    PackScope scope;            // (the pointwise launch takes a packed operand as cpg_conv2d_fwd does)
-    rc = route == ROUTE_C1 ? cpg_conv1x1_fwd_eval(d, x, w, pm, thr, bias, ep, y, ws, ws_bytes, stream, what)
+    // (the pointwise launch streams a packed operand as cpg_conv2d_fwd's does; the strided 3x3 tiles pack for themselves)
+    rc = route == ROUTE_C1 ? cpg_conv1x1_fwd_eval(d, x, w, pm, thr, bias, ep, y, ws, ws_bytes, stream, packed, what)
                            : cpg_conv3x3s2_fwd_eval(d, x, w, pm, thr, bias, ep, y, ws, ws_bytes, stream, what);
     if (rc == CPG_OK && ep.skip_stats != nullptr) {     // these classes skip nothing: what CPG_NO_DEAD_SKIP reports
         hipError_t e = hipMemsetAsync(ep.skip_stats, 0, 2 * sizeof(int32_t), stream);
@@ -779,9 +771,11 @@ extern "C" int cpg_conv2d_fwd_bn_eval(const cpg_conv_desc *d, const float *x, co
                                       const float *running_var, float eps, int32_t relu, float *y, int32_t *skip_stats, void *ws,
                                       size_t ws_bytes, void *stream) {
     const cpg::EvalEpilogue ep{cpg::EvalEpilogue::BN_EVAL, gamma, beta, running_mean, running_var, eps, relu, nullptr, 0, nullptr, skip_stats};
-    return fwd_eval(d, x, w, pm, thr, bias, ep, y, ws, ws_bytes, (hipStream_t)stream, "cpg_conv2d_fwd_bn_eval", [](ConvRoute route) {
+    cpg::PackedOperand packed;
+    return fwd_eval(d, x, w, pm, thr, bias, ep, packed, y, ws, ws_bytes, (hipStream_t)stream, "cpg_conv2d_fwd_bn_eval", [&](ConvRoute route) {
         if (route != ROUTE_C3 && route != ROUTE_C1 && route != ROUTE_C3S2)
             return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_bn_eval: only the 3x3 s1 p1, the pointwise and the 3x3 s2 kernels fuse the epilogue");
+        if (route != ROUTE_C3) packed = cpg::take_operand();
         return CPG_OK;
     });
 }
@@ -795,9 +789,9 @@ extern "C" int cpg_conv2d_fwd_bn_eval_add(const cpg_conv_desc *d, const float *x
                                           const float *bias, const float *gamma, const float *beta, const float *running_mean,
                                           const float *running_var, float eps, const float *residual, int32_t relu, float *y, void *ws,
                                           size_t ws_bytes, void *stream) {
-    PackScope scope;            // (a refused call, too, uses up the packed operand a caller armed)
+    const cpg::PackedOperand packed = cpg::take_operand();      // (on entry: a refused call, too, uses it up)
     const cpg::EvalEpilogue ep{cpg::EvalEpilogue::BN_EVAL, gamma, beta, running_mean, running_var, eps, relu, nullptr, 0, residual, nullptr};
-    return fwd_eval(d, x, w, pm, thr, bias, ep, y, ws, ws_bytes, (hipStream_t)stream, "cpg_conv2d_fwd_bn_eval_add", [&](ConvRoute route) {
+    return fwd_eval(d, x, w, pm, thr, bias, ep, packed, y, ws, ws_bytes, (hipStream_t)stream, "cpg_conv2d_fwd_bn_eval_add", [&](ConvRoute route) {
         if (route != ROUTE_C1) return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_bn_eval_add: only the pointwise kernels add the residual");
         CPG_REQUIRE(residual != nullptr, "cpg_conv2d_fwd_bn_eval_add: null residual");
         return CPG_OK;
@@ -819,12 +813,14 @@ extern "C" int cpg_conv2d_fwd_prelu_eval(const cpg_conv_desc *d, const float *x,
                                          int32_t *skip_stats, void *ws, size_t ws_bytes, void *stream) {
     // (per_channel: n_slopes == K once the count is admitted; K == 1 is one slope either way, index 0)
     const cpg::EvalEpilogue ep{cpg::EvalEpilogue::PRELU, nullptr, nullptr, nullptr, nullptr, 0.0f, 0, slope, n_slopes != 1, residual, skip_stats};
-    return fwd_eval(d, x, w, pm, thr, bias, ep, y, ws, ws_bytes, (hipStream_t)stream, "cpg_conv2d_fwd_prelu_eval", [&](ConvRoute) {
+    cpg::PackedOperand packed;
+    return fwd_eval(d, x, w, pm, thr, bias, ep, packed, y, ws, ws_bytes, (hipStream_t)stream, "cpg_conv2d_fwd_prelu_eval", [&](ConvRoute route) {
         CPG_REQUIRE(x && w && y && slope, "cpg_conv2d_fwd_prelu_eval: null pointer");
         CPG_REQUIRE(n_slopes == d->K || n_slopes == 1, "cpg_conv2d_fwd_prelu_eval: n_slopes must be K or 1");
         if (!cpg_conv2d_fwd_prelu_eval_supported(d, residual != nullptr ? 1 : 0))
             return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_prelu_eval: only the 3x3 s1 p1 kernels (and, without a residual, the 3x3 s2 kernels) "
                                            "fuse the epilogue; not on channel-split tiles");
+        if (route != ROUTE_C3) packed = cpg::take_operand();
         return CPG_OK;
     });
 }
@@ -838,7 +834,7 @@ extern "C" int32_t cpg_conv2d_dgrad_bnbwd_tiles(const cpg_conv_desc *d) {
 extern "C" int cpg_conv2d_dgrad_bnbwd(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr,
                                       const float *ypre, const float *gamma, const float *beta, const float *mean, const float *invstd,
                                       float *gm, float *partials, size_t partial_bytes, void *ws, size_t ws_bytes, void *stream) {
-    PackScope scope;
+    (void)cpg::take_operand();      // (used up, never streamed: this pass runs the direct kernels, which pack for themselves)
     ConvGeom g;
     int rc = make_geom(d, g);
     if (rc) return rc;
@@ -850,10 +846,10 @@ extern "C" int cpg_conv2d_dgrad_bnbwd(const cpg_conv_desc *d, const float *gy, c
 
 extern "C" int cpg_conv2d_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr,
                                 float *gx, void *ws, size_t ws_bytes, void *stream) {
-    PackScope scope;
+    const cpg::PackedOperand packed = cpg::take_operand();
     const ConvRoute route = fwd_route(d);
-    if (route == ROUTE_C3) return cpg_conv3x3_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream);
-    if (route == ROUTE_C1) return cpg_conv1x1_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream);
+    if (route == ROUTE_C3) return cpg_conv3x3_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream, packed);
+    if (route == ROUTE_C1) return cpg_conv1x1_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream, packed);
     if (route == ROUTE_C3S2) return cpg_conv3x3s2_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream);
     if (route == ROUTE_GROUPED) {
         ConvGeom g;
@@ -874,13 +870,13 @@ extern "C" int32_t cpg_conv2d_dgrad_add_supported(const cpg_conv_desc *d) {
 }
 extern "C" int cpg_conv2d_dgrad_add(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, const float *addend,
                                     float *gx, void *ws, size_t ws_bytes, void *stream) {
-    PackScope scope;
+    const cpg::PackedOperand packed = cpg::take_operand();
     if (!cpg_conv2d_dgrad_add_supported(d))
         return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_dgrad_add: dense 1x1 layers and the 3x3 layers of the two-wave Winograd kernel fuse the addend");
     CPG_REQUIRE(addend != nullptr && gy && w && gx, "cpg_conv2d_dgrad_add: null pointer");
     if (cpg_conv3x3_supported(d))
-        return cpg_conv3x3_wino_dgrad_add(d->N, d->K, d->C, d->H, d->W, d->K, d->C, gy, w, pm, thr, addend, gx, ws, ws_bytes, (hipStream_t)stream);
-    return cpg_conv1x1_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream, addend);
+        return cpg_conv3x3_wino_dgrad_add(d->N, d->K, d->C, d->H, d->W, d->K, d->C, gy, w, pm, thr, addend, gx, ws, ws_bytes, (hipStream_t)stream, packed);
+    return cpg_conv1x1_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream, packed, addend);
 }
 
 // ---- caller-owned packed weight operands (include/cpg_hip.h, ABI 3) ------------------------------------------------------------------
@@ -920,7 +916,7 @@ extern "C" int cpg_conv2d_pack(const cpg_conv_desc *d, const float *w, const flo
 }
 
 extern "C" int cpg_conv2d_use_packed(const void *packed, size_t bytes) {
-    cpg::pack_ctx() = cpg::PackCtx{packed != nullptr, (const float *)packed, bytes};       // (null disarms)
+    cpg::arm_operand(packed != nullptr ? cpg::PackedOperand{(const float *)packed, bytes} : cpg::PackedOperand{});       // (null disarms)
     return CPG_OK;
 }
 
@@ -931,22 +927,16 @@ extern "C" int32_t cpg_conv2d_wgrad_rider_supported(const cpg_conv_desc *d) {
     return cpg_conv3x3_wino_wgrad_rider_ok(d) ? 1 : 0;
 }
 extern "C" int cpg_conv2d_wgrad_attach_bn_bwd(const float *y, const float *gz, float *gy, const float *table, int32_t N, int32_t C, int32_t HW) {
-    cpg::WgradRider &r = cpg::wgrad_rider();
-    r = cpg::WgradRider{};
-    if (y == nullptr) return CPG_OK;             // (disarms)
+    cpg::arm_rider({});                          // (NULL, and a refused attach, disarm)
+    if (y == nullptr) return CPG_OK;
     CPG_REQUIRE(gz && gy && table, "cpg_conv2d_wgrad_attach_bn_bwd: null pointer");
     CPG_REQUIRE(N > 0 && C > 0 && HW > 0 && HW % 4 == 0 && (int64_t)N * C * HW * 4 < (1ll << 31),
                 "cpg_conv2d_wgrad_attach_bn_bwd: needs 4 | HW and a tensor below 2 GiB");
     CPG_REQUIRE(((((uintptr_t)y) | ((uintptr_t)gz) | ((uintptr_t)gy) | ((uintptr_t)table)) & 15) == 0,
                 "cpg_conv2d_wgrad_attach_bn_bwd: pointers must be 16-byte aligned");
-    r.armed = true, r.y = y, r.gz = gz, r.gy = gy, r.table = table, r.N = N, r.C = C, r.HW = HW;
+    cpg::arm_rider({y, gz, gy, table, N, C, HW});
     return CPG_OK;
 }
-namespace {
-struct RiderScope {          // one-shot, like PackScope
-    ~RiderScope() { cpg::wgrad_rider() = cpg::WgradRider{}; }
-};
-}  // namespace
 
 // the generic weight gradient (the caller checks the launches)
 static int wgrad_generic(const ConvGeom &g, const float *x, const float *gy, const float *w, const float *pm, float thr, float *gw, float *gpm,
@@ -971,11 +961,11 @@ static int wgrad_generic(const ConvGeom &g, const float *x, const float *gy, con
 
 extern "C" int cpg_conv2d_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm,
                                 float thr, float *gw, float *gpm, float *gb, void *ws, size_t ws_bytes, void *stream_v) {
-    RiderScope rider_scope;
+    const cpg::WgradRider rider = cpg::take_rider();
     ConvGeom g;
     int rc = make_geom(d, g);
     if (rc) return rc;
-    if (cpg::wgrad_rider().armed && !cpg_conv2d_wgrad_rider_supported(d))
+    if (rider.y != nullptr && !cpg_conv2d_wgrad_rider_supported(d))
         return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_wgrad: a BatchNorm backward is attached but this launch cannot carry it (cpg_conv2d_wgrad_rider_supported)");
     CPG_REQUIRE(x && gy && gw, "cpg_conv2d_wgrad: null pointer");
     CPG_REQUIRE((pm == nullptr) == (gpm == nullptr), "cpg_conv2d_wgrad: pm and gpm must both be given or both be NULL");
@@ -985,7 +975,7 @@ extern "C" int cpg_conv2d_wgrad(const cpg_conv_desc *d, const float *x, const fl
     hipStream_t stream = (hipStream_t)stream_v;
     const char *what = "cpg_conv2d_wgrad(bias)";         // (the specialised routes have checked their own launches)
     switch (wgrad_route(d)) {
-        case ROUTE_C3: rc = cpg_conv3x3_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream); break;
+        case ROUTE_C3: rc = cpg_conv3x3_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream, rider); break;
         case ROUTE_STEM2: rc = cpg_conv_stem2_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream); break;
         case ROUTE_C3S2: rc = cpg_conv3x3s2_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream); break;
         case ROUTE_C1: rc = cpg_conv1x1_wgrad(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream); break;

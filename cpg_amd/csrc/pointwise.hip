@@ -867,14 +867,14 @@ cpg::PackJob cpg_conv1x1_pack_job(const cpg_conv_desc *d, int dgrad) {
 }
 
 namespace {
-// *wp = the operand the launch streams: the caller's (cpg_conv2d_use_packed), or the one packed here into the workspace
+// *wp = the operand the launch streams: the caller's (packed, where there is one), or the one packed here into the workspace
 int pw_packed_operand(const cpg_conv_desc *d, int dgrad, const float *w, const float *pm, float thr, void *ws, size_t ws_bytes, hipStream_t stream,
-                      const char *what, const float **wp) {
+                      const cpg::PackedOperand &packed, const char *what, const float **wp) {
     const cpg::PackJob job = cpg_conv1x1_pack_job(d, dgrad);
     if (ws == nullptr || ws_bytes < job.bytes) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, job.bytes);
     CPG_REQUIRE((((uintptr_t)ws) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
-    const int rc = cpg::take_packed(job.bytes, wp, what);
-    if (rc != CPG_OK || *wp != nullptr) return rc;
+    if (const int rc = cpg::packed_fits(packed, job.bytes, what)) return rc;
+    if ((*wp = packed.data) != nullptr) return CPG_OK;
     hipLaunchKernelGGL(k_pw_pack, dim3(stream_grid(job.total, 256)), dim3(256), 0, stream, w, pm, thr, (float *)ws, d->K, d->C, job.a, job.b, dgrad);
     *wp = (const float *)ws;
     return CPG_OK;
@@ -883,9 +883,9 @@ int pw_packed_operand(const cpg_conv_desc *d, int dgrad, const float *w, const f
 
 namespace {
 int pw_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y, void *ws,
-           size_t ws_bytes, hipStream_t stream, float *stats, const PwBn *bn, const float *residual, const char *what) {
+           size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed, float *stats, const PwBn *bn, const float *residual, const char *what) {
     const float *wp = nullptr;
-    if (const int rc = pw_packed_operand(d, 0, w, pm, thr, ws, ws_bytes, stream, what, &wp)) return rc;
+    if (const int rc = pw_packed_operand(d, 0, w, pm, thr, ws, ws_bytes, stream, packed, what, &wp)) return rc;
     const int OH = (d->H - 1) / d->stride_h + 1, OW = (d->W - 1) / d->stride_w + 1;
     PwGeom g{d->N, d->C, d->K, pad_to(d->K, 128), OW, OH * OW, d->H * d->W, d->stride_h * d->W, d->stride_w, OH * OW, OW, 1, 0, (long long)d->N * OH * OW};
     const PwTile tile = pw_fwd_tile(d, (((uintptr_t)x) & 15) == 0);
@@ -903,27 +903,27 @@ int pw_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *
 }  // namespace
 
 int cpg_conv1x1_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                    float *y, void *ws, size_t ws_bytes, hipStream_t stream, float *stats) {
+                    float *y, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed, float *stats) {
     const char *what = "cpg_conv2d_fwd(1x1)";
     CPG_REQUIRE(x && w && y, "%s: null pointer", what);
-    return pw_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, stream, stats, nullptr, nullptr, what);
+    return pw_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, stream, packed, stats, nullptr, nullptr, what);
 }
 
 // inference: y = [max(0,] bn(conv + bias) [+ residual] [)] in one launch (k_pw's BNE instances); residual: dense, shaped like y, or null
 int cpg_conv1x1_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                         const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what) {
+                         const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed, const char *what) {
     if (ep.kind != cpg::EvalEpilogue::BN_EVAL) return fail(CPG_E_UNSUPPORTED, "%s(1x1): the pointwise kernels have the BatchNorm epilogue only", what);
     CPG_REQUIRE(x && w && y && ep.gamma && ep.beta && ep.mean && ep.var, "%s(1x1): null pointer", what);
     const PwBn bn{ep.gamma, ep.beta, ep.mean, ep.var, ep.eps, ep.relu};
-    return pw_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, stream, nullptr, &bn, ep.residual, what);
+    return pw_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, stream, packed, nullptr, &bn, ep.residual, what);
 }
 
 int cpg_conv1x1_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
-                      size_t ws_bytes, hipStream_t stream, const float *addend) {
+                      size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed, const float *addend) {
     const char *what = "cpg_conv2d_dgrad(1x1)";
     CPG_REQUIRE(gy && w && gx, "%s: null pointer", what);
     const float *wp = nullptr;
-    if (const int rc = pw_packed_operand(d, 1, w, pm, thr, ws, ws_bytes, stream, what, &wp)) return rc;
+    if (const int rc = pw_packed_operand(d, 1, w, pm, thr, ws, ws_bytes, stream, packed, what, &wp)) return rc;
     const int OH = (d->H - 1) / d->stride_h + 1, OW = (d->W - 1) / d->stride_w + 1;
     const bool dense = d->stride_h == 1 && d->stride_w == 1;
     if (!dense) {       // positions the strided conv never read receive no gradient

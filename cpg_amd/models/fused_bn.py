@@ -193,12 +193,10 @@ def _pool_backward(name, ctx, gp):
     """The backward shared by both BatchNorm2d -> ReLU -> MaxPool2d Functions (cpg_bn_relu_pool_bwd / cpg_bn_relu_pool3_bwd; with the
     window maxima saved by the forward, attached to the same call: cpg_bn_relu_pool_attach_max)."""
     (x, gamma, beta, mean, invstd, *emax), gp, N, C, _, gx, dgamma, dbeta, ws, nb = _bn_backward(ctx, gp)
-    for e in emax:
-        # (one-shot: the call below disarms the thread when it returns, whatever its status)
-        _lib.call('cpg_bn_relu_pool_attach_max', _lib.dptr(e), e.numel() * 4)
-    _lib.call(name, _lib.dptr(x), _lib.dptr(gp, name='grad_output'), _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(mean),
-              _lib.dptr(invstd), _lib.dptr(gx), _lib.dptr(dgamma), _lib.dptr(dbeta), N, C, x.shape[2], x.shape[3], int(ctx.training),
-              _lib.dptr(ws), nb, _lib.stream_ptr())
+    arms = tuple(('cpg_bn_relu_pool_attach_max', (_lib.dptr(e), e.numel() * 4)) for e in emax)
+    _lib.call_armed(arms, name, _lib.dptr(x), _lib.dptr(gp, name='grad_output'), _lib.dptr(gamma), _lib.dptr(beta), _lib.dptr(mean),
+                    _lib.dptr(invstd), _lib.dptr(gx), _lib.dptr(dgamma), _lib.dptr(dbeta), N, C, x.shape[2], x.shape[3], int(ctx.training),
+                    _lib.dptr(ws), nb, _lib.stream_ptr())
     return (gx, dgamma, dbeta) + (None,) * 8
 
 
@@ -212,13 +210,11 @@ class _BnReluPoolFn(torch.autograd.Function):
             H, W = x.shape[2:]
             y = torch.empty((N, C, H // 2, W // 2), dtype=torch.float32, device=x.device)
             use_max = pool_max is not None and not own_stats
-            if use_max:
-                # (one-shot: the call below disarms the thread when it returns, whatever its status)
-                _lib.call('cpg_bn_relu_pool_attach_max', _lib.dptr(pool_max, name='window maxima'), pool_max.numel() * 4)
-            _lib.call('cpg_bn_relu_pool_fwd', _lib.dptr(x, name='input'), _lib.dptr(gamma, name='bn.weight'), _lib.dptr(beta, name='bn.bias'),
-                      float(eps), float(momentum), _lib.dptr(running_mean if own_stats else None),
-                      _lib.dptr(running_var if own_stats else None), _lib.dptr(mean), _lib.dptr(invstd),
-                      _lib.dptr(y), N, C, H, W, int(own_stats), _lib.dptr(ws), nb, _lib.stream_ptr())
+            arms = (('cpg_bn_relu_pool_attach_max', (_lib.dptr(pool_max, name='window maxima'), pool_max.numel() * 4)),) if use_max else ()
+            _lib.call_armed(arms, 'cpg_bn_relu_pool_fwd', _lib.dptr(x, name='input'), _lib.dptr(gamma, name='bn.weight'),
+                            _lib.dptr(beta, name='bn.bias'), float(eps), float(momentum), _lib.dptr(running_mean if own_stats else None),
+                            _lib.dptr(running_var if own_stats else None), _lib.dptr(mean), _lib.dptr(invstd),
+                            _lib.dptr(y), N, C, H, W, int(own_stats), _lib.dptr(ws), nb, _lib.stream_ptr())
             return y, ((pool_max,) if use_max else ())
         return _bn_forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, training, stats, nbt, launch)
 

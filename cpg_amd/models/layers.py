@@ -98,21 +98,6 @@ def _skip_stats_ptr(skip_stats):
 PACK_CACHE = os.environ.get('CPG_PACK_CACHE', '1') not in ('0', '')
 
 
-def _call_packed(pk, name, *args):
-    """_lib.call of ONE conv entry point with the calling thread armed to stream the packed operand `pk` (None: plain call).
-    The library disarms itself inside that entry point; an exception raised on the way there (an argument that does not convert)
-    disarms here (once more, harmlessly, when the entry point itself failed), so that no LATER call of this thread can pick up an
-    operand that was not meant for it."""
-    if pk is None:
-        return _lib.call(name, *args)
-    _lib.call('cpg_conv2d_use_packed', _lib.dptr(pk), pk.numel() * 4)
-    try:
-        _lib.call(name, *args)
-    except BaseException:
-        _lib.lib().cpg_conv2d_use_packed(None, 0)
-        raise
-
-
 class BiasGradSink(object):
     """Hand-off from the PReLU that is the ONLY consumer of a biased conv's output (SphereNet, models/spherenet.py:203-247) to that
     conv's backward: the PReLU's one-pass backward sums its input gradient per channel while it writes it -- that sum IS the conv's bias
@@ -239,9 +224,10 @@ class _MaskedConv2dFn(torch.autograd.Function):
             ws, nbytes = _lib.workspace(L.cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
             tiles = L.cpg_conv2d_bnstats_tiles(ctypes.byref(d)) if bn_stats else 0
             # Packed weight operands (cpg_conv2d_pack, ABI 3): when this layer's forward AND its input gradient stream one, both are
-            # produced here in ONE launch; the forward takes its own now, the input gradient's rides in ctx until backward (the weights
-            # cannot change in between: autograd's version check on the saved w / pm guards exactly that).  One launch instead of two
-            # per layer and step.
+            # produced here in ONE launch, instead of two per layer and step; the forward takes its own now, the input gradient's rides in
+            # ctx until backward.  Nothing checks that the weights are still the ones it was packed from (autograd's version counter does not
+            # see the optimizers, which write through data_ptr(), nor the pruner's .data): what holds is that nothing in this code base
+            # updates the weights between a forward and its backward.
             pk_f = None
             if PACK_CACHE and ctx.needs_input_grad[0]:
                 uses_bnbwd = bn_hint is not None and bn_hint.epilogue and L.cpg_conv2d_dgrad_bnbwd_tiles(ctypes.byref(d)) > 0      # (that launch packs for the direct kernels)
@@ -256,14 +242,14 @@ class _MaskedConv2dFn(torch.autograd.Function):
                     _lib.dptr(bias, name='bias'), _lib.dptr(y))
             if tiles > 0:
                 stats = torch.empty((d.K, tiles, 2), dtype=torch.float32, device=x.device)
+                arms = ()
                 if pool_sink is not None and bias is None and L.cpg_conv2d_fwd_pool_max_supported(ctypes.byref(d)):
-                    # (one-shot: cpg_conv2d_fwd_bnstats disarms the thread when it returns, whatever its status)
                     pool_sink.E = torch.empty((d.N, d.K, oh // 2, ow // 2), dtype=torch.float32, device=x.device)
-                    _lib.call('cpg_conv2d_fwd_attach_pool_max', _lib.dptr(pool_sink.E), pool_sink.E.numel() * 4)
-                _call_packed(pk_f, 'cpg_conv2d_fwd_bnstats', *head, _lib.dptr(stats), stats.numel() * 4, _lib.dptr(ws), nbytes,
-                             _lib.stream_ptr())
+                    arms = (('cpg_conv2d_fwd_attach_pool_max', (_lib.dptr(pool_sink.E), pool_sink.E.numel() * 4)),)
+                _lib.call_armed(arms + _lib.use_packed(pk_f), 'cpg_conv2d_fwd_bnstats', *head, _lib.dptr(stats), stats.numel() * 4,
+                                _lib.dptr(ws), nbytes, _lib.stream_ptr())
             else:
-                _call_packed(pk_f, 'cpg_conv2d_fwd', *head, _lib.dptr(ws), nbytes, _lib.stream_ptr())
+                _lib.call_armed(_lib.use_packed(pk_f), 'cpg_conv2d_fwd', *head, _lib.dptr(ws), nbytes, _lib.stream_ptr())
         ctx.save_for_backward(x, w, p)
         ctx.desc, ctx.thr, ctx.has_bias = d, thr, bias is not None
         if not bn_stats:
@@ -323,11 +309,11 @@ class _MaskedConv2dFn(torch.autograd.Function):
                 pk, ctx.packed_dgrad = ctx.packed_dgrad, None      # (the operand packed at forward time, one-shot)
                 if addend is not None and L.cpg_conv2d_dgrad_add_supported(ctypes.byref(d)) and addend.shape == x.shape:
                     ad = addend.contiguous()
-                    _call_packed(pk, 'cpg_conv2d_dgrad_add', *head, _lib.dptr(ad, name='skip gradient'), _lib.dptr(gx), _lib.dptr(ws),
-                                 nbytes, s)
+                    _lib.call_armed(_lib.use_packed(pk), 'cpg_conv2d_dgrad_add', *head, _lib.dptr(ad, name='skip gradient'), _lib.dptr(gx),
+                                    _lib.dptr(ws), nbytes, s)
                     addend = None
                 else:
-                    _call_packed(pk, 'cpg_conv2d_dgrad', *head, _lib.dptr(gx), _lib.dptr(ws), nbytes, s)
+                    _lib.call_armed(_lib.use_packed(pk), 'cpg_conv2d_dgrad', *head, _lib.dptr(gx), _lib.dptr(ws), nbytes, s)
         if addend is not None:                  # (no fused path for this launch)
             gx = addend.clone() if gx is None else gx.add_(addend)
         return gx
@@ -357,11 +343,12 @@ class _MaskedConv2dFn(torch.autograd.Function):
             wsw, nbw = _lib.workspace(L.cpg_conv2d_wgrad_bf16_workspace_bytes(ctypes.byref(d)), x.device)
             _lib.call('cpg_conv2d_wgrad_bf16x3' if ctx.x3 else 'cpg_conv2d_wgrad_bf16', *head, _lib.dptr(wsw), nbw, s)
         else:
+            arms = ()
             if rider is not None:
                 ypre, gyb, table = rider[0], rider[1], rider[4]
-                _lib.call('cpg_conv2d_wgrad_attach_bn_bwd', _lib.dptr(ypre), _lib.dptr(gx), _lib.dptr(gyb), _lib.dptr(table), ypre.shape[0],
-                          ypre.shape[1], ypre.numel() // (ypre.shape[0] * ypre.shape[1]))
-            _lib.call('cpg_conv2d_wgrad', *head, _lib.dptr(gb), _lib.dptr(ws), nbytes, s)
+                arms = (('cpg_conv2d_wgrad_attach_bn_bwd', (_lib.dptr(ypre), _lib.dptr(gx), _lib.dptr(gyb), _lib.dptr(table), ypre.shape[0],
+                                                            ypre.shape[1], ypre.numel() // (ypre.shape[0] * ypre.shape[1]))),)
+            _lib.call_armed(arms, 'cpg_conv2d_wgrad', *head, _lib.dptr(gb), _lib.dptr(ws), nbytes, s)
             if rider is not None:
                 hint.store(gx, rider[1:4])
         return gw, gpm, (given if given is not None else gb)

@@ -559,11 +559,9 @@ bool ww_plan(const cpg_conv_desc *d, WwPlan &p) {
     return p.blocks <= 0x7FFFFFFFll;
 }
 
-// the rider: which launches can carry one, and its geometry
+// the rider: which launches can carry one, and its geometry (cpg_conv2d_wgrad_attach_bn_bwd admitted r: 16-byte aligned, 4 | HW, below 2 GiB)
 bool ww_rider_ok(const WwPlan &p) { return p.gs == 4 && !opt_on(OPT_NO_WW_RIDER); }
 bool ww_rider_plan(const WwPlan &p, const WgradRider &r, WwRider &rd, int &ri) {
-    if (r.N < 1 || r.C < 1 || r.HW < 4 || r.HW % 4 || (int64_t)r.N * r.C * r.HW * 4 >= (1ll << 31)) return false;
-    if ((((uintptr_t)r.y) | ((uintptr_t)r.gz) | ((uintptr_t)r.gy) | ((uintptr_t)r.table)) & 15) return false;
     rd.y = r.y, rd.gz = r.gz, rd.gy = r.gy, rd.table = r.table;
     rd.C = r.C, rd.HW = r.HW, rd.p4 = r.HW / 4, rd.ipp = (rd.p4 + 63) / 64;
     rd.bytes = r.N * r.C * r.HW * 4;
@@ -603,16 +601,21 @@ extern "C" size_t cpg_conv3x3_wino_wgrad_workspace(const cpg_conv_desc *d) {
 
 extern "C" int cpg_conv3x3_wino_wgrad(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr,
                                       float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream) {
+    return cpg_conv3x3_wino_wgrad_side(d, x, gy, w, pm, thr, gw, gpm, ws, ws_bytes, stream, WgradRider());
+}
+
+int cpg_conv3x3_wino_wgrad_side(const cpg_conv_desc *d, const float *x, const float *gy, const float *w, const float *pm, float thr,
+                                float *gw, float *gpm, void *ws, size_t ws_bytes, hipStream_t stream, const WgradRider &r) {
     WwPlan p;
     if (!ww_plan(d, p)) return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_wgrad(winograd): shape not supported");
     if (ws == nullptr || ws_bytes < p.ws_bytes)
         return fail(CPG_E_WORKSPACE, "cpg_conv2d_wgrad(winograd): workspace %zu < %zu bytes", ws_bytes, p.ws_bytes);
     WwRider rd{};
     int ri = 0;
-    if (WgradRider &r = wgrad_rider(); r.armed) {                // (one-shot: cpg_conv2d_wgrad disarms the thread when it returns)
+    if (r.y != nullptr) {
         if (!ww_rider_ok(p) || !ww_rider_plan(p, r, rd, ri))
             return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_wgrad(winograd): the attached BatchNorm backward cannot ride in this launch "
-                                           "(cpg_conv2d_wgrad_rider_supported, 4 | HW, < 2 GiB, 16-byte aligned pointers)");
+                                           "(cpg_conv2d_wgrad_rider_supported)");
         if (rd.y == x || rd.gz == x || rd.gy == x || rd.gy == gy || (const float *)rd.gy == rd.y || (const float *)rd.gy == rd.gz)
             return fail(CPG_E_INVALID, "cpg_conv2d_wgrad(winograd): the rider's result may not alias its inputs or the weight gradient's");
     }
