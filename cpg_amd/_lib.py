@@ -121,6 +121,8 @@ _SIGNATURES = {
     'cpg_conv2d_fwd_bnstats': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     'cpg_conv2d_fwd_bn_eval_supported': (_i32, [_desc]),
     'cpg_conv2d_fwd_bn_eval': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    'cpg_conv2d_fwd_bn_eval_pool_supported': (_i32, [_desc]),
+    'cpg_conv2d_fwd_bn_eval_pool': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _sz, _vp]),
     'cpg_conv2d_fwd_bn_eval_add_supported': (_i32, [_desc]),
     'cpg_conv2d_fwd_bn_eval_add': (_int, [_desc, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _vp, _vp, _sz, _vp]),
     'cpg_conv2d_fwd_prelu_eval_supported': (_i32, [_desc, _i32]),

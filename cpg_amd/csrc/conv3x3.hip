@@ -1329,6 +1329,12 @@ int cpg_conv3x3_eval_epilogue_ok(const cpg_conv_desc *d) {
     return plan.route == C3_DIRECT && plan.ksplit == 1 && plan.blocks <= 0x7FFFFFFFll ? 1 : 0;
 }
 
+// 1: the pooled inference epilogue (ep.pool) has a launch for this shape under the current option table: the plan is the Winograd inference
+// launch and the map is even (conv3x3_wino.hip's POOL instances; k_c3_fwd's tiles and the ODD instances have none)
+int cpg_conv3x3_eval_pool_ok(const cpg_conv_desc *d) {
+    return plan_fwd(false, d->N, d->C, d->K, d->H, d->W, C3_BN_EVAL).route == C3_WINO_EVAL && cpg_conv3x3_wino_eval_pool_ok(d->N, d->C, d->K, d->H, d->W) ? 1 : 0;
+}
+
 // the inference forward (Manager.validate's path, SphereNet's units): ep in the epilogue, and the dead-channel skip
 int cpg_conv3x3_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                          const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what) {
@@ -1339,6 +1345,8 @@ int cpg_conv3x3_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w,
         CPG_REQUIRE(x && w && y && ep.gamma && ep.beta && ep.mean && ep.var, "%s: null pointer", what);
         if (ep.residual != nullptr) return fail(CPG_E_UNSUPPORTED, "%s: the 3x3 kernels add no residual behind the BatchNorm", what);
     }
+    if (ep.pool && (ep.kind != cpg::EvalEpilogue::BN_EVAL || !cpg_conv3x3_eval_pool_ok(d)))
+        return fail(CPG_E_UNSUPPORTED, "%s: only the one- and two-wave Winograd launches of an even map pool in the epilogue", what);
     const bool skip = !opt_on(OPT_NO_DEAD_SKIP);
     int32_t *const skip_stats = ep.skip_stats;
     C3Extra ex;
@@ -1611,6 +1619,7 @@ int cpg_conv3x3s2_fwd(const cpg_conv_desc *d, const float *x, const float *w, co
 int cpg_conv3x3s2_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                            const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what) {
     if (ep.residual != nullptr) return fail(CPG_E_UNSUPPORTED, "%s: the strided 3x3 kernels add no residual", what);
+    if (ep.pool) return fail(CPG_E_UNSUPPORTED, "%s: the strided 3x3 kernels do not pool in the epilogue", what);
     if (ep.kind == cpg::EvalEpilogue::PRELU) {
         CPG_REQUIRE(x && w && y && ep.slope, "%s: null pointer", what);
         if (plan_fwd_s2(d).blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "%s: grid too large", what);

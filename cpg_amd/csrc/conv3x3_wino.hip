@@ -612,11 +612,15 @@ __device__ unsigned long long wg_dbg[65536 * 8];
 #else
 #define WG_STAMP(i)
 #endif
-template <bool DGRAD, bool STATS, bool BNE = false, bool PRE = false>
+// POOL (inference launches, with BNE: the same skip; even maps): the MaxPool2d(2, 2) behind the BatchNorm (+ ReLU) too.  A tile's 2x2 outputs ARE
+// one pool window and this wave holds all four in one lane: `y` is the POOLED tensor [N][M][H/2][W/2], one dword per (channel, tile) at the
+// tile's own index inside its image; the full-resolution activation is never written.
+template <bool DGRAD, bool STATS, bool BNE = false, bool PRE = false, bool POOL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_wg1(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, const float *__restrict__ bias,
            float *__restrict__ y, float *__restrict__ stats, WgBnEval bn) {
     static_assert(!PRE || (BNE && !DGRAD && !STATS), "the PReLU epilogue is an inference epilogue");
+    static_assert(!POOL || (BNE && !PRE && !DGRAD && !STATS), "the pooled epilogue is the BatchNorm inference epilogue's");
     __shared__ __attribute__((aligned(16))) float smem_all[4 * 2 * W1_RAW];
     // (readfirstlane: tells the compiler the wave index is wave-uniform, so that everything derived from it -- the tile run, the
     //  buffer descriptor of its first image -- lives in scalar registers; without it every buffer load became a waterfall loop)
@@ -886,6 +890,7 @@ void k_wg1(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
     const int n = (int)(tg / timg), r = (int)(tg % timg);
     const int ty = (int)((unsigned)r / twu), tx = (int)((unsigned)r % twu);
     float *yout = y + ((int64_t)n * g.M) * HW + (2 * ty) * g.W + 2 * tx;
+    float *pout = y + ((int64_t)n * g.M) * g.tiles_img + r;       // (POOL) window (ty, tx) of image n, channel 0
     float s1[16], s2[16];
     // (PRE) the residual, at the store's own address + the uniform distance between the two tensors: nothing new for the compiler to keep
     // per lane across the main loop (this kernel's loop owns all 256 vector registers)
@@ -923,6 +928,9 @@ void k_wg1(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
             v10 = (v10 - mu) * is * ga + be, v11 = (v11 - mu) * is * ga + be;
             if (bn.relu) v00 = relu_keep(v00), v01 = relu_keep(v01), v10 = relu_keep(v10), v11 = relu_keep(v11);
         }
+        if constexpr (POOL) {                  // the two row maxima, then the window's: the order the two-wave kernels combine them in
+            if (tv && co < g.M) pout[(int64_t)co * g.tiles_img] = max_keep(max_keep(v10, v11), max_keep(v00, v01));
+        } else
         if (tv && co < g.M) {
             f32x2 o;
             o[0] = v00, o[1] = v01;
@@ -978,10 +986,14 @@ constexpr int W2_RAW = 4 * 3 * W1_ROW;                    // one stage of one wa
 
 
 
-template <bool DGRAD, bool STATS, bool BNE = false, bool PRE = false>
+// POOL (see k_wg1): a wave ends the epilogue with output row ph of the tile.  It leaves max(v0, v1) in the exchange slot it has just read (the
+// other wave's, consumed, nobody else looks at it); after one more barrier wave ph combines the two row maxima of accumulator elements
+// 8 ph .. 8 ph + 7 (16 of the block's 32 channels) and stores them to the pooled tensor `y`.
+template <bool DGRAD, bool STATS, bool BNE = false, bool PRE = false, bool POOL = false>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_wg2(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, const float *__restrict__ bias,
            float *__restrict__ y, float *__restrict__ stats, WgBnEval bn) {
+    static_assert(!POOL || (BNE && !PRE && !DGRAD && !STATS), "the pooled epilogue is the BatchNorm inference epilogue's");
     __shared__ __attribute__((aligned(16))) float smem_all[2 * 32 * 64];       // 2 x 2 raw stages (3264 floats) / the exchange buffer
     const int tid = threadIdx.x, lane = tid & 63, ph = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, lh = lane >> 5;
@@ -1203,6 +1215,9 @@ void k_wg2(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
             v0 = (v0 - mu) * is * ga + be, v1 = (v1 - mu) * is * ga + be;
             if (bn.relu) v0 = relu_keep(v0), v1 = relu_keep(v1);
         }
+        if constexpr (POOL) {                  // this wave's row maximum, into the slot v0's partial came from (see POOL)
+            xch[(((ph ^ 1) * 2 + 0) * 16 + e) * 64 + lane] = max_keep(v0, v1);
+        } else
         if (tv && co < g.M) {
             f32x2 o;
             o[0] = v0, o[1] = v1;
@@ -1215,6 +1230,17 @@ void k_wg2(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
     }
     };
     if (bias != nullptr) out_all(std::true_type{}); else out_all(std::false_type{});
+    if constexpr (POOL) {
+        __syncthreads();                       // both waves' row maxima are in the exchange buffer
+        float *pout = y + ((int64_t)n * g.M) * g.tiles_img + r;       // window (ty, tx) of image n, channel 0
+#pragma unroll
+        for (int e8 = 0; e8 < 8; ++e8) {
+            const int e = ph * 8 + e8;
+            const int co = kb * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+            const float a = xch[((0 * 2 + 0) * 16 + e) * 64 + lane], b = xch[((1 * 2 + 0) * 16 + e) * 64 + lane];      // left by wave 1 / by wave 0
+            if (tv && co < g.M) pout[(int64_t)co * g.tiles_img] = max_keep(a, b);
+        }
+    }
     if (STATS) {                               // every wave is its own statistics tile: stats[k][2 run + ph][2]
 #pragma unroll
         for (int e = 0; e < 16; e += 8) half_wave_sum8(s1 + e), half_wave_sum8(s2 + e);
@@ -1274,8 +1300,12 @@ struct Bop {                                  // k_wg3's B operands of one chann
 // PRE (inference launches, with BNE: the same skip): y = prelu(conv + bias) [+ residual] instead of the BatchNorm expression (see WgBnEval).
 // The residual is fetched as ADD fetches its addend -- on the fast path four channels' worth with the group's exchange reads, at y's own
 // offsets -- but from bn.residual(): the bias slot holds the conv's bias here.
+// POOL (inference launches, with BNE: the same skip; even maps, any channel count): PMAX's exchange behind the BatchNorm (+ ReLU), with NO y store
+// at all -- `y` is the POOLED tensor [N][M][H/2][W/2], which wave ph writes for channel half kq = ph after the extra barrier.  One path for
+// whole and ragged units: the unit's scalar base + a 32-bit lane offset + the running scalar channel offset, every store guarded by
+// tile < tiles_total and co < M.
 template <bool DGRAD, bool STATS, bool BNE = false, bool ODD = false, bool SH = false, bool SPLIT = false, bool ADD = false, bool PMAX = false,
-          bool PRE = false>
+          bool PRE = false, bool POOL = false>
 __global__ __launch_bounds__(SH ? 256 : 128) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, const float *__restrict__ bias,
            float *__restrict__ y, float *__restrict__ stats, WgBnEval bn) {
@@ -1284,6 +1314,7 @@ void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
     static_assert(!SPLIT || (!STATS && !BNE && !ODD), "the tail launch has the plain epilogue only");
     static_assert(!ADD || (DGRAD && !STATS && !BNE && !SPLIT), "the addend rides in plain input-gradient launches");
     static_assert(!PMAX || (STATS && !DGRAD && !BNE && !ODD && !SPLIT && !ADD), "the window maxima go out with the statistics of an even map");
+    static_assert(!POOL || (BNE && !PRE && !DGRAD && !STATS && !ODD && !SH && !SPLIT && !ADD && !PMAX), "the pooled epilogue is the BatchNorm inference epilogue's, on even maps");
     constexpr int UNITF = 2 * 64 * 64;                       // per unit: 2 x 2 raw stages (3264 floats) / the epilogue's exchange buffer (32 KB)
     constexpr int BXF = 2 * 2 * 2 * 2 * 64 * 4;              // SH: [buffer][ph][channel j][half][lane][4] transformed operands (16 KB)
     __shared__ __attribute__((aligned(16))) float smem_all[SH ? 2 * UNITF + BXF : UNITF];
@@ -1787,8 +1818,11 @@ void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
             v0 = (v0 - mu) * is * ga + be, v1 = (v1 - mu) * is * ga + be;
             if (bn.relu) v0 = relu_keep(v0), v1 = relu_keep(v1);
         }
-        if constexpr (PMAX)                    // this wave's row maximum, into the slot `got` came from (see PMAX)
+        if constexpr (PMAX || POOL)            // this wave's row maximum, into the slot `got` came from (see PMAX)
             xch[((((ph ^ 1) * 2 + kq) * 16 + e) * 64 + lane) * 2] = max_keep(v0, v1);
+        if constexpr (POOL) {                  // (no y store; the fence keeps the exchange reads in their groups, as on the fast path)
+            if ((e & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+        } else
         if constexpr (FAST) {
             f32x2 o;
             o[0] = v0, o[1] = v1;
@@ -1853,6 +1887,27 @@ void k_wg3(WgGeom g, const float *__restrict__ x, const float *__restrict__ up, 
         for (int e = 0; e < 16; ++e) {
             const float a = rowmax[e * 64 * 2], b = rowmax[(2 * 16 + e) * 64 * 2];      // left by wave 1 / by wave 0
             if (tg < ttot) ebase[eoff + (unsigned)esoff] = max_keep(a, b);
+            esoff += (e & 3) == 3 ? 5 * timg1 : timg1;
+            asm volatile("" : "+s"(esoff));
+        }
+    } else if constexpr (POOL) {
+        auto rows = [&](auto hb) {             // (the general out_half: it differs from the fast one in the y stores only, and there are none)
+            out_half(hb, std::integral_constant<int, 0>{}, std::false_type{}), out_half(hb, std::integral_constant<int, 1>{}, std::false_type{});
+        };
+        if (bias != nullptr) rows(std::true_type{}); else rows(std::false_type{});
+        __syncthreads();                       // both waves' row maxima are in the exchange buffer
+        // wave ph: channel half kq = ph.  The tile index inside the image IS the window index: y[n][co][ty][tx]
+        float *ebase = yy + (int64_t)n0 * g.M * g.tiles_img;
+        const unsigned eoff = (unsigned)((nrel * g.M + kb * 64 + ph * 32 + 4 * lh_e) * g.tiles_img + ty * g.tw + tx);
+        const int co0 = kb * 64 + ph * 32 + 4 * lh_e;
+        int timg1 = g.tiles_img;               // (a running scalar channel offset behind an opaque barrier, as HW4 above)
+        asm volatile("" : "+s"(timg1));
+        int esoff = 0;
+        const float *rowmax = xch + (ph * 16 * 64 + lane) * 2;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const float a = rowmax[e * 64 * 2], b = rowmax[(2 * 16 + e) * 64 * 2];      // left by wave 1 / by wave 0
+            if (tg < ttot && co0 + (e & 3) + 8 * (e >> 2) < g.M) ebase[eoff + (unsigned)esoff] = max_keep(a, b);
             esoff += (e & 3) == 3 ? 5 * timg1 : timg1;
             asm volatile("" : "+s"(esoff));
         }
@@ -2097,7 +2152,8 @@ enum WgMode {
     WG_FWD_BNE,       // ... + eval-mode BatchNorm (+ ReLU), dead-channel skip: the inference epilogue
     WG_FWD_PRE,       // ... + PReLU (+ residual) instead of the BatchNorm, the same skip: SphereNet's inference epilogue
     WG_DGRAD,         // gx = dgrad(gy)
-    WG_DGRAD_ADD      // ... + addend (rides in the bias slot)
+    WG_DGRAD_ADD,     // ... + addend (rides in the bias slot)
+    WG_FWD_BNE_POOL   // WG_FWD_BNE + the MaxPool2d(2, 2) behind it: y is the pooled tensor (even maps; not ODD, SH or SPLIT)
 };
 struct WgLaunch {     // the arguments every instance takes
     const WgGeom &g;
@@ -2109,7 +2165,7 @@ struct WgLaunch {     // the arguments every instance takes
 #define WG_GO(kernel, blocks, threads, a, stats_arg) \
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, (a).stream, (a).g, (a).x, (a).up, (a).bias, (a).y, stats_arg, (a).bne)
 
-// k_wg3<DGRAD, STATS, BNE, ODD, SH, SPLIT, ADD, PMAX, PRE>: 22 instances (PRE: where BNE exists).  ODD (odd maps) and SH (two units per four-wave block) exclude each
+// k_wg3<DGRAD, STATS, BNE, ODD, SH, SPLIT, ADD, PMAX, PRE, POOL>: 23 instances (PRE: where BNE exists; POOL: the even-map BNE one).  ODD (odd maps) and SH (two units per four-wave block) exclude each
 // other; SPLIT (a tail piece: raw partial output) exists for the plain forward and input gradient of even maps; SH has no BNE; PMAX
 // (window maxima) exists for the statistics forward of even maps, SH or not.
 template <bool ODD, bool SH, bool SPLIT>
@@ -2133,9 +2189,12 @@ static int wg3_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
     if constexpr (!SH && !SPLIT) {
         if (mode == WG_FWD_PRE) { WG_GO((k_wg3<false, false, true, ODD, false, false, false, false, true>), blocks, threads, a, nullptr); return CPG_OK; }
     }
+    if constexpr (!ODD && !SH && !SPLIT) {
+        if (mode == WG_FWD_BNE_POOL) { WG_GO((k_wg3<false, false, true, false, false, false, false, false, false, true>), blocks, threads, a, nullptr); return CPG_OK; }
+    }
     return fail(CPG_E_UNSUPPORTED, "conv3x3 (winograd): k_wg3 has no instance for mode %d (odd %d, shared %d, split %d)", (int)mode, ODD, SH, SPLIT);
 }
-// k_wg2<DGRAD, STATS, BNE, PRE> and k_wg1<DGRAD, STATS, BNE, PRE>: 5 instances each, no addend
+// k_wg2<DGRAD, STATS, BNE, PRE, POOL> and k_wg1<DGRAD, STATS, BNE, PRE, POOL>: 6 instances each, no addend
 static int wg2_launch(WgMode mode, unsigned blocks, const WgLaunch &a);
 static int wg1_launch(WgMode mode, unsigned blocks, const WgLaunch &a);
 // the cooperative block kernel k_wg_fwd (CPG_WINO_KERNEL=block only): packs for itself, no inference epilogue
@@ -2163,6 +2222,12 @@ static WgBnEval wg_epilogue(const cpg::EvalEpilogue *ep, int *live, int m) {
         bn.gamma = ep->gamma, bn.beta = ep->beta, bn.mean = ep->mean, bn.var = ep->var, bn.eps = ep->eps, bn.relu = ep->relu;
     bn.live = live, bn.Mp = pad_to(m, 128);
     return bn;
+}
+// ... and the mode that goes with it.  ep->pool has no slot in the block: the pooled epilogue is other code, not a run-time branch -- it picks
+// the POOL instances, whose `y` is the pooled tensor (cpg_conv3x3_wino_run_eval has refused what they do not take)
+static WgMode wg_eval_mode(const cpg::EvalEpilogue &ep) {
+    if (ep.kind == cpg::EvalEpilogue::PRELU) return WG_FWD_PRE;
+    return ep.pool ? WG_FWD_BNE_POOL : WG_FWD_BNE;
 }
 
 extern "C" int cpg_conv3x3_wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x,
@@ -2200,14 +2265,21 @@ extern "C" int cpg_conv3x3_wino_eval_ok(int N, int c_read, int m, int H, int W) 
     return wino_variant(c_read, m) != WV_BLOCK && cpg_conv3x3_wino_ok(N, c_read, m, H, W);
 }
 
-// forward with ep in the epilogue (eval-mode BatchNorm (+ ReLU), or bias, PReLU (+ residual)); live (may be null): live_words ints, zeroed
-// here, layout of k_c3_pack
+// 1: ... and so is the pooled one (ep.pool: the POOL instances of k_wg1 / k_wg2 / k_wg3 -- every launch of an even map; the ODD instances have none)
+extern "C" int cpg_conv3x3_wino_eval_pool_ok(int N, int c_read, int m, int H, int W) {
+    return !((H | W) & 1) && cpg_conv3x3_wino_eval_ok(N, c_read, m, H, W);
+}
+
+// forward with ep in the epilogue (eval-mode BatchNorm (+ ReLU) (+ MaxPool2d(2, 2): y is then the pooled tensor), or bias, PReLU (+ residual));
+// live (may be null): live_words ints, zeroed here, layout of k_c3_pack
 int cpg_conv3x3_wino_run_eval(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr, const float *bias,
                               const cpg::EvalEpilogue &ep, int *live, size_t live_words, float *y, void *ws, size_t ws_bytes, hipStream_t stream,
                               const char *what) {
     if (ep.kind == cpg::EvalEpilogue::PRELU && ep.slope == nullptr) return fail(CPG_E_INVALID, "%s(winograd): null slope", what);
     if (ep.kind == cpg::EvalEpilogue::BN_EVAL && ep.residual != nullptr)
         return fail(CPG_E_UNSUPPORTED, "%s(winograd): no residual behind the BatchNorm", what);
+    if (ep.pool && (ep.kind != cpg::EvalEpilogue::BN_EVAL || !cpg_conv3x3_wino_eval_pool_ok(N, C, K, H, W)))
+        return fail(CPG_E_UNSUPPORTED, "%s(winograd): the pooled epilogue is the BatchNorm epilogue's, on the one- and two-wave kernels of an even map", what);
     if (live != nullptr) {
         hipError_t e = hipMemsetAsync(live, 0, live_words * sizeof(int), stream);
         if (e != hipSuccess) return hip_status(e, what);
@@ -2245,7 +2317,7 @@ static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, in
         }
         const int64_t runs = (g.tiles_total + W1_T - 1) / W1_T;
         const bool persist = wino_persist();
-        WgMode mode = ep != nullptr ? (ep->kind == cpg::EvalEpilogue::PRELU ? WG_FWD_PRE : WG_FWD_BNE) : dgrad ? (addend != nullptr ? WG_DGRAD_ADD : WG_DGRAD) : stats != nullptr ? WG_FWD_STATS : WG_FWD;
+        WgMode mode = ep != nullptr ? wg_eval_mode(*ep) : dgrad ? (addend != nullptr ? WG_DGRAD_ADD : WG_DGRAD) : stats != nullptr ? WG_FWD_STATS : WG_FWD;
         // the window maxima a caller attached (cpg_conv2d_fwd_attach_pool_max): E rides in the bias slot of the PMAX instances
         float *const pool_e = mode == WG_FWD_STATS ? pool_max : nullptr;
         if (pool_e != nullptr) mode = WG_FWD_STATS_PMAX;
@@ -2335,6 +2407,7 @@ static int wg2_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
         case WG_FWD_STATS: WG_GO((k_wg2<false, true>), blocks, 128, a, a.stats); return CPG_OK;
         case WG_FWD: WG_GO((k_wg2<false, false>), blocks, 128, a, nullptr); return CPG_OK;
         case WG_FWD_PRE: WG_GO((k_wg2<false, false, true, true>), blocks, 128, a, nullptr); return CPG_OK;
+        case WG_FWD_BNE_POOL: WG_GO((k_wg2<false, false, true, false, true>), blocks, 128, a, nullptr); return CPG_OK;
         default: return fail(CPG_E_UNSUPPORTED, "conv3x3 (winograd): k_wg2 takes no addend");
     }
 }
@@ -2345,6 +2418,7 @@ static int wg1_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
         case WG_FWD_STATS: WG_GO((k_wg1<false, true>), blocks, 256, a, a.stats); return CPG_OK;
         case WG_FWD: WG_GO((k_wg1<false, false>), blocks, 256, a, nullptr); return CPG_OK;
         case WG_FWD_PRE: WG_GO((k_wg1<false, false, true, true>), blocks, 256, a, nullptr); return CPG_OK;
+        case WG_FWD_BNE_POOL: WG_GO((k_wg1<false, false, true, false, true>), blocks, 256, a, nullptr); return CPG_OK;
         default: return fail(CPG_E_UNSUPPORTED, "conv3x3 (winograd): k_wg1 takes no addend");
     }
 }

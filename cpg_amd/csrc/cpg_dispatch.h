@@ -9,7 +9,8 @@
 #include "igemm_core.h"
 
 // ---- the inference epilogue: everything an inference forward does behind the conv, named once --------------------------------------------------
-// BN_EVAL: y = [relu(] bn(conv + bias) [+ residual] [)] with an eval-mode BatchNorm2d (gamma, beta, mean, var: K floats each).
+// BN_EVAL: y = [relu(] bn(conv + bias) [+ residual] [)] with an eval-mode BatchNorm2d (gamma, beta, mean, var: K floats each);
+//          pool = 1: y = max over each 2x2 window of that (no residual), the pooled tensor alone is written.
 // PRELU:   y = prelu(conv + bias) [+ residual]; slope: K floats, or one shared (per_channel = 0).
 // residual (may be null): dense, shaped like y.  skip_stats (may be null): 2 device words that receive the dead-channel skip's
 // {4 * (input chunks up to the last live one), output blocks skipped}: written by cpg_conv3x3_fwd_eval, the only class that skips;
@@ -27,6 +28,7 @@ struct EvalEpilogue {
     int per_channel;
     const float *residual;
     int32_t *skip_stats;
+    int pool;                                   // BN_EVAL: 1 = the MaxPool2d(2, 2) behind it too, y is [N][K][H/2][W/2]; 0 (and PRELU): none
 };
 }  // namespace cpg
 
@@ -44,8 +46,10 @@ int cpg_conv3x3_fwd_bnstats(const cpg_conv_desc *d, const float *x, const float 
                             float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed, float *pool_max);
 // 1: the inference epilogues have a launch for this shape under the current option table (the planner's answer; 0: the channel-split tile)
 int cpg_conv3x3_eval_epilogue_ok(const cpg_conv_desc *d);
+// 1: ... and the pooled one (ep.pool) too: that launch is a one- or two-wave Winograd kernel on an even map (the direct tiles have none)
+int cpg_conv3x3_eval_pool_ok(const cpg_conv_desc *d);
 // forward with ep folded into the epilogue, and the dead-channel skip.  Refused: BN_EVAL with a residual; PRELU where cpg_conv3x3_eval_epilogue_ok
-// answers 0 (the channel-split tile)
+// answers 0 (the channel-split tile); ep.pool where cpg_conv3x3_eval_pool_ok answers 0
 int cpg_conv3x3_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                          const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what);
 int cpg_conv3x3_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
@@ -71,7 +75,7 @@ int cpg_conv3x3s2_bnstats_tiles(const cpg_conv_desc *d);
 // stats (may be null): [K][tiles][2] BatchNorm partial sums
 int cpg_conv3x3s2_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias, float *y,
                       float *stats, void *ws, size_t ws_bytes, hipStream_t stream);
-// forward with ep folded into the epilogue.  Refused: a residual (a strided conv opens a stage).  The strided tiles skip nothing
+// forward with ep folded into the epilogue.  Refused: a residual (a strided conv opens a stage), ep.pool.  The strided tiles skip nothing
 int cpg_conv3x3s2_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                            const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const char *what);
 int cpg_conv3x3s2_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,
@@ -106,7 +110,10 @@ int cpg_conv3x3_wino_run_side(int dgrad, int N, int c_read, int m, int H, int W,
 extern "C" int cpg_conv3x3_wino_pool_max_ok(int N, int c_read, int m, int H, int W);
 // 1: the inference epilogue is available on the Winograd kernels (not on the cooperative block kernel)
 extern "C" int cpg_conv3x3_wino_eval_ok(int N, int c_read, int m, int H, int W);
-// forward with ep in the epilogue (BN_EVAL without a residual, or PRELU; a null slope is refused) and the dead-channel skip;
+// 1: ... and the pooled one (ep.pool): every such launch of an even map
+extern "C" int cpg_conv3x3_wino_eval_pool_ok(int N, int c_read, int m, int H, int W);
+// forward with ep in the epilogue (BN_EVAL without a residual, or PRELU; a null slope is refused; ep.pool where cpg_conv3x3_wino_eval_pool_ok
+// answers 0 is refused before anything is launched) and the dead-channel skip;
 // live (may be null): live_words ints, zeroed here, layout of k_c3_pack (cpg_conv3x3_fwd_eval copies ep.skip_stats out of them)
 int cpg_conv3x3_wino_run_eval(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr, const float *bias,
                               const cpg::EvalEpilogue &ep, int *live, size_t live_words, float *y, void *ws, size_t ws_bytes, hipStream_t stream,
@@ -169,7 +176,7 @@ cpg::PackJob cpg_conv1x1_pack_job(const cpg_conv_desc *d, int dgrad);
 int cpg_conv1x1_fwd(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                     float *y, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed, float *stats = nullptr);
 int cpg_conv1x1_bnstats_tiles(const cpg_conv_desc *d);
-// forward with ep folded into the epilogue: BN_EVAL only (PRELU is refused), with or without a residual.  Nothing is skipped
+// forward with ep folded into the epilogue: BN_EVAL only (PRELU and ep.pool are refused), with or without a residual.  Nothing is skipped
 int cpg_conv1x1_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                          const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed, const char *what);
 // addend (may be null; stride 1 only): gx = dgrad(gy) + addend

@@ -780,6 +780,33 @@ extern "C" int cpg_conv2d_fwd_bn_eval(const cpg_conv_desc *d, const float *x, co
     });
 }
 
+// ... with the MaxPool2d(2, 2) behind it in the same epilogue: y_pooled[N][K][H/2][W/2], the full-resolution activation is never written.
+// The 3x3 s1 p1 class on an even map whose inference launch is a one- or two-wave Winograd kernel (cpg_conv3x3_eval_pool_ok: the planner's
+// answer); the plan, the dead-channel skip and skip_stats are cpg_conv2d_fwd_bn_eval's.
+extern "C" int32_t cpg_conv2d_fwd_bn_eval_pool_supported(const cpg_conv_desc *d) {
+    ConvGeom g;
+    if (d == nullptr || make_geom(d, g) != CPG_OK || fwd_route(d) != ROUTE_C3) return 0;
+    return cpg_conv3x3_eval_pool_ok(d) ? 1 : 0;
+}
+extern "C" int cpg_conv2d_fwd_bn_eval_pool(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr,
+                                           const float *bias, const float *gamma, const float *beta, const float *running_mean,
+                                           const float *running_var, float eps, int32_t relu, float *y_pooled, int32_t *skip_stats,
+                                           void *ws, size_t ws_bytes, void *stream) {
+    const cpg::EvalEpilogue ep{cpg::EvalEpilogue::BN_EVAL, gamma, beta, running_mean, running_var, eps, relu, nullptr, 0, nullptr, skip_stats, 1};
+    const cpg::PackedOperand packed;      // (the 3x3 s1 p1 route streams none: an armed operand stays armed, as in cpg_conv2d_fwd_bn_eval)
+    return fwd_eval(d, x, w, pm, thr, bias, ep, packed, y_pooled, ws, ws_bytes, (hipStream_t)stream, "cpg_conv2d_fwd_bn_eval_pool", [&](ConvRoute) {
+        if (!cpg_conv2d_fwd_bn_eval_pool_supported(d))
+            return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_fwd_bn_eval_pool: only the one- and two-wave Winograd launches of a 3x3 s1 p1 conv on an "
+                                           "even map pool in the epilogue");
+        if (x != nullptr && y_pooled != nullptr) {      // (null pointers are the family entry's to refuse)
+            const uintptr_t xb = (uintptr_t)x, yb = (uintptr_t)y_pooled;
+            const size_t xn = (size_t)d->N * d->C * d->H * d->W * sizeof(float), yn = (size_t)d->N * d->K * (d->H / 2) * (d->W / 2) * sizeof(float);
+            CPG_REQUIRE(xb + xn <= yb || yb + yn <= xb, "cpg_conv2d_fwd_bn_eval_pool: y_pooled overlaps x");
+        }
+        return CPG_OK;
+    });
+}
+
 // ... and the residual block's tail, conv -> eval-mode BatchNorm2d -> + residual (-> ReLU), on the pointwise kernels
 extern "C" int32_t cpg_conv2d_fwd_bn_eval_add_supported(const cpg_conv_desc *d) {
     ConvGeom g;

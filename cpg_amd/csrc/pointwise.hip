@@ -913,6 +913,7 @@ int cpg_conv1x1_fwd(const cpg_conv_desc *d, const float *x, const float *w, cons
 int cpg_conv1x1_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w, const float *pm, float thr, const float *bias,
                          const cpg::EvalEpilogue &ep, float *y, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed, const char *what) {
     if (ep.kind != cpg::EvalEpilogue::BN_EVAL) return fail(CPG_E_UNSUPPORTED, "%s(1x1): the pointwise kernels have the BatchNorm epilogue only", what);
+    if (ep.pool) return fail(CPG_E_UNSUPPORTED, "%s(1x1): the pointwise kernels do not pool in the epilogue", what);
     CPG_REQUIRE(x && w && y && ep.gamma && ep.beta && ep.mean && ep.var, "%s(1x1): null pointer", what);
     const PwBn bn{ep.gamma, ep.beta, ep.mean, ep.var, ep.eps, ep.relu};
     return pw_fwd(d, x, w, pm, thr, bias, y, ws, ws_bytes, stream, packed, nullptr, &bn, ep.residual, what);

@@ -574,6 +574,9 @@ class FusedSequential(nn.Sequential):
     fuse_pool = True
     fuse_stats = True       # conv -> BatchNorm2d: the conv kernel's epilogue produces the batch-statistics partial sums
     fuse_eval = True        # inference: conv -> BatchNorm2d(eval) -> ReLU as one kernel (BatchNorm folded into the conv epilogue)
+    # inference: conv -> BatchNorm2d(eval) -> ReLU -> MaxPool2d(2, 2) as one kernel (the pool window is the Winograd output tile; the
+    # full-resolution activation is never written).  The measurement decides the default: profiles/vgg_eval_pool_fuse.md
+    fuse_eval_pool = False
     skip_log = None         # diagnostics: set to a list to collect one int32[2] tensor per fused inference conv --
     #                         {4 * (4-channel input chunks up to the last live one), output blocks skipped by the dead-channel test}
 
@@ -586,7 +589,7 @@ class FusedSequential(nn.Sequential):
         mods = list(self._modules.values())
         n = len(mods)
         mods += [None] * 3
-        steps = (self._bn_relu, self._lone_bn, self._conv_bn_relu_eval, self._conv_bn_eval, self._stem, self._conv_bn_relu_pool, self._conv)
+        steps = (self._bn_relu, self._lone_bn, self._conv_bn_relu_pool_eval, self._conv_bn_relu_eval, self._conv_bn_eval, self._stem, self._conv_bn_relu_pool, self._conv)
         i, stats, hint = 0, None, None
         while i < n:
             window = mods[i:i + 4]
@@ -619,9 +622,26 @@ class FusedSequential(nn.Sequential):
             return None
         return 1, bn_relu(input, m, relu=False, stats=stats), None, hint
 
+    def _conv_bn_relu_pool_eval(self, mods, input, stats, hint):
+        """Inference (fuse_eval_pool): conv -> BatchNorm2d(eval) -> ReLU -> MaxPool2d(2, 2) as one kernel that writes the pooled tensor
+        alone.  Where the conv has no such kernel for this shape (forward_bn_eval_pool returns None) the steps below run exactly as
+        without this one."""
+        m, bn, relu, pool = mods
+        if not (self.fuse_eval_pool and self.fuse and self.fuse_eval and self.fuse_pool and ENABLED and not torch.is_grad_enabled()
+                and hasattr(m, 'forward_bn_eval_pool') and isinstance(bn, nn.BatchNorm2d) and not bn.training
+                and bn.track_running_stats and bn.affine and isinstance(relu, nn.ReLU) and _is_pool2(pool) and input.is_cuda):
+            return None
+        st = None if self.skip_log is None else torch.zeros(2, dtype=torch.int32, device=input.device)
+        y = m.forward_bn_eval_pool(input, bn, relu=True, skip_stats=st)
+        if y is None:
+            return None
+        if st is not None:
+            self.skip_log.append(st)
+        return 4, y, None, None
+
     def _conv_bn_relu_eval(self, mods, input, stats, hint):
-        """Inference: conv -> BatchNorm2d(eval) -> ReLU as one kernel.  (A following MaxPool2d keeps the conv + fused BN/ReLU/pool pair:
-        same HBM traffic, and the un-pooled activation is never written either way.)"""
+        """Inference: conv -> BatchNorm2d(eval) -> ReLU as one kernel.  (A following MaxPool2d(2, 2) is _conv_bn_relu_pool_eval's where that
+        step takes it; otherwise it keeps the conv + fused BN/ReLU/pool pair.)"""
         m, bn, relu, nxt3 = mods
         if not (self.fuse and self.fuse_eval and ENABLED and not torch.is_grad_enabled() and hasattr(m, 'forward_bn_eval')
                 and isinstance(bn, nn.BatchNorm2d) and not bn.training and bn.track_running_stats and bn.affine

@@ -546,7 +546,7 @@ class SharableConv2d(_Sharable):
         return getattr(self, 'math', None) or CONV_MATH
 
     def forward_with_bn_stats(self, input, bn_hint=None, pool_sink=None):
-        """(Shared with packnet_models.layers.PlainConv2d, which borrows this method, forward_with_skip, forward_bn_eval, forward_bn_eval_add, forward_prelu_eval and their frame _forward_eval: they may read
+        """(Shared with packnet_models.layers.PlainConv2d, which borrows this method, forward_with_skip, forward_bn_eval, forward_bn_eval_pool, forward_bn_eval_add, forward_prelu_eval and their frame _forward_eval: they may read
         only piggymask, info['threshold'], _math(), groups, stride, padding, dilation, weight and bias, and call forward();
         tests/test_packnet_host.py and tests/test_packnet_nets_host.py check that.)
         (y, stats): forward plus the BatchNorm partial sums of y from the same kernel; stats is None when this shape
@@ -568,12 +568,13 @@ class SharableConv2d(_Sharable):
                                                    self.stride, self.padding, self.dilation, self.groups, self._math(), bias_sink, want_stats)
         return y, (stats if stats.numel() else None), skip
 
-    def _forward_eval(self, input, entry, query_args, own):
-        """The frame forward_bn_eval, forward_bn_eval_add and forward_prelu_eval share (borrowed with them by PlainConv2d, under the same
+    def _forward_eval(self, input, entry, query_args, own, pooled=False):
+        """The frame forward_bn_eval, forward_bn_eval_pool, forward_bn_eval_add and forward_prelu_eval share (borrowed with them by PlainConv2d, under the same
         rule).  Refuses (None) grad mode, a malformed input and the arithmetics and groups without such kernels; makes the contiguous
         copies and the descriptor; asks `entry`_supported(descriptor, *query_args); lets the caller check what is its own --
         own(output shape) returns None to refuse, or (the arguments between bias and y, those between y and the workspace); then allocates
-        the output and the workspace and makes the call."""
+        the output (pooled: of the MaxPool2d(2, 2) behind the conv's own output shape -- the entry writes nothing else) and the workspace
+        and makes the call."""
         if (torch.is_grad_enabled() or input.dim() != 4 or input.shape[0] == 0 or input.shape[1] != self.weight.shape[1] * self.groups
                 or self._math() != 'fp32' or self.groups != 1):
             return None
@@ -588,7 +589,7 @@ class SharableConv2d(_Sharable):
         args = own(shape)
         if args is None:
             return None
-        y = torch.empty(shape, dtype=torch.float32, device=x.device)
+        y = torch.empty(shape[:2] + (shape[2] // 2, shape[3] // 2) if pooled else shape, dtype=torch.float32, device=x.device)
         ws, nbytes = _lib.workspace(L.cpg_conv2d_workspace_bytes(ctypes.byref(d)), x.device)
         _lib.call(entry, ctypes.byref(d), _lib.dptr(x, name='input'), _lib.dptr(w, name='weight'), _lib.dptr(p, name='piggymask'),
                   float(self.info['threshold']), _lib.dptr(self.bias, name='bias'), *args[0], _lib.dptr(y), *args[1], _lib.dptr(ws), nbytes,
@@ -602,6 +603,16 @@ class SharableConv2d(_Sharable):
         {4 * (4-channel input chunks up to the last live one), output blocks skipped} (dead-channel skip, see include/cpg_hip.h)."""
         return self._forward_eval(input, 'cpg_conv2d_fwd_bn_eval', (),
                                   lambda shape: (_bn_eval_args(bn) + (int(bool(relu)),), (_skip_stats_ptr(skip_stats),)))
+
+    def forward_bn_eval_pool(self, input, bn, relu=True, skip_stats=None):
+        """max_pool2d(relu(bn(conv(input))), 2, 2) with `bn` an eval-mode nn.BatchNorm2d, as ONE kernel (cpg_conv2d_fwd_bn_eval_pool: the
+        3x3 s1 p1 shapes on even maps that run a one- or two-wave Winograd kernel) -- bit for bit the pooled output of forward_bn_eval, which
+        is never written.  Inference only, like forward_bn_eval, with its skip_stats; returns None when grad mode is on, the input is not
+        on the device or this shape has no such kernel (the caller then runs the layers as before)."""
+        if not input.is_cuda:
+            return None
+        return self._forward_eval(input, 'cpg_conv2d_fwd_bn_eval_pool', (),
+                                  lambda shape: (_bn_eval_args(bn) + (int(bool(relu)),), (_skip_stats_ptr(skip_stats),)), pooled=True)
 
     def forward_bn_eval_add(self, input, bn, res, relu=True):
         """relu(bn(conv(input)) + res), the tail of a residual block (models/resnet.py:94-104), with `bn` an eval-mode nn.BatchNorm2d, as

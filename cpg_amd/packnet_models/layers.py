@@ -5,7 +5,7 @@ The reference's packnet_models build their trunks from stock nn.Conv2d / nn.Line
 nn.Linear -- constructor, parameters, state_dict keys and seeded initialisation are torch's -- and only their forward / backward run the
 library's convolution and GEMM kernels, with no piggymask (the kernels' `pm == NULL` form, as models.layers.HeadLinear for one layer).
 They offer the hooks FusedSequential and the residual-block helpers look for (`forward_with_bn_stats`, `forward_with_skip`,
-`forward_bn_eval`, `forward_bn_eval_add`, `forward_prelu_eval`, and `_forward_eval`, the frame those three share), so the baselines get the fused BatchNorm, stem, skip-add and inference paths of the CPG models.  fp32, HIP tensors only: no CPU fallback.
+`forward_bn_eval`, `forward_bn_eval_pool`, `forward_bn_eval_add`, `forward_prelu_eval`, and `_forward_eval`, the frame those four share), so the baselines get the fused BatchNorm, stem, skip-add and inference paths of the CPG models.  fp32, HIP tensors only: no CPU fallback.
 """
 import types
 
@@ -35,8 +35,9 @@ class PlainConv2d(nn.Conv2d):
 
     forward_with_bn_stats = nl.SharableConv2d.forward_with_bn_stats
     forward_with_skip = nl.SharableConv2d.forward_with_skip      # (residual blocks: fused_bn.conv_bn_act_skip / conv_prelu_skip)
-    _forward_eval = nl.SharableConv2d._forward_eval                  # (the frame of the three inference methods below)
+    _forward_eval = nl.SharableConv2d._forward_eval                  # (the frame of the four inference methods below)
     forward_bn_eval = nl.SharableConv2d.forward_bn_eval
+    forward_bn_eval_pool = nl.SharableConv2d.forward_bn_eval_pool    # (the conv in front of a MaxPool2d(2, 2) at inference: FusedSequential)
     forward_bn_eval_add = nl.SharableConv2d.forward_bn_eval_add      # (the Bottleneck tail at inference: fused_bn.conv_bn_add_act)
     forward_prelu_eval = nl.SharableConv2d.forward_prelu_eval        # (SphereNet's conv -> PReLU [-> + residual] at inference: fused_bn.conv_prelu)
 

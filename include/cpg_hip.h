@@ -460,6 +460,26 @@ int cpg_conv2d_fwd_bn_eval(const cpg_conv_desc *desc, const float *x, const floa
                            const float *bias, const float *gamma, const float *beta, const float *running_mean,
                            const float *running_var, float eps, int32_t relu, float *y, int32_t *skip_stats, void *workspace,
                            size_t workspace_bytes, void *stream);
+/* ... and the MaxPool2d(2, 2) of models/vgg.py:142-143 behind the group in the same kernel:
+ *     y_pooled[N][K][H/2][W/2] = max over each 2x2 window of [max(0,] (conv(x, W_eff) + bias - running_mean) / sqrt(running_var + eps) * gamma + beta [)]
+ * Per element the expression of cpg_conv2d_fwd_bn_eval -- the same operation order, invstd formed in the kernel, relu_keep -- and the
+ * four values of a window combined with max_keep: bit for bit torch.nn.functional.max_pool2d(y, 2, 2) of cpg_conv2d_fwd_bn_eval's y, a
+ * NaN in the window gives a NaN.  The full-resolution activation is never written (one F(2x2, 3x3) Winograd output tile is one window).
+ * Shapes: 3x3 / stride 1 / pad 1 / dilation 1 / groups 1 with H and W even whose inference launch is a one- or two-wave Winograd kernel
+ * (cpg_conv2d_winograd(desc, 3) == 1), any channel counts those take (78 / 156 / 313 / 627 included).  Everything else -- odd maps, the
+ * direct tiles (maps and channel counts the Winograd kernels refuse, CPG_NO_WINO), the cooperative block kernel (CPG_WINO_KERNEL=block),
+ * strided, pointwise, grouped and other descriptors -- answers 0 from cpg_conv2d_fwd_bn_eval_pool_supported(desc), the planner's answer
+ * under the current option table (no launch code runs for it), and CPG_E_UNSUPPORTED from the call before anything is launched:
+ * y_pooled is not touched.  Dead-channel skip and skip_stats: cpg_conv2d_fwd_bn_eval's for the same descriptor and option table (the
+ * liveness words are re-zeroed by every call; {0, 0} with CPG_NO_DEAD_SKIP); a block with no live output channel writes [max(0,]
+ * BatchNorm(bias) [)] to its pooled outputs.  workspace: cpg_conv2d_workspace_bytes(desc).  Pointers as for cpg_conv2d_fwd_bn_eval
+ * (bias and skip_stats may be NULL); y_pooled must not overlap x (CPG_E_INVALID).  No gradient counterpart.  Callers probe for the
+ * symbols; CPG_ABI_VERSION is unchanged. */
+int32_t cpg_conv2d_fwd_bn_eval_pool_supported(const cpg_conv_desc *desc);
+int cpg_conv2d_fwd_bn_eval_pool(const cpg_conv_desc *desc, const float *x, const float *w, const float *piggymask, float threshold,
+                                const float *bias, const float *gamma, const float *beta, const float *running_mean,
+                                const float *running_var, float eps, int32_t relu, float *y_pooled, int32_t *skip_stats, void *workspace,
+                                size_t workspace_bytes, void *stream);
 /* The residual topologies' inference (models/resnet.py:83-95 under model.eval(): `conv1 -> bn1 -> relu`, `conv2 -> bn2 -> relu`,
  * `conv3 -> bn3`, and the shortcut `downsample = nn.Sequential(conv1x1, norm_layer)` of models/resnet.py:179-182): the two entry points
  * above also take every pointwise shape (1x1, any stride, pad 0, C and K multiples of 16) and every 3x3 / stride 2 / pad 1 shape that
