@@ -234,7 +234,12 @@ class NetC(nn.Module):
         return [['conv2.weight'], ['conv2.weight', 'relu1.weight'], ['head.weight', 'head.bias']]
 
 
+EXTRA_TOPOLOGIES = {}       # name -> class(lib): topologies that other modules add (tests/_train_loop.py: the mini ResNet 'R')
+
+
 def _new(topo, lib):
+    if topo in EXTRA_TOPOLOGIES:
+        return EXTRA_TOPOLOGIES[topo](lib)
     if topo == 'A':
         return NetA(lib)
     if topo == 'C':
@@ -278,8 +283,9 @@ def build_library(topo, ref32, device):
     """The library net of `topo` with the parameters and buffers of `ref32` (strict: the names must agree)."""
     net = _new(topo, True)
     mods = dict(net.named_modules())
-    for name in net.masked:
-        mods[name].piggymask = nn.Parameter(torch.zeros(mods[name].weight.shape))
+    for name, m in ref32.named_modules():        # a piggymask wherever the reference has one (build_reference: the layers of net.masked)
+        if getattr(m, 'piggymask', None) is not None:
+            mods[name].piggymask = nn.Parameter(torch.zeros(mods[name].weight.shape))
     net.load_state_dict(ref32.state_dict(), strict=True)
     assert [n for n, _ in net.named_parameters()] == [n for n, _ in ref32.named_parameters()]
     return net.to(device)
@@ -429,10 +435,14 @@ def run(net, sit, data, device='cpu', dtype=torch.float32, mark=None):
 class Margin(object):
     """Forward pre-hooks on every ReLU / PReLU / MaxPool2d of a reference net: the smallest |pre-activation| and the smallest gap between
     the two largest values of a pooling window (taken on the ReLU's INPUT: ReLU and max commute, and two clipped zeros tie without
-    carrying any gradient)."""
+    carrying any gradient).  MaxPool2d(2, 2) and the overlapping MaxPool2d(3, 2, 1) (padded with -inf, as the pool pads; there a window
+    whose maximum the ReLU clips carries no gradient and does not count).  trace=True also keeps every tensor the margin was taken over,
+    in call order: ('act', module name, pre-activation) and ('pool', module name, window gaps, +inf where a window does not count)."""
 
-    def __init__(self, net):
+    def __init__(self, net, trace=False):
         self.value, self.count, self._pre = float('inf'), 0, None
+        self.trace = [] if trace else None
+        self._names = {m: n for n, m in net.named_modules()}
         for m in net.modules():
             if isinstance(m, (nn.ReLU, nn.PReLU)):
                 m.register_forward_pre_hook(self._act)
@@ -444,14 +454,22 @@ class Margin(object):
         self._pre = x
         self.count += x.numel()
         self.value = min(self.value, float(x.abs().min()))
+        if self.trace is not None:
+            self.trace.append(('act', self._names[mod], x))
 
     def _pool(self, mod, args):
         pre = self._pre
-        assert pre is not None and pre.shape == args[0].shape and mod.kernel_size == 2 and mod.stride == 2
-        win = pre.unfold(2, 2, 2).unfold(3, 2, 2).reshape(*pre.shape[:2], -1, 4)
+        k, s, p = mod.kernel_size, mod.stride, mod.padding
+        assert pre is not None and pre.shape == args[0].shape and (k, s, p) in ((2, 2, 0), (3, 2, 1))
+        win = F.pad(pre, (p, p, p, p), value=float('-inf')).unfold(2, k, s).unfold(3, k, s).reshape(*pre.shape[:2], -1, k * k)
         top = win.topk(2, dim=-1).values
-        self.count += top[..., 0].numel()
-        self.value = min(self.value, float((top[..., 0] - top[..., 1]).min()))
+        gap = top[..., 0] - top[..., 1]
+        if k == 3:
+            gap = torch.where(top[..., 0] > 0, gap, torch.full_like(gap, float('inf')))
+        self.count += int(torch.isfinite(gap).sum())
+        self.value = min(self.value, float(gap.min()))
+        if self.trace is not None:
+            self.trace.append(('pool', self._names[mod], gap))
 
 
 @functools.lru_cache(maxsize=None)

@@ -1055,7 +1055,11 @@ def test_train_steps_golden(arch):
     (1 of 8192 in layer4.0 in this fixture: tools/attic/diag_train_steps.py) -- ONE such flip moves that channel's d(beta) by 4 %
     and every upstream weight gradient by ~0.5 % of its scale.  They get 2e-2 of scale elementwise and 1e-2 in relative L2;
     the per-kernel accuracy behind them is pinned separately (conv / linear oracle tests at 1e-4, the fused BatchNorm kernels
-    against fp64 at 1e-6 in test_fused_bn_small_planes_fp64)."""
+    against fp64 at 1e-6 in test_fused_bn_small_planes_fp64).
+
+    The parity statement for ResNet-style steps 2 and later is tests/test_train_loop_gpu.py::test_loop_matches_fp64 (reference and
+    bound: tests/test_train_loop_host.py): shallow nets of the same blocks, stem and pool do not separate over four steps, and every
+    tensor of every step -- updates, momentum, running statistics, owner masks -- is held to fp64 at 1e-5 .. 1e-4 there."""
     from cpg_amd.models.spherenet import AngleLoss
     g = load_golden('train_steps_' + arch)
     width, ncls = float(g['width']), int(g['num_classes'])
