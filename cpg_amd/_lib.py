@@ -167,6 +167,13 @@ _SIGNATURES = {
                                            _i64, _vp]),
     'cpg_pair_distance': (_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     'cpg_pair_sweep': (_int, [_vp, _vp, _i64, ctypes.POINTER(_f64), _i32, _i32, _vp, _vp, _vp]),
+    'cpg_pair_fold_mean': (_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
+    'cpg_pair_distance_centred': (_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+    'cpg_pair_sweep_folds': (_int, [_vp, _i64, _vp, _i64, ctypes.POINTER(_f64), _i32, _i32, _vp, _vp, _vp]),
+    'cpg_pair_val_max_thresholds': (_i32, []),
+    'cpg_pair_val_workspace_bytes': (_sz, [_i32]),
+    'cpg_pair_val_table': (_int, [_vp, _i64, _vp, _i64, ctypes.POINTER(_f64), _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    'cpg_pair_val_at': (_int, [_vp, _i64, _vp, _i64, ctypes.POINTER(_f64), _i32, _vp, _vp]),
     'cpg_loss_heads_workspace_bytes': (_sz, [_i32, _i32, _i32]),
     'cpg_softmax_xent_fwd': (_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     'cpg_softmax_xent_fwd_bwd': (_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -119,18 +119,26 @@ class ManagerBase(object):
         loss = self.criterion(output, target)
         return loss, classification_accuracy(output, target)
 
-    def score_pairs(self, embeddings, epoch_idx=0):
-        """The scoring half of evalLFW on eval_embeddings' list of (emb_a, emb_p, issame) batches."""
-        from .metrics import fv_evaluate
+    def score_pairs(self, embeddings, epoch_idx=0, full=False, subtract_mean=False):
+        """The scoring half of evalLFW on eval_embeddings' list of (emb_a, emb_p, issame) batches.  By default the 10-fold accuracy
+        alone, as evalLFW uses it.  full=True also fills `last_lfw` with VAL@FAR = 1e-3 over the reference's fine table
+        np.arange(0, 4, 0.001): 'val_train' / 'far_train' (every fold's training table), 'val', 'val_std', 'far' by the reference's
+        rule -- NaN, with the reason in 'val_error', where the reference raises (its interpolation, or a test fold without a "same"
+        or a "different" pair: cpg_amd/utils/metrics.py) -- and 'val_first', 'val_first_std', 'far_first' ('val_first_error') at
+        each fold's largest threshold whose training FAR stays within the target."""
+        from . import metrics
         if not embeddings or not all(isinstance(b, tuple) and len(b) == 3 for b in embeddings):
             raise ValueError('evalLFW needs a validation loader of (a, p, issame) batches')
         emb_a = torch.cat([b[0] for b in embeddings])
         emb_p = torch.cat([b[1] for b in embeddings])
         labels = torch.cat([torch.as_tensor(b[2]).reshape(-1).to(emb_a.device) for b in embeddings])
-        tpr, fpr, accuracy, val, val_std, far = fv_evaluate(emb_a, emb_p, labels, distance_metric=True, subtract_mean=False,
-                                                            threshold_dtype=getattr(self.args, 'lfw_threshold_dtype', 'float64'))
+        dtype = getattr(self.args, 'lfw_threshold_dtype', 'float64')
+        # calculate_roc's three steps (the distances are kept for VAL@FAR)
+        dist = metrics.fold_distances(emb_a, emb_p, labels, 10, True, subtract_mean)
+        tpr, fpr, accuracy = metrics.roc_from_counts(*metrics.roc_counts(np.arange(0, 4, 0.01), dist, labels, 10, dtype))
+        extra = self._val_at_far(metrics, dist, labels, dtype) if full else {}
         mean, std = np.mean(accuracy), np.std(accuracy)
-        self.last_lfw = {'tpr': tpr, 'fpr': fpr, 'accuracy': accuracy}
+        self.last_lfw = dict(extra, tpr=tpr, fpr=fpr, accuracy=accuracy)
         self.last_stats = dict(self.last_stats, accuracy=float(mean), accuracy_std=float(std))
         if self.progress:
             print('In evalLFW(): Test set: Accuracy: {:.5f}+-{:.5f}'.format(mean, std))
@@ -139,6 +147,21 @@ class ManagerBase(object):
                           + 'Test set: Accuracy: {:.5f}+-{:.5f}, '.format(mean, std)
                           + 'task_ratio: {:.2f}'.format(self.pruner.calculate_curr_task_ratio())))
         return mean
+
+    @staticmethod
+    def _val_at_far(metrics, dist, labels, dtype, far_target=1e-3):
+        thr = metrics._thresholds(np.arange(0, 4, 0.001), dtype)
+        val_train, far_train = metrics.val_tables(thr, dist, labels, 10)
+        out = {'val_train': val_train, 'far_train': far_train, 'far_target': far_target}
+        nan = float('nan')
+        for rule, keys in ((metrics.threshold_at_far, ('val', 'val_std', 'far', 'val_error')),
+                           (metrics.first_at_far, ('val_first', 'val_first_std', 'far_first', 'val_first_error'))):
+            try:        # the interpolation's ValueError, or a test fold without a "same" / "different" pair (ZeroDivisionError)
+                val, far = metrics.val_far_at([rule(f, thr, far_target) for f in far_train], dist, labels, 10, dtype)
+                out.update(zip(keys, (np.mean(val), np.std(val), np.mean(far))))
+            except (ValueError, ZeroDivisionError) as e:
+                out.update(zip(keys, (nan, nan, nan, '%s: %s' % (type(e).__name__, e))))
+        return out
 
 
 class Manager(ManagerBase):
@@ -284,14 +307,16 @@ class Manager(ManagerBase):
                                    'task{} ratio'.format(self.inference_dataset_idx): self.pruner.calculate_curr_task_ratio()}
         return out
 
-    def evalLFW(self, epoch_idx):
+    def evalLFW(self, epoch_idx, full=False, subtract_mean=False):
         """utils/manager.py:156-195: apply_mask(), eval mode, `forward_to_embeddings` of both images of every (a, p, issame) batch
         (eval_embeddings), then fv_evaluate(distance_metric=True, subtract_mean=False) over the reference's thresholds
         np.arange(0, 4, 0.01) -- distances and the 10-fold threshold search on the device, the embeddings never leave it.  Logs
         `Accuracy mean+-std` as the reference does and returns np.mean(accuracy).  args.lfw_threshold_dtype = 'float32' compares
         as numpy 1.x did (cpg_amd/utils/metrics.py); the default is numpy >= 2's fp64 comparison.  Under data parallelism with a
-        replicated pair loader every rank scores every pair and returns the same value."""
-        return self.score_pairs(self.eval_embeddings(epoch_idx), epoch_idx)
+        replicated pair loader every rank scores every pair and returns the same value.  full=True also leaves VAL@FAR = 1e-3 and
+        the folds' training tables in `last_lfw`, subtract_mean=True centres every fold on its training mean (score_pairs); the
+        return value stays np.mean(accuracy)."""
+        return self.score_pairs(self.eval_embeddings(epoch_idx), epoch_idx, full=full, subtract_mean=subtract_mean)
 
     # ------------------------------------------------------------------ checkpoints (utils/manager.py:198-320)
     def save_checkpoint(self, optimizers, epoch_idx, save_folder):

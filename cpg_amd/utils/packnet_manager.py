@@ -117,11 +117,11 @@ class Manager(ManagerBase):
                 out.append((root.forward_to_embeddings(a), root.forward_to_embeddings(p), label))
         return out
 
-    def evalLFW(self, epoch_idx):
+    def evalLFW(self, epoch_idx, full=False, subtract_mean=False):
         """utils/packnet_manager.py:109-144: fv_evaluate(distance_metric=True, subtract_mean=False) over the pair embeddings, on the
         scoring path of utils.manager.Manager.evalLFW (cpg_amd/utils/metrics.py: distances and the 10-fold threshold search on the device;
-        args.lfw_threshold_dtype as there).  Returns np.mean(accuracy)."""
-        return self.score_pairs(self.eval_embeddings(epoch_idx), epoch_idx)
+        args.lfw_threshold_dtype as there; full and subtract_mean as there too).  Returns np.mean(accuracy)."""
+        return self.score_pairs(self.eval_embeddings(epoch_idx), epoch_idx, full=full, subtract_mean=subtract_mean)
 
     def one_shot_prune(self, one_shot_prune_perc):
         self.pruner.one_shot_prune(one_shot_prune_perc)

@@ -735,6 +735,43 @@ int cpg_pair_distance(const float *a, int64_t lda, const float *b, int64_t ldb, 
 int cpg_pair_sweep(const float *dist, const uint8_t *issame, int64_t n, const double *thr_host, int32_t n_thr, int32_t nfolds, int64_t *counts,
                    int64_t *best, void *stream);
 
+/* ---- pair verification with subtract_mean, and VAL@FAR (utils/metrics.py: calculate_roc / calculate_val with subtract_mean=True,
+ * calculate_val_far).  Compatible additions: the ABI version stays 3.  Folds are KFold(nfolds, shuffle=False)'s, as above.
+ *
+ * cpg_pair_fold_mean: mean[f][c], fp32 [nfolds][d], = np.mean(np.concatenate([a[train_f], b[train_f]]), axis=0)[c], train_f every pair
+ * outside fold f: the sum starts from the add reduction's identity 0 and takes the 2 (n - |fold f|) rows one after another, a's
+ * first (numpy's order for axis 0 of a C-contiguous float32 matrix; for d == 1 the rows form one contiguous run, which numpy sums
+ * pairwise as cpg_pair_distance's row sums), then one division by float32(row count).  Every (fold, column) walks its own rows: no
+ * "total minus the fold".  Bit-identical to numpy.  nfolds >= 2, n >= nfolds.
+ *
+ * cpg_pair_distance_centred: cpg_pair_distance of (a - mean[f], b - mean[f]) for every fold f < nfolds, each difference rounded to
+ * fp32 before use: dist (and sim, may be NULL) are fp32 [nfolds][n], row f for fold f.  Same arithmetic and order as
+ * cpg_pair_distance otherwise.
+ *
+ * cpg_pair_sweep_folds: cpg_pair_sweep where fold f reads row f of a distance matrix [nfolds][ldd], ldd >= n.
+ *
+ * cpg_pair_val_table: calculate_val's inner loop.  table: int64 [nfolds][n_thr][2] = {true accepts, false accepts} of fold f's
+ * TRAIN pairs at threshold t ((double)dist < thr[t], as cpg_pair_sweep); totals: int64 [nfolds][2] = {n_same, n_diff} of those
+ * pairs.  ldd == 0: every fold reads the same n distances; ldd >= n: fold f reads row f.  thr_host: a HOST table of n_thr strictly
+ * ascending fp64 values, 1 <= n_thr <= cpg_pair_val_max_thresholds (the kernel keeps two histograms of n_thr + 1 counters in
+ * one block's LDS; a longer table is refused with CPG_E_INVALID, never truncated).  workspace: cpg_pair_val_workspace_bytes(n_thr)
+ * bytes of device memory, 8-byte aligned (the table's device copy; 0 for an n_thr the call refuses).
+ *
+ * cpg_pair_val_at: calculate_val_far on every fold's TEST pairs at one threshold per fold.  thr_host: nfolds HOST fp64 values (any
+ * value; NaN accepts nothing).  out: int64 [nfolds][4] = {true accepts, false accepts, n_same, n_diff}.  nfolds >= 1 (one fold: all
+ * n pairs).  ldd as for cpg_pair_val_table. */
+int cpg_pair_fold_mean(const float *a, int64_t lda, const float *b, int64_t ldb, int64_t n, int32_t d, int32_t nfolds, float *mean, void *stream);
+int cpg_pair_distance_centred(const float *a, int64_t lda, const float *b, int64_t ldb, int64_t n, int32_t d, int32_t metric, const float *mean,
+                              int32_t nfolds, float *dist, float *sim, void *stream);
+int cpg_pair_sweep_folds(const float *dist, int64_t ldd, const uint8_t *issame, int64_t n, const double *thr_host, int32_t n_thr, int32_t nfolds,
+                         int64_t *counts, int64_t *best, void *stream);
+int32_t cpg_pair_val_max_thresholds(void);
+size_t cpg_pair_val_workspace_bytes(int32_t n_thr);
+int cpg_pair_val_table(const float *dist, int64_t ldd, const uint8_t *issame, int64_t n, const double *thr_host, int32_t n_thr, int32_t nfolds,
+                       int64_t *table, int64_t *totals, void *workspace, size_t workspace_bytes, void *stream);
+int cpg_pair_val_at(const float *dist, int64_t ldd, const uint8_t *issame, int64_t n, const double *thr_host, int32_t nfolds, int64_t *out,
+                    void *stream);
+
 /* ---- loss heads: from the network's output to the loss, the accuracy and the gradient that starts the backward pass.  Compatible
  * additions: the ABI version stays 3 (probe with dlsym, as for the rider entries above).  Every reduction has a fixed order (no
  * floating-point atomics): two calls on the same inputs give the same bytes.  loss and correct are ONE float each in device memory;

@@ -7,6 +7,11 @@ replaces.
           host, tpr / fpr / accuracy), device-synchronised wall clock.
   host    the same scoring the reference's way: numpy distance (np.sum, np.linalg.norm, np.arccos), then for every fold the
           400 + 400 calculate_accuracy calls of calculate_roc on the train and test slices.
+  fv      the whole of fv_evaluate's work at the same size, subtract_mean False and True: the folds' distances (with the means and
+          the centred F x n distance matrix when subtract_mean), calculate_roc's sweep over 400 thresholds and calculate_val's over
+          4 000, the thresholds at FAR = 1e-3 and the test folds' val / far.  The reference's own interpolation raises on such a
+          table (far_train repeats values), so both sides pick the thresholds with first_at_far's rule.  Device: every new kernel in
+          HIP events, and the whole call in device-synchronised wall clock.  Host: the reference's loops in numpy, as `host` above.
   evallfw Manager.evalLFW of a width-1.0 SphereNet-20 over 6 000 PairLoader pairs drawn from a synthetic 12 000-image store at
           112 x 112, batch 256: embeddings, scoring, logging -- device-synchronised wall clock.
 
@@ -91,6 +96,85 @@ def part_device(reps):
             'device': torch.cuda.get_device_name(0)}
 
 
+def _device_fv(metrics, a, b, same, subtract_mean):
+    thr = np.arange(0, 4, 0.001)
+    dist = metrics.fold_distances(a, b, same, FOLDS, 1, subtract_mean)
+    roc = metrics.roc_from_counts(*metrics.roc_counts(np.arange(0, 4, 0.01), dist, same, FOLDS))
+    _, far_train = metrics.val_tables(thr, dist, same, FOLDS)
+    val, far = metrics.val_far_at([metrics.first_at_far(f, thr, 1e-3) for f in far_train], dist, same, FOLDS)
+    return roc + (np.mean(val), np.std(val), np.mean(far))
+
+
+def part_fv(reps, host_reps):
+    import ctypes
+    import torch
+    from cpg_amd import _lib
+    from cpg_amd.utils import metrics
+    rng = np.random.default_rng(1)
+    e1, e2, same = _pairs(rng)
+    a, b = torch.from_numpy(e1).cuda(), torch.from_numpy(e2).cuda()
+    lab = torch.from_numpy(same.astype(np.uint8)).cuda()
+    h = _lib.lib()
+    sp, i64 = _lib.stream_ptr, lambda t: ctypes.c_void_p(t.data_ptr())
+    thr_roc, thr_val = np.arange(0, 4, 0.01), np.arange(0, 4, 0.001)
+    p_roc, p_val = (t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) for t in (thr_roc, thr_val))
+    mean = torch.empty((FOLDS, DIM), device='cuda')
+    dist = torch.empty((FOLDS, N_PAIRS), device='cuda')
+    counts = torch.empty((FOLDS, 400, 4), dtype=torch.int64, device='cuda')
+    best = torch.empty(FOLDS, dtype=torch.int64, device='cuda')
+    table = torch.empty((FOLDS, 4000, 2), dtype=torch.int64, device='cuda')
+    totals = torch.empty((FOLDS, 2), dtype=torch.int64, device='cuda')
+    out = torch.empty((FOLDS, 4), dtype=torch.int64, device='cuda')
+    ws, nbytes = _lib.workspace(int(h.cpg_pair_val_workspace_bytes(4000)), 'cuda')
+    at = np.full(FOLDS, 0.9)
+    p_at = at.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    calls = {
+        'fold_mean': lambda: h.cpg_pair_fold_mean(_lib.dptr(a), DIM, _lib.dptr(b), DIM, N_PAIRS, DIM, FOLDS, _lib.dptr(mean), sp()),
+        'distance_centred': lambda: h.cpg_pair_distance_centred(_lib.dptr(a), DIM, _lib.dptr(b), DIM, N_PAIRS, DIM, 1, _lib.dptr(mean), FOLDS,
+                                                                _lib.dptr(dist), None, sp()),
+        'sweep_folds': lambda: h.cpg_pair_sweep_folds(_lib.dptr(dist), N_PAIRS, _lib.dptr(lab, torch.uint8), N_PAIRS, p_roc, 400, FOLDS,
+                                                      i64(counts), i64(best), sp()),
+        'val_table_rows': lambda: h.cpg_pair_val_table(_lib.dptr(dist), N_PAIRS, _lib.dptr(lab, torch.uint8), N_PAIRS, p_val, 4000, FOLDS,
+                                                       i64(table), i64(totals), _lib.dptr(ws), nbytes, sp()),
+        'val_table_shared': lambda: h.cpg_pair_val_table(_lib.dptr(dist), 0, _lib.dptr(lab, torch.uint8), N_PAIRS, p_val, 4000, FOLDS,
+                                                         i64(table), i64(totals), _lib.dptr(ws), nbytes, sp()),
+        'val_at': lambda: h.cpg_pair_val_at(_lib.dptr(dist), N_PAIRS, _lib.dptr(lab, torch.uint8), N_PAIRS, p_at, FOLDS, i64(out), sp()),
+    }
+    rec = {'pairs': N_PAIRS, 'dim': DIM, 'folds': FOLDS, 'reps': reps, 'host_reps': host_reps, 'kernels_ms': {}}
+    for name, fn in calls.items():
+        ts = []
+        for i in range(reps + 5):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            _lib.check(name, fn())
+            e.record()
+            e.synchronize()
+            if i >= 5:
+                ts.append(s.elapsed_time(e))
+        rec['kernels_ms'][name] = {'median': float(np.median(ts)), 'min': float(min(ts))}
+    for sm in (False, True):
+        walls = []
+        for i in range(reps + 3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = _device_fv(metrics, a, b, same, sm)
+            torch.cuda.synchronize()
+            if i >= 3:
+                walls.append((time.perf_counter() - t0) * 1e3)
+        hosts = []
+        for _ in range(host_reps):
+            t0 = time.perf_counter()
+            want = _host_fv(e1, e2, same, sm)
+            hosts.append((time.perf_counter() - t0) * 1e3)
+        key = 'subtract_mean' if sm else 'plain'
+        rec[key] = {'device_wall_ms_median': float(np.median(walls)), 'device_wall_ms_min': float(min(walls)),
+                    'host_wall_ms_median': float(np.median(hosts)), 'host_wall_ms_min': float(min(hosts)),
+                    'device_accuracy': float(np.mean(got[2])), 'host_accuracy': float(np.mean(want[2])),
+                    'device_val': float(got[3]), 'host_val': float(want[3])}
+    rec['numpy'], rec['threads'] = np.__version__, os.environ.get('OMP_NUM_THREADS')
+    return rec
+
+
 def _host_accuracy(threshold, dist, issame):
     predict = np.less(dist, threshold)
     tp = np.sum(np.logical_and(predict, issame))
@@ -121,6 +205,49 @@ def _host_roc(thr, e1, e2, issame):
             tprs[f, i], fprs[f, i], _ = _host_accuracy(t, dist[test], issame[test])
         acc[f] = _host_accuracy(thr[b], dist[test], issame[test])[2]
     return np.mean(tprs, 0), np.mean(fprs, 0), acc
+
+
+def _host_distance(e1, e2):
+    dot = np.sum(np.multiply(e1, e2), axis=1)
+    norm = np.linalg.norm(e1, axis=1) * np.linalg.norm(e2, axis=1)
+    return np.arccos(np.clip(dot / norm, 0, 1)) * 4 / math.pi
+
+
+def _host_val_far(threshold, dist, issame):
+    predict = np.less(dist, threshold)
+    ta = np.sum(np.logical_and(predict, issame))
+    fa = np.sum(np.logical_and(predict, np.logical_not(issame)))
+    return float(ta) / float(np.sum(issame)), float(fa) / float(np.sum(np.logical_not(issame)))
+
+
+def _host_fv(e1, e2, issame, subtract_mean):
+    """fv_evaluate the reference's way (calculate_roc, then calculate_val, each with its own distances per fold), the threshold at
+    the FAR target by first_at_far's rule."""
+    thr_roc, thr_val = np.arange(0, 4, 0.01), np.arange(0, 4, 0.001)
+    n = len(issame)
+    tprs, fprs, acc = np.zeros((FOLDS, 400)), np.zeros((FOLDS, 400)), np.zeros(FOLDS)
+    val, far = np.zeros(FOLDS), np.zeros(FOLDS)
+    q, r = divmod(n, FOLDS)
+    for which in ('roc', 'val'):
+        at = 0
+        for f in range(FOLDS):
+            size = q + (1 if f < r else 0)
+            test = np.arange(at, at + size)
+            train = np.concatenate([np.arange(0, at), np.arange(at + size, n)])
+            at += size
+            mean = np.mean(np.concatenate([e1[train], e2[train]]), axis=0) if subtract_mean else 0.0
+            dist = _host_distance(e1 - mean, e2 - mean)
+            if which == 'roc':
+                acc_train = np.array([_host_accuracy(t, dist[train], issame[train])[2] for t in thr_roc])
+                b = int(np.argmax(acc_train))
+                for i, t in enumerate(thr_roc):
+                    tprs[f, i], fprs[f, i], _ = _host_accuracy(t, dist[test], issame[test])
+                acc[f] = _host_accuracy(thr_roc[b], dist[test], issame[test])[2]
+            else:
+                far_train = np.array([_host_val_far(t, dist[train], issame[train])[1] for t in thr_val])
+                ok = np.nonzero(far_train <= 1e-3)[0]
+                val[f], far[f] = _host_val_far(thr_val[ok[-1]] if len(ok) else 0.0, dist[test], issame[test])
+    return np.mean(tprs, 0), np.mean(fprs, 0), acc, np.mean(val), np.std(val), np.mean(far)
 
 
 def part_host(reps):
@@ -171,7 +298,7 @@ def part_evallfw(reps, batch):
 
 
 def _md(rec, cmd):
-    d, h, e = rec.get('device'), rec.get('host'), rec.get('evallfw')
+    d, h, e, v = rec.get('device'), rec.get('host'), rec.get('evallfw'), rec.get('fv')
     out = ['# LFW pair scoring: device kernels, the host computation they replace, and a whole evalLFW (`tools/verify_bench.py`)', '',
            'One MI355X, one process.  Record: `verify_bench.json`, written by `%s`.  Synthetic data: the cost depends on the sizes only.' % cmd,
            '']
@@ -186,6 +313,15 @@ def _md(rec, cmd):
         out += ['## Host restatement: numpy distance + the reference\'s calculate_roc loops (%s threads, numpy %s)' % (h['threads'], h['numpy']), '',
                 '| step | median ms | min ms |', '|---|---|---|',
                 '| distance + 10 folds x (400 train + 400 test) calculate_accuracy | %.1f | %.1f |' % (h['wall_ms_median'], h['wall_ms_min']), '']
+    if v:
+        out += ['## fv_evaluate\'s whole work (roc over 400 thresholds, VAL@FAR over 4 000), %d pairs x %d, metric 1, %d folds' % (v['pairs'], v['dim'], v['folds']),
+                '', '| kernel (HIP events) | median ms | min ms |', '|---|---|---|']
+        out += ['| cpg_pair_%s | %.4f | %.4f |' % (k, t['median'], t['min']) for k, t in v['kernels_ms'].items()]
+        out += ['', '| whole call (wall clock) | device median ms | device min ms | host numpy median ms | host min ms |', '|---|---|---|---|---|']
+        out += ['| subtract_mean=%s | %.3f | %.3f | %.1f | %.1f |' % (k == 'subtract_mean', v[k]['device_wall_ms_median'], v[k]['device_wall_ms_min'],
+                                                                      v[k]['host_wall_ms_median'], v[k]['host_wall_ms_min']) for k in ('plain', 'subtract_mean')]
+        out += ['', 'Host: the reference\'s loops in numpy %s with %s threads; both sides take each fold\'s threshold by first_at_far\'s rule (the '
+                'reference\'s interpolation raises on this table).' % (v['numpy'], v['threads']), '']
     if e:
         out += ['## Manager.evalLFW: SphereNet-20 width 1.0, %d pairs from a %d-image store at 112 x 112, batch %d'
                 % (e['pairs'], e['images'], e['batch']), '',
@@ -197,7 +333,7 @@ def _md(rec, cmd):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--part', default='all', choices=['all', 'device', 'host', 'evallfw'])
+    ap.add_argument('--part', default='all', choices=['all', 'device', 'host', 'fv', 'evallfw'])
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--host-reps', type=int, default=3)
     ap.add_argument('--lfw-reps', type=int, default=3)
@@ -210,6 +346,8 @@ def main():
         rec['device'] = part_device(a.reps)
     if a.part in ('all', 'host'):
         rec['host'] = part_host(a.host_reps)
+    if a.part in ('all', 'fv'):
+        rec['fv'] = part_fv(a.reps, a.host_reps)
     if a.part in ('all', 'evallfw'):
         rec['evallfw'] = part_evallfw(a.lfw_reps, a.batch)
     argv, skip = [], False
