@@ -318,7 +318,8 @@ using X3N1 = B16Cfg<128, 8, 32, 2, 2, 1, 2, 1>;
 int run(bool dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm, float thr,
         const float *bias, float *y, void *ws, size_t ws_bytes, hipStream_t stream, int np) {
     const char *what = dgrad ? "cpg_conv2d_dgrad_bf16" : "cpg_conv2d_fwd_bf16";
-    const size_t need = packb_bytes(c_read, m, np);
+    // the published size (cpg_conv2d_bf16_workspace_bytes), whatever part of it this pass and plane count use: one rule for all entry points
+    const size_t need = std::max(packb_bytes(C, K), packb_bytes(K, C));
     if (ws == nullptr || ws_bytes < need) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
     CPG_REQUIRE((((uintptr_t)ws) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
     u32x4 *wp = (u32x4 *)ws;
@@ -582,7 +583,9 @@ inline int wpick(const cpg_conv_desc *d) { return d->W % 8 == 0 && d->W >= 56 ? 
 template <class Cfg>
 int wlaunch(const cpg_conv_desc *d, const float *x, const float *gy, const Epilogue &ep, void *ws, size_t ws_bytes, hipStream_t stream) {
     const B16WPlan p = wplan<Cfg>(d);
-    if (ws == nullptr || ws_bytes < p.ws_bytes) return fail(CPG_E_WORKSPACE, "cpg_conv2d_wgrad_bf16: workspace %zu < %zu bytes", ws_bytes, p.ws_bytes);
+    const size_t need = cpg_conv2d_wgrad_bf16_workspace_bytes(d);      // the published size: the larger of the one- and two-plane plans
+    if (ws == nullptr || ws_bytes < need) return fail(CPG_E_WORKSPACE, "cpg_conv2d_wgrad_bf16: workspace %zu < %zu bytes", ws_bytes, need);
+    CPG_REQUIRE((((uintptr_t)ws) & 15) == 0, "cpg_conv2d_wgrad_bf16: workspace must be 16-byte aligned");      // (as the forward's: one rule for both)
     constexpr size_t smem = (size_t)Cfg::NSTAGE * Cfg::STAGEQ * sizeof(u32x4);
     static_assert(smem <= 160 * 1024, "LDS budget");
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_c3b_wgrad<Cfg>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);

@@ -527,7 +527,13 @@ int cpg_conv2d_fwd_prelu_eval(const cpg_conv_desc *desc, const float *x, const f
  * The *_bf16x3 entry points run the same kernels with every operand split into two bf16 terms, v = hi + lo (hi = bf16(v),
  * lo = bf16(v - hi)), and accumulate a_hi*b_hi + a_hi*b_lo + a_lo*b_hi in fp32: ~16 mantissa bits per product instead of 8
  * (measured 5e-6 of the output scale per layer against 2.5e-3 for plain bf16 and 2.5e-7 for fp32 MFMA) at 3/16 of the fp32
- * MFMA cost.  Also opt-in: it meets north_star's 1e-4 logit bar, but it is not the reference's fp32 arithmetic. */
+ * MFMA cost.  Also opt-in: it meets north_star's 1e-4 logit bar, but it is not the reference's fp32 arithmetic.
+ * Non-finite values: bf16x3 turns an Inf operand into NaN (lo = Inf - Inf), where plain bf16 keeps it an Inf
+ * (tests/test_conv_bf16_gpu.py test_an_inf_operand_is_nan_under_bf16x3_and_inf_under_bf16).  Both arithmetics round a finite |v|
+ * above bf16's largest finite value (about 3.3895e38) to Inf, so such an operand leaves no finite output where fp32 would
+ * (test_a_finite_value_above_the_bf16_range_is_not_finite).
+ * Workspaces: every bf16 entry point refuses (CPG_E_WORKSPACE) less than its query's answer, whatever part of it the call
+ * uses, and (CPG_E_INVALID) a workspace that is not 16-byte aligned. */
 int32_t cpg_conv2d_bf16_supported(const cpg_conv_desc *desc);
 int32_t cpg_conv2d_wgrad_bf16_supported(const cpg_conv_desc *desc);
 size_t cpg_conv2d_wgrad_bf16_workspace_bytes(const cpg_conv_desc *desc);

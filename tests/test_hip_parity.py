@@ -631,8 +631,10 @@ def test_conv_bf16x3_meets_the_fp32_bar(N, C, H, W, K, pm):
     if pm:
         layer.piggymask = nn.Parameter(pmv.to(DEV))
     xd = x.to(DEV).requires_grad_(True)
-    y = layer(xd)
-    y.backward(gy.to(DEV))
+    import _bf16_cases
+    with _bf16_cases.recording() as ran:
+        y = layer(xd)
+        y.backward(gy.to(DEV))
     y32 = ops.conv2d_forward(x.numpy(), w.numpy(), None if pmv is None else pmv.numpy(), None, 1, 1, 1)
     r = ops.conv2d_backward(x.numpy(), w.numpy(), gy.numpy(), None if pmv is None else pmv.numpy(), False, 1, 1, 1)
 
@@ -640,7 +642,7 @@ def test_conv_bf16x3_meets_the_fp32_bar(N, C, H, W, K, pm):
         return float(np.abs(a.detach().cpu().numpy() - ref).max() / np.abs(ref).max())
     errs = (rel(y, y32), rel(xd.grad, r['gx']), rel(layer.weight.grad, r['gw']))
     assert max(errs) < 1e-4, errs
-    assert min(errs) > 5e-8 or True
+    assert [n for n in ran if n.startswith('cpg_conv2d_')] == list(_bf16_cases.ENTRY['bf16x3']), ran      # the three x3 kernels, nothing else
     if pm:
         assert rel(layer.piggymask.grad, r['gpm']) < 1e-4
 
