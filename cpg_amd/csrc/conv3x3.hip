@@ -1248,16 +1248,23 @@ int run_fwd(bool dgrad, int N, int c_read, int m, int H, int W, int K, int C, co
     const char *what = dgrad ? "cpg_conv2d_dgrad(3x3)" : "cpg_conv2d_fwd(3x3)";
     C3Extra ex = extra;             // (ex.live is filled in below)
     const C3Plan plan = plan_fwd(dgrad, N, c_read, m, H, W, ex.bb ? C3_BN_BWD : ex.eval ? C3_BN_EVAL : ex.stats ? C3_STATS : C3_PLAIN);
-    if (plan.route == C3_WINO)
-        return cpg_conv3x3_wino_run_side(dgrad ? 1 : 0, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, ex.stats, ws, ws_bytes, stream, ex.packed, ex.pool_max);
-    // Workspace layout of the Winograd inference forward:
-    // [the direct kernels' packed-weight region (unused) | liveness words, where cpg_conv3x3_fwd_eval looks for them | U]
-    if (plan.route == C3_WINO_EVAL) {
+    if (plan.route == C3_WINO || plan.route == C3_WINO_EVAL) {
+        cpg::WinoCall c{};
+        c.dgrad = dgrad ? 1 : 0, c.N = N, c.c_read = c_read, c.m = m, c.H = H, c.W = W, c.K = K, c.C = C;
+        c.x = x, c.w = w, c.pm = pm, c.thr = thr, c.bias = bias, c.y = y, c.stream = stream;
+        if (plan.route == C3_WINO) {
+            c.stats = ex.stats, c.pool_max = ex.pool_max, c.packed = ex.packed;
+            c.ws = ws, c.ws_bytes = ws_bytes, c.what = dgrad ? "cpg_conv2d_dgrad" : "cpg_conv2d_fwd";
+            return cpg_conv3x3_wino_launch(c);
+        }
+        // Workspace layout of the Winograd inference forward:
+        // [the direct kernels' packed-weight region (unused) | liveness words, where cpg_conv3x3_fwd_eval looks for them | U]
         const size_t off = (pack_bytes(c_read, m) + 15) / 16 * 16;
         if (ws == nullptr || ws_bytes < off) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, off);
-        int *live = ex.skip ? reinterpret_cast<int *>((float *)ws + pack_floats(c_read, m)) : nullptr;
-        return cpg_conv3x3_wino_run_eval(N, c_read, m, H, W, x, w, pm, thr, bias, *ex.eval, live, live_words(c_read, m), y, (char *)ws + off,
-                                         ws_bytes - off, stream, ex.what);
+        c.ep = ex.eval, c.live_words = live_words(c_read, m);
+        c.live = ex.skip ? reinterpret_cast<int *>((float *)ws + pack_floats(c_read, m)) : nullptr;
+        c.ws = (char *)ws + off, c.ws_bytes = ws_bytes - off, c.what = ex.what;
+        return cpg_conv3x3_wino_launch(c);
     }
     if (plan.route == C3_STEM) return cpg_conv3x3_stem_run(N, c_read, m, H, W, x, w, pm, thr, bias, y, ex.stats, stream);
     float *wp = (float *)ws;
@@ -1372,7 +1379,7 @@ int cpg_conv3x3_fwd_eval(const cpg_conv_desc *d, const float *x, const float *w,
 bool cpg_conv3x3_pack_job(const cpg_conv_desc *d, int dgrad, cpg::PackJob *job) {
     const int c_read = dgrad ? d->K : d->C, m = dgrad ? d->C : d->K;
     return plan_fwd(dgrad != 0, d->N, c_read, m, d->H, d->W, C3_PLAIN).route == C3_WINO &&
-           cpg_conv3x3_wino_pack_job(dgrad, d->N, c_read, m, d->H, d->W, d->K, d->C, job);
+           cpg_conv3x3_wino_pack_job(dgrad, d->N, c_read, m, d->H, d->W, job);
 }
 
 int cpg_conv3x3_dgrad(const cpg_conv_desc *d, const float *gy, const float *w, const float *pm, float thr, float *gx, void *ws,

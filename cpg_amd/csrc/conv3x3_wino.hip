@@ -14,7 +14,7 @@
 //               (image, tile row, tile column) order, whatever the map size -- no padding tiles, blocks may straddle rows and
 //               images.  NW = 4 (the default): BK = 32, two blocks per CU; NW = 8: BK = 64, one block per CU (every
 //               transformed input element feeds twice the MFMAs, less staging work per MFMA -- but measured slower, see
-//               wino_nw()).  Wave (tq, ph, kq) owns tiles tq*32..+31, positions ph*8..+7 and
+//               WinoPlan::nw).  Wave (tq, ph, kq) owns tiles tq*32..+31, positions ph*8..+7 and
 //               channels kq*32..+31: 8 accumulators of 32 x 32.  Per chunk of 4 input channels:
 //     G  global -> registers.  A vector-memory instruction occupies the texture addresser for 16 cycles whatever its width
 //        (gathering every tile's 4 x 4 patch with 16 dword loads made the kernel TA-bound), so the patch rows are fetched
@@ -35,6 +35,7 @@
 //   STATS: per-channel sum / sum of squares of the block's outputs for the BatchNorm that follows (as k_c3_fwd<.., STATS>).
 //   dgrad       the same kernel on gy with the filter transposed and spatially flipped (k_wg_pack's dgrad flavour).
 #include <algorithm>
+#include <cstdio>
 #include <type_traits>
 #include "cpg_dispatch.h"
 #include "wino_acc.h"
@@ -58,7 +59,7 @@ struct WgGeom {
     int span;                 // images a block's 64 consecutive tiles can touch
     unsigned nblocks;         // k_wg1 / k_wg3: logical blocks of the launch (the grid may be smaller: blocks loop over them)
     float inv_timg, inv_tw;   // 1 / tiles_img, 1 / tw (wg_divmod)
-    // k_wg3<.., SPLIT> (the tail launch of wino_run): logical blocks split_first .. of the layer, each cut into split_s pieces of split_nch
+    // k_wg3<.., SPLIT> (the tail launch of wg3_run): logical blocks split_first .. of the layer, each cut into split_s pieces of split_nch
     // channel chunks; piece s writes its partial outputs to y + s * split_stride
     unsigned split_first;
     int split_s, split_nch;
@@ -1283,7 +1284,7 @@ struct Bop {                                  // k_wg3's B operands of one chann
 // accumulators, the epilogue and its exchange between the two waves of a unit -- is per unit, as before; every sum is bit for bit
 // what the two-wave block computes.
 // SPLIT (round 5): the TAIL launch of a layer whose units do not fill their last round (SphereNet-20's 256 -> 256 @14 at batch 256: 784
-// four-wave blocks on 256 CUs = 3.06 rounds -- the last 16 blocks ran alone for a whole round).  wino_run() launches the full rounds as
+// four-wave blocks on 256 CUs = 3.06 rounds -- the last 16 blocks ran alone for a whole round).  wg3_run() launches the full rounds as
 // before and the leftover logical blocks here, each cut into split_s pieces along the channel loop (piece s contracts chunks
 // s * split_nch .. and stores its partial outputs -- the output transform is linear -- to its own slice of a workspace); k_wg_tail_reduce
 // adds the slices in a fixed order (+ bias) into y.  No statistics / inference epilogue, even maps.
@@ -1986,12 +1987,13 @@ inline int pad_to(int v, int m) { return (v + m - 1) / m * m; }
 struct WgTail {
     bool on;
     unsigned first_lb, end_lb;    // logical blocks of the tail
-    int64_t main_units, left;
+    int64_t left;
     int S, nch_per, n_first;
     int64_t stride;               // floats per piece: images n_first .. N - 1 of the output
-    size_t bytes;
+    size_t off, bytes;            // the pieces in the workspace: behind the packed filter (pack_bytes of it), 256-byte aligned
+    WgGeom g;                     // the pieces' launch: the layer's geometry with the split filled in, nblocks = the pieces
 };
-static WgTail wino_tail_plan(const WgGeom &g0, int64_t nblocks, bool sh) {
+static WgTail wino_tail_plan(const WgGeom &g0, int64_t nblocks, bool sh, size_t pack_bytes) {
     WgTail t{};
     if (opt_or(OPT_WINO_TAIL, 1) == 0) return t;
     const int64_t units = sh ? nblocks / 2 : nblocks, slots = sh ? kCUs : 2 * kCUs;
@@ -2004,82 +2006,31 @@ static WgTail wino_tail_plan(const WgGeom &g0, int64_t nblocks, bool sh) {
     S = (g0.nch + per - 1) / per;
     if (S < 2) return t;
     t.first_lb = (unsigned)(sh ? 2 * full : full), t.end_lb = (unsigned)nblocks;
-    t.main_units = full, t.left = left, t.S = S, t.nch_per = per;
+    t.left = left, t.S = S, t.nch_per = per;
     const int nkb64 = (g0.nkb + 1) / 2;
     t.n_first = (int)(((int64_t)(t.first_lb / (unsigned)nkb64) * W1_T) / g0.tiles_img);
     t.stride = (int64_t)(g0.N - t.n_first) * g0.M * g0.H * g0.W;
-    t.bytes = (size_t)S * t.stride * sizeof(float);
+    t.off = (pack_bytes + 255) / 256 * 256, t.bytes = (size_t)S * t.stride * sizeof(float);
     t.on = t.bytes <= ((size_t)64 << 20) && t.stride > 0;
+    t.g = g0;
+    t.g.split_first = t.first_lb, t.g.split_s = S, t.g.split_nch = per, t.g.split_stride = t.stride;
+    t.g.nblocks = (unsigned)((sh ? 2 : 1) * left * S);
     return t;
 }
 
-// waves per block for a launch.  The 8-wave / 64-channel block does half the staging work per MFMA, but its eight waves run in
-// lock step behind one barrier and it measured 3-4 % SLOWER than two independent 4-wave blocks per CU on every VGG16 layer
-// (docs/LAB_NOTEBOOK.md section 4.9), so it is only reachable through CPG_WINO_NW=8 (A/B experiments, tests).
-inline int wino_nw(int c_read, int m) {
-    return opt_or(OPT_WINO_NW, 4) == 8 ? 8 : 4;
-}
-
+// the cooperative block kernel (CPG_WINO_KERNEL=block only): NW waves per block, `blocks` of them -- one per (tile run, channel block)
 template <int NW>
-int wino_launch(bool dgrad, const WgGeom &g, int64_t tblocks, const float *x, const float *up, const float *bias, float *y, float *stats,
-                hipStream_t stream) {
-    const int64_t blocks = tblocks * g.nkb;
-    if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "conv3x3 (winograd): grid too large");
+void wino_launch(bool dgrad, const WgGeom &g, unsigned blocks, const float *x, const float *up, const float *bias, float *y, float *stats,
+                 hipStream_t stream) {
     if (dgrad)
-        hipLaunchKernelGGL((k_wg_fwd<NW, true, false>), dim3((unsigned)blocks), dim3(64 * NW), 0, stream, g, x, up, bias, y, nullptr);
+        hipLaunchKernelGGL((k_wg_fwd<NW, true, false>), dim3(blocks), dim3(64 * NW), 0, stream, g, x, up, bias, y, nullptr);
     else if (stats != nullptr)
-        hipLaunchKernelGGL((k_wg_fwd<NW, false, true>), dim3((unsigned)blocks), dim3(64 * NW), 0, stream, g, x, up, bias, y, stats);
+        hipLaunchKernelGGL((k_wg_fwd<NW, false, true>), dim3(blocks), dim3(64 * NW), 0, stream, g, x, up, bias, y, stats);
     else
-        hipLaunchKernelGGL((k_wg_fwd<NW, false, false>), dim3((unsigned)blocks), dim3(64 * NW), 0, stream, g, x, up, bias, y, nullptr);
-    return CPG_OK;
+        hipLaunchKernelGGL((k_wg_fwd<NW, false, false>), dim3(blocks), dim3(64 * NW), 0, stream, g, x, up, bias, y, nullptr);
 }
 
-}  // namespace
-
-// ---- host side ---------------------------------------------------------------------------------------------------
-// eligibility of one launch (c_read channels contracted, m produced): even maps, the staging offsets of
-// the images a block can touch fit 31 bits
-// odd maps (7 x 7: ResNet-50 layer4, SphereNet conv4_x): only the two-wave kernel k_wg3 has the edge handling (its ODD instances), and it
-// only pays with a long channel loop -- >= 128 channels read, >= 64 produced, no forced kernel choice
-static inline bool wino_odd_ok(int c_read, int m, int H, int W) {
-    return ((H | W) & 1) && H >= 3 && W >= 3 && c_read >= 128 && m >= 64 && cpg::opt(cpg::OPT_WINO_KERNEL) == cpg::OPT_UNSET && !cpg::opt_on(cpg::OPT_NO_WINO_ODD);
-}
-extern "C" int cpg_conv3x3_wino_ok(int N, int c_read, int m, int H, int W) {
-    if (cpg::opt_on(cpg::OPT_NO_WINO)) return 0;
-    if (c_read < 16 || m < 16 || N < 1) return 0;           // (any channel count: wg_chunk_base)
-    if (((H | W) & 1) && !wino_odd_ok(c_read, m, H, W)) return 0;
-    const int tiles_img = ((H + 1) / 2) * ((W + 1) / 2);
-    const int span = (WG_T + tiles_img - 1) / tiles_img + 1;
-    if ((int64_t)N * tiles_img + 64 >= (1ll << 31)) return 0;               // 32-bit tile indices in the kernels
-    return (int64_t)span * std::max(c_read, m) * H * W * 4 < (1ll << 31);   // (a unit's images behind one buffer descriptor: read and written)
-}
-
-extern "C" size_t cpg_conv3x3_wino_pack_bytes(int c_read, int m) {      // (the 64-channel blocking pads m further: covers both)
-    return (size_t)pad_to(m, 64) * pad_to(c_read, WG_CK) * 16 * sizeof(float);
-}
-
-static inline int wino_variant(int c_read, int m, bool stats = true);
-static void wino_geom(WgGeom &g, int N, int c_read, int m, int H, int W) {
-    g = WgGeom{};
-    g.N = N, g.C = c_read, g.H = H, g.W = W, g.M = m;
-    g.th = (H + 1) / 2, g.tw = (W + 1) / 2, g.tiles_img = g.th * g.tw;
-    g.inv_timg = 1.0f / (float)g.tiles_img, g.inv_tw = 1.0f / (float)g.tw;
-    g.tiles_total = (int64_t)N * g.tiles_img;
-    g.nkb = pad_to(m, 32) / 32, g.nch = pad_to(c_read, WG_CK) / WG_CK;
-    g.span = (W1_T + g.tiles_img - 1) / g.tiles_img + 1;
-}
-static inline bool wino_sh(const WgGeom &g) { return ((g.nkb + 1) / 2) % 2 == 0 && cpg::opt_or(cpg::OPT_WG3_SHARE, 1) != 0; }
-// workspace behind the packed filter for the partial outputs of a tail launch (0: this launch has none) -- part of cpg_conv2d_workspace_bytes
-extern "C" size_t cpg_conv3x3_wino_tail_bytes(int N, int c_read, int m, int H, int W) {
-    if (((H | W) & 1) || !cpg_conv3x3_wino_ok(N, c_read, m, H, W) || wino_variant(c_read, m, false) != 3 /* WV_PAIR64 */) return 0;
-    WgGeom g;
-    wino_geom(g, N, c_read, m, H, W);
-    const int64_t blocks = ((g.tiles_total + W1_T - 1) / W1_T) * ((g.nkb + 1) / 2);
-    if (blocks > 0x7FFFFFFFll) return 0;
-    const WgTail t = wino_tail_plan(g, blocks, wino_sh(g));
-    return t.on ? t.bytes + 256 : 0;
-}
-
+// ---- host side: the plan ---------------------------------------------------------------------------------------------
 // Which Winograd forward / input-gradient kernel a launch uses.  Default: k_wg3 (two waves per unit, 64 output channels each) when the
 // layer reads and produces at least 64 channels, else k_wg1 (one wave per unit).  (Until round 4 the launches WITH the BatchNorm-statistics
 // epilogue switched at 128 channels read: k_wg3's statistics epilogue was the heavier one.  After round 3's work on it -- sums per
@@ -2087,10 +2038,9 @@ extern "C" size_t cpg_conv3x3_wino_tail_bytes(int N, int c_read, int m, int H, i
 // CPG_WINO_KERNEL=-,64) reads 64 -> 64 @224 4.716 -> 4.546 ms and 64 -> 128 @112 2.277 -> 2.217 ms for k_wg3.)
 // CPG_WINO_KERNEL = wave | pair | 64 | block forces k_wg1 / k_wg2 / k_wg3 / the cooperative block kernel (A/B experiments, tests).
 enum { WV_BLOCK = 0, WV_WAVE = 1, WV_PAIR = 2, WV_PAIR64 = 3 };
-static inline int wino_variant(int c_read, int m, bool stats) {
-    if (const int forced = cpg::opt(cpg::OPT_WINO_KERNEL); forced != cpg::OPT_UNSET)      // (block | wave | pair | 64 -> WV_*)
+int wino_variant(int c_read, int m) {
+    if (const int forced = opt(OPT_WINO_KERNEL); forced != OPT_UNSET)      // (block | wave | pair | 64 -> WV_*)
         return forced >= WV_BLOCK && forced <= WV_PAIR64 ? forced : WV_WAVE;
-    (void)stats;
     if (c_read < 64 || m < 64) return WV_WAVE;
     // Channel counts that are no multiple of 64 (the grown networks: 78 / 156 / 313 / 627 outputs): a unit of k_wg3 produces 64 channels, one
     // of k_wg1 32, and the padding of the last block is MFMA time.  At equal padding k_wg3 is the faster kernel by 5-8 % (shared transform),
@@ -2100,49 +2050,144 @@ static inline int wino_variant(int c_read, int m, bool stats) {
     return p64 * 10 > p32 * 11 ? WV_WAVE : WV_PAIR64;
 }
 
-// The packed operand of a forward / input-gradient launch of the one- and two-wave kernels: the per-lane transformed filter U in
-// k_wg1_pack's layout, cpg_conv3x3_wino_pack_bytes(c_read, m) bytes.  w is the layer's [K][C][3][3] weight.
-static cpg::PackJob wino_pack_job(int dgrad, int c_read, int m, int K, int C) {
-    const int nch = pad_to(c_read, WG_CK) / WG_CK;
-    return cpg::PackJob{2, K, C, m, c_read, nch, dgrad ? 1 : 0, (long long)((m + 31) / 32) * nch * 32 * WG_CK, cpg_conv3x3_wino_pack_bytes(c_read, m)};
+// eligibility of one launch (c_read channels contracted, m produced): the staging offsets of the images a block can touch fit 31 bits.
+// Odd maps (7 x 7: ResNet-50 layer4, SphereNet conv4_x): only the two-wave kernel k_wg3 has the edge handling (its ODD instances), and it
+// only pays with a long channel loop -- >= 128 channels read, >= 64 produced, no forced kernel choice
+bool wino_eligible(int N, int c_read, int m, int H, int W) {
+    if (opt_on(OPT_NO_WINO)) return false;
+    if (c_read < 16 || m < 16 || N < 1) return false;           // (any channel count: wg_chunk_base)
+    if (((H | W) & 1) && !(H >= 3 && W >= 3 && c_read >= 128 && m >= 64 && opt(OPT_WINO_KERNEL) == OPT_UNSET && !opt_on(OPT_NO_WINO_ODD)))
+        return false;
+    const int tiles_img = ((H + 1) / 2) * ((W + 1) / 2);
+    const int span = (WG_T + tiles_img - 1) / tiles_img + 1;    // (the widest unit's, whichever kernel runs)
+    if ((int64_t)N * tiles_img + 64 >= (1ll << 31)) return false;               // 32-bit tile indices in the kernels
+    return (int64_t)span * std::max(c_read, m) * H * W * 4 < (1ll << 31);   // (a unit's images behind one buffer descriptor: read and written)
 }
-// ... of the launch cpg_conv3x3_wino_run would make; false: that launch streams no operand a caller could hand in -- a shape
-// cpg_conv3x3_wino_ok refuses, or the cooperative block kernel (CPG_WINO_KERNEL=block), which packs for itself
-bool cpg_conv3x3_wino_pack_job(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, cpg::PackJob *job) {
-    if (!cpg_conv3x3_wino_ok(N, c_read, m, H, W)) return false;
-    if (!((H | W) & 1) && wino_variant(c_read, m) == WV_BLOCK) return false;
-    *job = wino_pack_job(dgrad, c_read, m, K, C);
-    return true;
+
+// What differs between launches of one shape: the direction (the pack job), an inference launch (neither shared transforms nor a tail),
+// and whether the tail may be planned at all (false: the single launch of a caller whose workspace ends behind the packed filter).
+struct WinoWant {
+    bool dgrad, eval, tail;
+};
+constexpr WinoWant kWinoTrain{false, false, true};      // what the shape queries ask: direction-free answers of a training launch
+
+// Everything a launch or a query needs, from the shape and the option table alone: no pointer, no workspace, no thread state.
+struct WinoPlan {
+    bool ok;                  // the shape is eligible; the rest describes the launch an eligible shape gets
+    bool odd;                 // an odd map: k_wg3's ODD instances
+    int variant, nw;          // WV_*; waves per block of the block kernel (4, or 8: 64 channels per block -- it does half the staging work per
+                              // MFMA, but its eight waves run in lock step behind one barrier and it measured 3-4 % SLOWER than two independent
+                              // 4-wave blocks per CU on every VGG16 layer (docs/LAB_NOTEBOOK.md section 4.9): CPG_WINO_NW=8 only)
+    WgGeom g;                 // nblocks: the logical blocks of the main launch (the whole launch's, less the tail's)
+    int64_t blocks;           // logical blocks of the whole launch
+    bool grid_ok;             // ... fit a grid; false: "grid too large", nothing below is filled in
+    unsigned grid, threads;   // the main launch, after the persistent clamp
+    bool sh;                  // k_wg3<.., SH>: two units per four-wave block share the input transform
+    WgTail tail;              // k_wg3<.., SPLIT> + k_wg_tail_reduce behind the main launch (on: planned)
+    size_t pack_bytes;        // the transformed filter at the head of the workspace
+    PackJob job;              // ... as k_wg1_pack writes it (the block kernel packs another layout for itself)
+    int tiles;                // BatchNorm-statistics tiles per channel of a forward launch
+    // what the launch can carry: the inference epilogues, the pooled one, the window maxima, an addend, a caller-packed operand
+    bool eval, eval_pool, pool_max, addend, takes_packed;
+};
+
+// CPG_WINO_PERSIST=0: one block per logical block instead of the persistent grid (A/B experiments).
+// How many resident grids' worth of persistent blocks a launch gets: 8.  One grid (every block resident from the start, ~200 units
+// per wave on the big layers) and 4, 8 or 16 grids measured the same within 0.5 % on every VGG16 layer -- a block that runs a
+// dozen units has amortised its dispatch --, but with one exactly-resident grid a launch that finds some CUs taken (RCCL's
+// kernels on the communication stream) would run its last blocks alone afterwards; with 8 the dispatcher balances whatever
+// share of the chip is free to within 1/8 of a round.  CPG_WINO_GRIDS overrides (A/B experiments).
+unsigned wino_persistent_grid(int64_t units, int resident) {
+    if (opt_or(OPT_WINO_PERSIST, 1) == 0) return (unsigned)units;
+    return (unsigned)std::min<int64_t>(units, (int64_t)std::max(1, opt_or(OPT_WINO_GRIDS, 8)) * resident);
 }
+
+WinoPlan wino_plan(WinoWant want, int N, int c_read, int m, int H, int W) {
+    WinoPlan p{};
+    p.ok = wino_eligible(N, c_read, m, H, W);
+    p.odd = ((H | W) & 1) != 0;
+    p.variant = p.odd ? WV_PAIR64 : wino_variant(c_read, m);
+    p.nw = opt_or(OPT_WINO_NW, 4) == 8 ? 8 : 4;
+    const bool block = p.variant == WV_BLOCK, pair64 = p.variant == WV_PAIR64;
+    p.eval = p.ok && !block, p.eval_pool = p.eval && !p.odd, p.takes_packed = p.eval;
+    p.addend = p.ok && pair64;           // (k_wg3<.., ADD>: >= 64 channels on both sides, or an odd map)
+    p.pool_max = p.ok && pair64 && !p.odd && m % 64 == 0 && !opt_on(OPT_NO_POOL_MAX);      // (k_wg3<.., PMAX>: whole 64-channel blocks)
+    // The geometry.  The block kernel differs from the one- and two-wave kernels in two numbers: its unit is a run of WG_T = 64 consecutive
+    // tiles, theirs W1_T = 32 (`span`, the images a run can touch, follows), and its channel blocks are 8 * nw wide, theirs 32 (`nkb`).
+    // (It runs even maps only, so th = (H + 1) / 2 is its H / 2.)
+    const int run = block ? WG_T : W1_T, bk = block ? 8 * p.nw : 32;
+    WgGeom &g = p.g;
+    g.N = N, g.C = c_read, g.H = H, g.W = W, g.M = m;
+    g.th = (H + 1) / 2, g.tw = (W + 1) / 2, g.tiles_img = g.th * g.tw;
+    g.inv_timg = 1.0f / (float)g.tiles_img, g.inv_tw = 1.0f / (float)g.tw;
+    g.tiles_total = (int64_t)N * g.tiles_img;
+    g.nkb = pad_to(m, bk) / bk, g.nch = pad_to(c_read, WG_CK) / WG_CK;
+    g.span = (run + g.tiles_img - 1) / g.tiles_img + 1;
+    const int64_t runs = (g.tiles_total + run - 1) / run;
+    p.tiles = (int)(block || p.variant == WV_WAVE ? runs : 2 * runs);       // (every wave of a pair is its own statistics tile)
+    // the packed operand: the per-lane transformed filter U in k_wg1_pack's layout (the 64-channel blocking pads m further: covers both);
+    // the layer's weight is [K][C][3][3], whichever side the launch reads
+    p.pack_bytes = cpg_conv3x3_wino_pack_bytes(c_read, m);
+    p.job = PackJob{2, want.dgrad ? c_read : m, want.dgrad ? m : c_read, m, c_read, g.nch, want.dgrad ? 1 : 0,
+                    (long long)((m + 31) / 32) * g.nch * 32 * WG_CK, p.pack_bytes};
+    // logical blocks: one per (run, channel block) -- k_wg1's four waves take four runs, k_wg3's unit two channel blocks
+    p.blocks = pair64 ? runs * ((g.nkb + 1) / 2) : p.variant == WV_WAVE ? (runs + 3) / 4 * g.nkb : runs * g.nkb;
+    p.grid_ok = p.blocks <= 0x7FFFFFFFll;
+    if (!p.grid_ok) return p;
+    g.nblocks = (unsigned)p.blocks;
+    if (pair64 && !p.odd && !want.eval) {       // (inference launches: no SH instance with an epilogue, and no tail)
+        p.sh = ((g.nkb + 1) / 2) % 2 == 0 && opt_or(OPT_WG3_SHARE, 1) != 0;       // training launches whose 64-channel blocks pair up
+        if (want.tail) p.tail = wino_tail_plan(g, p.blocks, p.sh, p.pack_bytes);
+        if (p.tail.on) g.nblocks = p.tail.first_lb;      // the full rounds run as before on logical blocks 0 .. first_lb - 1
+    }
+    // k_wg1 and k_wg3 are persistent: one four-wave block per CU is resident, or two two-wave blocks
+    if (pair64)
+        p.threads = p.sh ? 256 : 128, p.grid = wino_persistent_grid(p.sh ? g.nblocks / 2 : g.nblocks, p.sh ? kCUs : 2 * kCUs);
+    else if (p.variant == WV_WAVE)
+        p.threads = 256, p.grid = wino_persistent_grid(g.nblocks, kCUs);
+    else
+        p.threads = block ? 64 * p.nw : 128, p.grid = g.nblocks;
+    return p;
+}
+
+}  // namespace
+
+// ---- the queries: each reads the plan ------------------------------------------------------------------------------------
+extern "C" int cpg_conv3x3_wino_ok(int N, int c_read, int m, int H, int W) { return wino_plan(kWinoTrain, N, c_read, m, H, W).ok ? 1 : 0; }
+
+extern "C" size_t cpg_conv3x3_wino_pack_bytes(int c_read, int m) {
+    return (size_t)pad_to(m, 64) * pad_to(c_read, WG_CK) * 16 * sizeof(float);
+}
+
+// workspace behind the packed filter for the partial outputs of a tail launch (0: this launch has none) -- part of cpg_conv2d_workspace_bytes
+size_t cpg_conv3x3_wino_tail_bytes(int N, int c_read, int m, int H, int W) {
+    const WinoPlan p = wino_plan(kWinoTrain, N, c_read, m, H, W);
+    return p.ok && p.tail.on ? p.tail.bytes + 256 : 0;
+}
+
+// number of BatchNorm-statistics tiles per channel of a forward launch (stats[m][tiles][2])
+extern "C" int cpg_conv3x3_wino_tiles(int N, int c_read, int m, int H, int W) { return wino_plan(kWinoTrain, N, c_read, m, H, W).tiles; }
+
+// the packed operand of the launch cpg_conv3x3_wino_launch would make; false: that launch streams no operand a caller could hand in -- a
+// shape that is not eligible, or the cooperative block kernel (CPG_WINO_KERNEL=block), which packs for itself
+bool cpg_conv3x3_wino_pack_job(int dgrad, int N, int c_read, int m, int H, int W, cpg::PackJob *job) {
+    const WinoPlan p = wino_plan(WinoWant{dgrad != 0, false, true}, N, c_read, m, H, W);
+    if (p.takes_packed) *job = p.job;
+    return p.takes_packed;
+}
+
+int cpg_conv3x3_wino_pool_max_ok(int N, int c_read, int m, int H, int W) { return wino_plan(kWinoTrain, N, c_read, m, H, W).pool_max ? 1 : 0; }
+int cpg_conv3x3_wino_eval_ok(int N, int c_read, int m, int H, int W) { return wino_plan(kWinoTrain, N, c_read, m, H, W).eval ? 1 : 0; }
+int cpg_conv3x3_wino_eval_pool_ok(int N, int c_read, int m, int H, int W) { return wino_plan(kWinoTrain, N, c_read, m, H, W).eval_pool ? 1 : 0; }
+int cpg_conv3x3_wino_dgrad_add_ok(int N, int c_read, int m, int H, int W) { return wino_plan(kWinoTrain, N, c_read, m, H, W).addend ? 1 : 0; }
 
 #ifdef WG_TIMING
 extern "C" int cpg_debug_wg_timing(unsigned long long *dst, int n) {
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(wg_dbg), (size_t)n * 8 * sizeof(unsigned long long));
 }
 #endif
-// CPG_WINO_PERSIST=0: one block per logical block instead of the persistent grid (A/B experiments)
-static inline bool wino_persist() {
-    return cpg::opt_or(cpg::OPT_WINO_PERSIST, 1) != 0;
-}
 
-// How many resident grids' worth of persistent blocks a launch gets: 8.  One grid (every block resident from the start, ~200 units
-// per wave on the big layers) and 4, 8 or 16 grids measured the same within 0.5 % on every VGG16 layer -- a block that runs a
-// dozen units has amortised its dispatch --, but with one exactly-resident grid a launch that finds some CUs taken (RCCL's
-// kernels on the communication stream) would run its last blocks alone afterwards; with 8 the dispatcher balances whatever
-// share of the chip is free to within 1/8 of a round.  CPG_WINO_GRIDS overrides (A/B experiments).
-static inline int wino_grids() {
-    return std::max(1, cpg::opt_or(cpg::OPT_WINO_GRIDS, 8));
-}
-
-// number of BatchNorm-statistics tiles per channel of a forward launch (stats[m][tiles][2])
-extern "C" int cpg_conv3x3_wino_tiles(int N, int c_read, int m, int H, int W) {
-    const int64_t tiles = (int64_t)N * ((H + 1) / 2) * ((W + 1) / 2);
-    const int v = ((H | W) & 1) ? WV_PAIR64 : wino_variant(c_read, m);
-    if (v == WV_PAIR || v == WV_PAIR64) return (int)(2 * ((tiles + W1_T - 1) / W1_T));     // every wave of a pair is its own tile
-    const int per = v == WV_WAVE ? W1_T : WG_T;
-    return (int)((tiles + per - 1) / per);
-}
-
+// ---- the launch ------------------------------------------------------------------------------------------------------
 // What a launch of the one- and two-wave kernels computes.  Each kernel family has ONE function that maps a mode to the template
 // instance; an instance that does not exist cannot be named, and a mode a family lacks is a status, not a launch.
 enum WgMode {
@@ -2157,11 +2202,33 @@ enum WgMode {
 };
 struct WgLaunch {     // the arguments every instance takes
     const WgGeom &g;
-    const float *x, *up, *bias;      // bias: the addend under WG_DGRAD_ADD, the window maxima E under WG_FWD_STATS_PMAX
+    const float *x, *up, *bias;      // bias: the kernels' one slot -- wg_slot
     float *y, *stats;                // stats: passed under WG_FWD_STATS only
     const WgBnEval &bne;             // read under WG_FWD_BNE / WG_FWD_PRE only
     hipStream_t stream;
 };
+// The mode of a call, and what rides in the kernels' one slot under it: the addend, the window maxima E a caller attached
+// (cpg_conv2d_fwd_attach_pool_max), else the bias.  ep->pool has no slot in the parameter block: the pooled epilogue is other code, not a
+// run-time branch -- it picks the POOL instances, whose `y` is the pooled tensor.
+static WgMode wg_mode(const cpg::WinoCall &c) {
+    if (c.ep != nullptr) return c.ep->kind == cpg::EvalEpilogue::PRELU ? WG_FWD_PRE : c.ep->pool ? WG_FWD_BNE_POOL : WG_FWD_BNE;
+    if (c.dgrad) return c.addend != nullptr ? WG_DGRAD_ADD : WG_DGRAD;
+    return c.stats == nullptr ? WG_FWD : c.pool_max != nullptr ? WG_FWD_STATS_PMAX : WG_FWD_STATS;
+}
+static const float *wg_slot(WgMode mode, const cpg::WinoCall &c) {
+    return mode == WG_DGRAD_ADD ? c.addend : mode == WG_FWD_STATS_PMAX ? c.pool_max : c.bias;
+}
+// The kernels' parameter block from the descriptor (null: no inference epilogue) -- the one place that knows which name of a pair each kind fills.
+static WgBnEval wg_epilogue(const cpg::EvalEpilogue *ep, int *live, int m) {
+    WgBnEval bn{};
+    if (ep == nullptr) return bn;
+    if (ep->kind == cpg::EvalEpilogue::PRELU)      // (the slots behind slope(), residual() and per_channel())
+        bn.gamma = ep->slope, bn.beta = ep->residual, bn.relu = ep->per_channel ? 1 : 0;
+    else
+        bn.gamma = ep->gamma, bn.beta = ep->beta, bn.mean = ep->mean, bn.var = ep->var, bn.eps = ep->eps, bn.relu = ep->relu;
+    bn.live = live, bn.Mp = pad_to(m, 128);
+    return bn;
+}
 #define WG_GO(kernel, blocks, threads, a, stats_arg) \
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, (a).stream, (a).g, (a).x, (a).up, (a).bias, (a).y, stats_arg, (a).bne)
 
@@ -2194,212 +2261,39 @@ static int wg3_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
     }
     return fail(CPG_E_UNSUPPORTED, "conv3x3 (winograd): k_wg3 has no instance for mode %d (odd %d, shared %d, split %d)", (int)mode, ODD, SH, SPLIT);
 }
+
+// (The four launchers below stand in this order, and name their instances in this order, on purpose: the compiler emits kernels in the order
+// of their first reference from host code, and host-side edits keep this file's device code byte-identical -- tools/build_digest.py.)
+
+// The two-wave kernel's launch as planned: the main launch, then -- where the plan has a tail -- the leftover units of the last round as
+// pieces of the channel loop (k_wg3<.., SPLIT>, raw partial outputs into the workspace behind the packed filter) and k_wg_tail_reduce,
+// which adds the pieces (+ bias, + addend; with the BatchNorm statistics and the window maxima too) into y.
+static int wg3_run(const WinoPlan &p, WgMode mode, const WgLaunch &whole, const cpg::WinoCall &c) {
+    if (p.odd) return wg3_launch<true, false, false>(mode, p.grid, whole);
+    const WgTail &t = p.tail;
+    // piece 0's slice, addressed like y: its first image is n_first
+    float *const part0 = reinterpret_cast<float *>(reinterpret_cast<uintptr_t>(c.ws) + t.off) - (int64_t)t.n_first * p.g.M * p.g.H * p.g.W;
+    auto reduce = [&]() {
+        const dim3 rg(stream_grid((int64_t)(t.end_lb - t.first_lb) * 64 * W1_T, 256));
+        if (mode == WG_FWD_STATS_PMAX)
+            hipLaunchKernelGGL((k_wg_tail_reduce<true, true>), rg, dim3(256), 0, c.stream, t.g, part0, c.bias, c.y, t.first_lb, t.end_lb, c.stats, (const float *)c.pool_max);
+        else if (c.stats != nullptr)
+            hipLaunchKernelGGL(k_wg_tail_reduce<true>, rg, dim3(256), 0, c.stream, t.g, part0, c.bias, c.y, t.first_lb, t.end_lb, c.stats, (const float *)nullptr);
+        else
+            hipLaunchKernelGGL(k_wg_tail_reduce<false>, rg, dim3(256), 0, c.stream, t.g, part0, c.bias, c.y, t.first_lb, t.end_lb, (float *)nullptr, c.addend);
+    };
+    auto go = [&](bool split, WgMode md, unsigned blocks, const WgLaunch &a) {
+        if (p.sh) return !split ? wg3_launch<false, true, false>(md, blocks, a) : wg3_launch<false, true, true>(md, blocks, a);
+        return !split ? wg3_launch<false, false, false>(md, blocks, a) : wg3_launch<false, false, true>(md, blocks, a);
+    };
+    int rc = go(false, mode, p.grid, whole);
+    if (rc != CPG_OK || !t.on) return rc;
+    const WgBnEval none{};
+    const WgLaunch pieces{t.g, c.x, whole.up, nullptr, part0, nullptr, none, c.stream};      // (forward or input gradient, nothing else)
+    if ((rc = go(true, c.dgrad ? WG_DGRAD : WG_FWD, (unsigned)(t.left * t.S), pieces)) == CPG_OK) reduce();
+    return rc;
+}
 // k_wg2<DGRAD, STATS, BNE, PRE, POOL> and k_wg1<DGRAD, STATS, BNE, PRE, POOL>: 6 instances each, no addend
-static int wg2_launch(WgMode mode, unsigned blocks, const WgLaunch &a);
-static int wg1_launch(WgMode mode, unsigned blocks, const WgLaunch &a);
-// the cooperative block kernel k_wg_fwd (CPG_WINO_KERNEL=block only): packs for itself, no inference epilogue
-static int wino_run_block(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
-                          float thr, const float *bias, float *y, float *stats, void *ws, hipStream_t stream, const char *what);
-// (These three are defined below wino_run, in the order wino_run reaches them: the compiler emits kernels in the order of their first
-// reference, and host-side edits keep this file's device code byte-identical -- tools/build_digest.py.)
-
-// y[N][m][H][W] = conv3x3(x[N][c_read][H][W], W .* bin(pm)) (+ bias); dgrad: x = gy, the filter transposed and flipped.
-// w is the layer's [K][C][3][3] weight.  stats (forward only, may be null): [m][tiles][2] partial sums for the BatchNorm.
-// ep (forward only, may be null): the inference epilogue, with live (may be null), the liveness words of its dead-channel skip.
-// packed: for the one- and two-wave launches without ep.  pool_max (may be null; cpg_conv2d_fwd_bnstats has checked it): receives the window maxima of y.
-static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
-                    float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream,
-                    const cpg::EvalEpilogue *ep, const cpg::PackedOperand &packed = cpg::PackedOperand(), float *pool_max = nullptr,
-                    const float *addend = nullptr, int *live = nullptr);
-
-// The kernels' parameter block from the descriptor (null: no inference epilogue) -- the one place that knows which name of a pair each kind fills.
-static WgBnEval wg_epilogue(const cpg::EvalEpilogue *ep, int *live, int m) {
-    WgBnEval bn{};
-    if (ep == nullptr) return bn;
-    if (ep->kind == cpg::EvalEpilogue::PRELU)      // (the slots behind slope(), residual() and per_channel())
-        bn.gamma = ep->slope, bn.beta = ep->residual, bn.relu = ep->per_channel ? 1 : 0;
-    else
-        bn.gamma = ep->gamma, bn.beta = ep->beta, bn.mean = ep->mean, bn.var = ep->var, bn.eps = ep->eps, bn.relu = ep->relu;
-    bn.live = live, bn.Mp = pad_to(m, 128);
-    return bn;
-}
-// ... and the mode that goes with it.  ep->pool has no slot in the block: the pooled epilogue is other code, not a run-time branch -- it picks
-// the POOL instances, whose `y` is the pooled tensor (cpg_conv3x3_wino_run_eval has refused what they do not take)
-static WgMode wg_eval_mode(const cpg::EvalEpilogue &ep) {
-    if (ep.kind == cpg::EvalEpilogue::PRELU) return WG_FWD_PRE;
-    return ep.pool ? WG_FWD_BNE_POOL : WG_FWD_BNE;
-}
-
-extern "C" int cpg_conv3x3_wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x,
-                                    const float *w, const float *pm, float thr, const float *bias, float *y, float *stats,
-                                    void *ws, size_t ws_bytes, hipStream_t stream) {
-    return wino_run(dgrad, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, stats, ws, ws_bytes, stream, nullptr);
-}
-int cpg_conv3x3_wino_run_side(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
-                              float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream,
-                              const cpg::PackedOperand &packed, float *pool_max) {
-    return wino_run(dgrad, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, stats, ws, ws_bytes, stream, nullptr, packed, pool_max);
-}
-
-// input gradient + addend (gx = dgrad(gy) + addend): the two-wave kernel's launches (>= 64 channels on both sides, or an odd map)
-extern "C" int cpg_conv3x3_wino_dgrad_add_ok(int N, int c_read, int m, int H, int W) {
-    if (!cpg_conv3x3_wino_ok(N, c_read, m, H, W)) return 0;
-    return (((H | W) & 1) || wino_variant(c_read, m, false) == WV_PAIR64) ? 1 : 0;
-}
-int cpg_conv3x3_wino_dgrad_add(int N, int c_read, int m, int H, int W, int K, int C, const float *gy, const float *w, const float *pm, float thr,
-                               const float *addend, float *gx, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed) {
-    if (!cpg_conv3x3_wino_dgrad_add_ok(N, c_read, m, H, W) || addend == nullptr)
-        return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_dgrad_add(winograd): shape not supported");
-    return wino_run(1, N, c_read, m, H, W, K, C, gy, w, pm, thr, nullptr, gx, nullptr, ws, ws_bytes, stream, nullptr, packed, nullptr, addend);
-}
-
-// 1: a forward launch with statistics of this shape can also write the 2x2 window maxima of its output (k_wg3<.., PMAX>): the two-wave
-// kernel on an even map, whole 64-channel blocks, CPG_NO_POOL_MAX unset
-extern "C" int cpg_conv3x3_wino_pool_max_ok(int N, int c_read, int m, int H, int W) {
-    if (cpg::opt_on(cpg::OPT_NO_POOL_MAX) || ((H | W) & 1) || m % 64 != 0) return 0;
-    return cpg_conv3x3_wino_ok(N, c_read, m, H, W) && wino_variant(c_read, m, true) == WV_PAIR64 ? 1 : 0;
-}
-
-// 1: the inference epilogue is available on the Winograd kernel (the one-wave kernel only)
-extern "C" int cpg_conv3x3_wino_eval_ok(int N, int c_read, int m, int H, int W) {
-    return wino_variant(c_read, m) != WV_BLOCK && cpg_conv3x3_wino_ok(N, c_read, m, H, W);
-}
-
-// 1: ... and so is the pooled one (ep.pool: the POOL instances of k_wg1 / k_wg2 / k_wg3 -- every launch of an even map; the ODD instances have none)
-extern "C" int cpg_conv3x3_wino_eval_pool_ok(int N, int c_read, int m, int H, int W) {
-    return !((H | W) & 1) && cpg_conv3x3_wino_eval_ok(N, c_read, m, H, W);
-}
-
-// forward with ep in the epilogue (eval-mode BatchNorm (+ ReLU) (+ MaxPool2d(2, 2): y is then the pooled tensor), or bias, PReLU (+ residual));
-// live (may be null): live_words ints, zeroed here, layout of k_c3_pack
-int cpg_conv3x3_wino_run_eval(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                              const cpg::EvalEpilogue &ep, int *live, size_t live_words, float *y, void *ws, size_t ws_bytes, hipStream_t stream,
-                              const char *what) {
-    if (ep.kind == cpg::EvalEpilogue::PRELU && ep.slope == nullptr) return fail(CPG_E_INVALID, "%s(winograd): null slope", what);
-    if (ep.kind == cpg::EvalEpilogue::BN_EVAL && ep.residual != nullptr)
-        return fail(CPG_E_UNSUPPORTED, "%s(winograd): no residual behind the BatchNorm", what);
-    if (ep.pool && (ep.kind != cpg::EvalEpilogue::BN_EVAL || !cpg_conv3x3_wino_eval_pool_ok(N, C, K, H, W)))
-        return fail(CPG_E_UNSUPPORTED, "%s(winograd): the pooled epilogue is the BatchNorm epilogue's, on the one- and two-wave kernels of an even map", what);
-    if (live != nullptr) {
-        hipError_t e = hipMemsetAsync(live, 0, live_words * sizeof(int), stream);
-        if (e != hipSuccess) return hip_status(e, what);
-    }
-    return wino_run(0, N, C, K, H, W, K, C, x, w, pm, thr, bias, y, nullptr, ws, ws_bytes, stream, &ep, cpg::PackedOperand(), nullptr, nullptr, live);
-}
-
-static int wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
-                    float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream,
-                    const cpg::EvalEpilogue *ep, const cpg::PackedOperand &packed, float *pool_max, const float *addend, int *live) {
-    const char *what = dgrad ? "cpg_conv2d_dgrad(winograd)" : "cpg_conv2d_fwd(winograd)";
-    // addend (input-gradient launches of the two-wave kernel only: cpg_conv3x3_wino_dgrad_add_ok): added to the result in the epilogue
-    // (k_wg3<.., ADD>; the tail pieces' share in k_wg_tail_reduce)
-    if (addend != nullptr && (!dgrad || bias != nullptr || ep != nullptr || stats != nullptr))
-        return fail(CPG_E_INVALID, "%s: an addend rides in plain input-gradient launches only", what);
-    const size_t need = cpg_conv3x3_wino_pack_bytes(c_read, m);
-    if (ws == nullptr || ws_bytes < need) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, ws_bytes, need);
-    CPG_REQUIRE((((uintptr_t)ws) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
-    const bool odd = ((H | W) & 1) != 0;
-    const int variant = odd ? WV_PAIR64 : wino_variant(c_read, m, stats != nullptr);
-    if (variant != WV_BLOCK) {
-        WgGeom g;
-        wino_geom(g, N, c_read, m, H, W);
-        float *up = (float *)ws;
-        const WgBnEval none{}, bne = wg_epilogue(ep, live, m);
-        // (the inference epilogue's pack also writes the liveness flags: never taken from a caller's operand)
-        const cpg::PackedOperand pre = ep == nullptr ? packed : cpg::PackedOperand();
-        if (const int rc = cpg::packed_fits(pre, need, what)) return rc;
-        if (pre.data != nullptr) {
-            up = const_cast<float *>(pre.data);
-        } else {
-            const cpg::PackJob job = wino_pack_job(dgrad, c_read, m, K, C);
-            hipLaunchKernelGGL(k_wg1_pack, dim3(stream_grid(job.total, 256)), dim3(256), 0, stream, w, pm, thr, up, K, C, m, c_read, job.c,
-                               job.d, bne.live, bne.Mp);
-        }
-        const int64_t runs = (g.tiles_total + W1_T - 1) / W1_T;
-        const bool persist = wino_persist();
-        WgMode mode = ep != nullptr ? wg_eval_mode(*ep) : dgrad ? (addend != nullptr ? WG_DGRAD_ADD : WG_DGRAD) : stats != nullptr ? WG_FWD_STATS : WG_FWD;
-        // the window maxima a caller attached (cpg_conv2d_fwd_attach_pool_max): E rides in the bias slot of the PMAX instances
-        float *const pool_e = mode == WG_FWD_STATS ? pool_max : nullptr;
-        if (pool_e != nullptr) mode = WG_FWD_STATS_PMAX;
-        const WgLaunch whole{g, x, up, mode == WG_DGRAD_ADD ? addend : pool_e != nullptr ? pool_e : bias, y, stats, bne, stream};
-        int rc;
-        if (variant == WV_PAIR64) {
-            int64_t blocks = runs * ((g.nkb + 1) / 2);
-            if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "%s: grid too large", what);
-            g.nblocks = (unsigned)blocks;
-            if (persist) blocks = std::min<int64_t>(blocks, (int64_t)wino_grids() * 2 * kCUs);
-            if (odd) {
-                if ((rc = wg3_launch<true, false, false>(mode, (unsigned)blocks, whole)) != CPG_OK) return rc;
-                CPG_CHECK_LAUNCH(what);
-                return CPG_OK;
-            }
-            // The leftover units of the last round (k_wg3<.., SPLIT>): the full rounds run as before on logical blocks 0 .. first_lb - 1, the rest
-            // as pieces of the channel loop into the workspace behind the packed filter, k_wg_tail_reduce adds the pieces (+ bias) into y.
-            const bool sh = ep == nullptr && wino_sh(g);
-            WgTail tail{};
-            const size_t tail_off = (need + 255) / 256 * 256;
-            if (ep == nullptr) tail = wino_tail_plan(g, g.nblocks, sh);      // (with the BatchNorm statistics too: k_wg_tail_reduce<true> sums them)
-            if (tail.on && ws_bytes < tail_off + tail.bytes) tail.on = false;       // (a caller with the round-4 workspace: one launch, as before)
-            WgGeom gt = g;
-            float *part0 = nullptr;
-            if (tail.on) {
-                g.nblocks = tail.first_lb;
-                gt.split_first = tail.first_lb, gt.split_s = tail.S, gt.split_nch = tail.nch_per, gt.split_stride = tail.stride;
-                gt.nblocks = (unsigned)((sh ? 2 : 1) * tail.left * tail.S);
-                // piece 0's slice, addressed like y: its first image is n_first
-                part0 = reinterpret_cast<float *>(reinterpret_cast<uintptr_t>(ws) + tail_off) - (int64_t)tail.n_first * g.M * H * W;
-            }
-            auto finish_tail = [&]() {
-                const dim3 rg(stream_grid((int64_t)(tail.end_lb - tail.first_lb) * 64 * W1_T, 256));
-                if (pool_e != nullptr)
-                    hipLaunchKernelGGL((k_wg_tail_reduce<true, true>), rg, dim3(256), 0, stream, gt, part0, bias, y, tail.first_lb, tail.end_lb, stats, (const float *)pool_e);
-                else if (stats != nullptr)
-                    hipLaunchKernelGGL(k_wg_tail_reduce<true>, rg, dim3(256), 0, stream, gt, part0, bias, y, tail.first_lb, tail.end_lb, stats, (const float *)nullptr);
-                else
-                    hipLaunchKernelGGL(k_wg_tail_reduce<false>, rg, dim3(256), 0, stream, gt, part0, bias, y, tail.first_lb, tail.end_lb, (float *)nullptr, addend);
-            };
-            const WgLaunch pieces{gt, x, up, nullptr, part0, nullptr, none, stream};      // (the tail: raw partial outputs, forward or input gradient)
-            const unsigned tb = (unsigned)(tail.left * tail.S);
-            // two units per block sharing the input transform (k_wg3<..., SH>): training launches whose 64-channel blocks pair up
-            if (sh) {
-                int64_t pairs = (int64_t)g.nblocks / 2;
-                if (persist) pairs = std::min<int64_t>(pairs, (int64_t)wino_grids() * kCUs);       // (one four-wave block per CU is resident)
-                if ((rc = wg3_launch<false, true, false>(mode, (unsigned)pairs, whole)) != CPG_OK) return rc;
-                if (tail.on) {
-                    if ((rc = wg3_launch<false, true, true>(dgrad ? WG_DGRAD : WG_FWD, tb, pieces)) != CPG_OK) return rc;
-                    finish_tail();
-                }
-                CPG_CHECK_LAUNCH(what);
-                return CPG_OK;
-            }
-            if (tail.on) blocks = std::min<int64_t>(blocks, (int64_t)g.nblocks);
-            if ((rc = wg3_launch<false, false, false>(mode, (unsigned)blocks, whole)) != CPG_OK) return rc;
-            if (tail.on) {
-                if ((rc = wg3_launch<false, false, true>(dgrad ? WG_DGRAD : WG_FWD, tb, pieces)) != CPG_OK) return rc;
-                finish_tail();
-            }
-            CPG_CHECK_LAUNCH(what);
-            return CPG_OK;
-        }
-        if (variant == WV_PAIR) {
-            const int64_t blocks = runs * g.nkb;
-            if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "%s: grid too large", what);
-            if ((rc = wg2_launch(mode, (unsigned)blocks, whole)) != CPG_OK) return rc;
-            CPG_CHECK_LAUNCH(what);
-            return CPG_OK;
-        }
-        int64_t blocks = (runs + 3) / 4 * g.nkb;
-        if (blocks > 0x7FFFFFFFll) return fail(CPG_E_UNSUPPORTED, "%s: grid too large", what);
-        g.nblocks = (unsigned)blocks;
-        if (persist) blocks = std::min<int64_t>(blocks, (int64_t)wino_grids() * kCUs);
-        if ((rc = wg1_launch(mode, (unsigned)blocks, whole)) != CPG_OK) return rc;
-        CPG_CHECK_LAUNCH(what);
-        return CPG_OK;
-    }
-    if (ep != nullptr) return fail(CPG_E_UNSUPPORTED, "%s: the block kernels have no inference epilogue", what);
-    return wino_run_block(dgrad, N, c_read, m, H, W, K, C, x, w, pm, thr, bias, y, stats, ws, stream, what);
-}
-
 static int wg2_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
     switch (mode) {
         case WG_FWD_BNE: WG_GO((k_wg2<false, false, true>), blocks, 128, a, nullptr); return CPG_OK;
@@ -2423,26 +2317,83 @@ static int wg1_launch(WgMode mode, unsigned blocks, const WgLaunch &a) {
     }
 }
 #undef WG_GO
+// the cooperative block kernel k_wg_fwd: its own pack (k_wg_pack's layout, `bk` channels per block), bias and statistics only
+static void wg_block_run(const WinoPlan &p, const cpg::WinoCall &c) {
+    const int bk = 8 * p.nw;
+    float *up = (float *)c.ws;
+    hipLaunchKernelGGL(k_wg_pack, dim3(stream_grid((int64_t)p.g.nkb * p.g.nch * bk * WG_CK, 256)), dim3(256), 0, c.stream, c.w, c.pm, c.thr, up,
+                       c.K, c.C, c.m, c.c_read, p.g.nch, c.dgrad ? 1 : 0, bk);
+    if (p.nw == 8) wino_launch<8>(c.dgrad != 0, p.g, p.grid, c.x, up, c.bias, c.y, c.stats, c.stream);
+    else wino_launch<4>(c.dgrad != 0, p.g, p.grid, c.x, up, c.bias, c.y, c.stats, c.stream);
+}
 
-static int wino_run_block(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
-                          float thr, const float *bias, float *y, float *stats, void *ws, hipStream_t stream, const char *what) {
-    const int nw = wino_nw(c_read, m), BK = 8 * nw;
-    WgGeom g;
-    g.N = N, g.C = c_read, g.H = H, g.W = W, g.M = m;
-    g.th = H / 2, g.tw = W / 2, g.tiles_img = g.th * g.tw;
-    g.inv_timg = 1.0f / (float)g.tiles_img, g.inv_tw = 1.0f / (float)g.tw;
-    g.tiles_total = (int64_t)N * g.tiles_img;
-    g.nkb = pad_to(m, BK) / BK, g.nch = pad_to(c_read, WG_CK) / WG_CK;
-    g.span = (WG_T + g.tiles_img - 1) / g.tiles_img + 1;
-    float *up = (float *)ws;
-    hipLaunchKernelGGL(k_wg_pack, dim3(stream_grid((int64_t)g.nkb * g.nch * BK * WG_CK, 256)), dim3(256), 0, stream, w, pm, thr, up,
-                       K, C, m, c_read, g.nch, dgrad ? 1 : 0, BK);
-    const int64_t tblocks = cpg_conv3x3_wino_tiles(N, c_read, m, H, W);
-    const int rc = nw == 8 ? wino_launch<8>(dgrad != 0, g, tblocks, x, up, bias, y, stats, stream)
-                           : wino_launch<4>(dgrad != 0, g, tblocks, x, up, bias, y, stats, stream);
+// The one entry (cpg_dispatch.h: cpg::WinoCall): validate, plan, take or pack the operand, launch the plan.
+int cpg_conv3x3_wino_launch(const cpg::WinoCall &c) {
+    char what[96];
+    snprintf(what, sizeof what, "%s(winograd)", c.what);
+    const cpg::EvalEpilogue *const ep = c.ep;
+    // ---- validate: what the call asks for, then what the plan can carry
+    CPG_REQUIRE(c.K == (c.dgrad ? c.c_read : c.m) && c.C == (c.dgrad ? c.m : c.c_read), "%s: the weight is [K][C][3][3], K x C = %d x %d here", what,
+                c.dgrad ? c.c_read : c.m, c.dgrad ? c.m : c.c_read);
+    if (ep != nullptr && ep->kind == cpg::EvalEpilogue::PRELU && ep->slope == nullptr) return fail(CPG_E_INVALID, "%s: null slope", what);
+    if (ep != nullptr && ep->kind == cpg::EvalEpilogue::BN_EVAL && ep->residual != nullptr)
+        return fail(CPG_E_UNSUPPORTED, "%s: no residual behind the BatchNorm", what);
+    // addend: added to the result in the epilogue (k_wg3<.., ADD>; the tail pieces' share in k_wg_tail_reduce)
+    if (c.addend != nullptr && (!c.dgrad || c.bias != nullptr || ep != nullptr || c.stats != nullptr))
+        return fail(CPG_E_INVALID, "%s: an addend rides in plain input-gradient launches only", what);
+    WinoWant want{c.dgrad != 0, ep != nullptr, true};
+    WinoPlan p = wino_plan(want, c.N, c.c_read, c.m, c.H, c.W);
+    if (!p.ok || (c.addend != nullptr && !p.addend)) return fail(CPG_E_UNSUPPORTED, "%s: shape not supported", what);
+    if (ep != nullptr && !p.eval) return fail(CPG_E_UNSUPPORTED, "%s: the block kernels have no inference epilogue", what);
+    if (ep != nullptr && ep->pool && (ep->kind != cpg::EvalEpilogue::BN_EVAL || !p.eval_pool))
+        return fail(CPG_E_UNSUPPORTED, "%s: the pooled epilogue is the BatchNorm epilogue's, on the one- and two-wave kernels of an even map", what);
+    if (c.ws == nullptr || c.ws_bytes < p.pack_bytes) return fail(CPG_E_WORKSPACE, "%s: workspace %zu < %zu bytes", what, c.ws_bytes, p.pack_bytes);
+    CPG_REQUIRE((((uintptr_t)c.ws) & 15) == 0, "%s: workspace must be 16-byte aligned", what);
+    if (!p.grid_ok) return fail(CPG_E_UNSUPPORTED, "%s: grid too large", what);
+    // The run-time degrade: a caller whose workspace holds the packed filter but not the tail pieces (cpg_conv2d_workspace_bytes of an
+    // older release) gets the plan without a tail -- the single launch.
+    if (p.tail.on && c.ws_bytes < p.tail.off + p.tail.bytes) want.tail = false, p = wino_plan(want, c.N, c.c_read, c.m, c.H, c.W);
+    // ---- the operand: the caller's, or packed here.  (The inference epilogue's pack also writes the liveness flags -- zeroed first --: never
+    // taken from a caller's operand.)
+    const WgBnEval bne = wg_epilogue(ep, c.live, c.m);
+    if (c.live != nullptr) {
+        hipError_t e = hipMemsetAsync(c.live, 0, c.live_words * sizeof(int), c.stream);
+        if (e != hipSuccess) return hip_status(e, what);
+    }
+    const float *up = (const float *)c.ws;
+    if (p.variant != WV_BLOCK) {
+        const cpg::PackedOperand pre = ep == nullptr ? c.packed : cpg::PackedOperand();
+        if (const int rc = cpg::packed_fits(pre, p.pack_bytes, what)) return rc;
+        if (pre.data != nullptr)
+            up = pre.data;
+        else
+            hipLaunchKernelGGL(k_wg1_pack, dim3(stream_grid(p.job.total, 256)), dim3(256), 0, c.stream, c.w, c.pm, c.thr, (float *)c.ws, c.K, c.C, c.m,
+                               c.c_read, p.job.c, p.job.d, bne.live, bne.Mp);
+    }
+    // ---- the launch
+    const WgMode mode = wg_mode(c);
+    const WgLaunch whole{p.g, c.x, up, wg_slot(mode, c), c.y, c.stats, bne, c.stream};
+    int rc = CPG_OK;
+    switch (p.variant) {
+        case WV_PAIR64: rc = wg3_run(p, mode, whole, c); break;
+        case WV_PAIR: rc = wg2_launch(mode, p.grid, whole); break;
+        case WV_WAVE: rc = wg1_launch(mode, p.grid, whole); break;
+        default: wg_block_run(p, c);
+    }
     if (rc != CPG_OK) return rc;
     CPG_CHECK_LAUNCH(what);
     return CPG_OK;
+}
+
+// today's signature, for tools/wino_bench.py in a CPG_EXPORT_ALL build: a plain forward (stats may be null) or input gradient
+extern "C" int cpg_conv3x3_wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x,
+                                    const float *w, const float *pm, float thr, const float *bias, float *y, float *stats,
+                                    void *ws, size_t ws_bytes, hipStream_t stream) {
+    cpg::WinoCall c{};
+    c.dgrad = dgrad, c.N = N, c.c_read = c_read, c.m = m, c.H = H, c.W = W, c.K = K, c.C = C;
+    c.x = x, c.w = w, c.pm = pm, c.thr = thr, c.bias = bias, c.y = y, c.stats = stats;
+    c.ws = ws, c.ws_bytes = ws_bytes, c.stream = stream, c.what = dgrad ? "cpg_conv2d_dgrad" : "cpg_conv2d_fwd";
+    return cpg_conv3x3_wino_launch(c);
 }
 
 // cpg_conv2d_pack's launch (declared in cpg_common.h): job b may be null

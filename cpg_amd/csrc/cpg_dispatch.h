@@ -85,43 +85,54 @@ int cpg_conv3x3s2_wgrad(const cpg_conv_desc *d, const float *x, const float *gy,
                         float *gpm, void *ws, size_t ws_bytes, hipStream_t stream);
 
 // ---- conv3x3_wino.hip: Winograd F(2x2, 3x3) forward / input gradient.  c_read / m: channels contracted over / produced ----------------------
+// Every query below reads the plan (wino_plan) of the launch cpg_conv3x3_wino_launch makes, from the shape and the option table alone.
 // eligibility of one launch (CPG_NO_WINO: never; odd maps: the two-wave kernel's ODD instances only)
 extern "C" int cpg_conv3x3_wino_ok(int N, int c_read, int m, int H, int W);
 // bytes of the transformed filter at the head of the workspace
 extern "C" size_t cpg_conv3x3_wino_pack_bytes(int c_read, int m);
-// workspace behind the packed filter for the partial outputs of a tail launch (0: this launch has none)
-extern "C" size_t cpg_conv3x3_wino_tail_bytes(int N, int c_read, int m, int H, int W);
 // BatchNorm-statistics tiles per channel of a forward launch (stats[m][tiles][2])
 extern "C" int cpg_conv3x3_wino_tiles(int N, int c_read, int m, int H, int W);
-// the packed operand of the launch cpg_conv3x3_wino_run would make; false: none a caller could hand in (a shape cpg_conv3x3_wino_ok
-// refuses; the cooperative block kernel, which packs for itself)
-bool cpg_conv3x3_wino_pack_job(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, cpg::PackJob *job);
-// y[N][m][H][W] = conv3x3(x[N][c_read][H][W], W .* bin(pm)) (+ bias); dgrad: x = gy, the filter transposed and flipped.
-// w is the layer's [K][C][3][3] weight.  stats (forward only, may be null): [m][tiles][2]
+// workspace behind the packed filter for the partial outputs of a tail launch (0: this launch has none)
+size_t cpg_conv3x3_wino_tail_bytes(int N, int c_read, int m, int H, int W);
+// the packed operand of that launch; false: none a caller could hand in (a shape that is not eligible; the cooperative block kernel,
+// which packs for itself)
+bool cpg_conv3x3_wino_pack_job(int dgrad, int N, int c_read, int m, int H, int W, cpg::PackJob *job);
+// 1: the launch can carry ... the 2x2 window maxima of a forward with statistics (the two-wave kernel on an even map, m a multiple of 64;
+// CPG_NO_POOL_MAX: never); the inference epilogues (not the cooperative block kernel); the pooled one (ep.pool: ... of an even map);
+// an addend to the input gradient (the two-wave kernel: >= 64 channels on both sides, or an odd map)
+int cpg_conv3x3_wino_pool_max_ok(int N, int c_read, int m, int H, int W);
+int cpg_conv3x3_wino_eval_ok(int N, int c_read, int m, int H, int W);
+int cpg_conv3x3_wino_eval_pool_ok(int N, int c_read, int m, int H, int W);
+int cpg_conv3x3_wino_dgrad_add_ok(int N, int c_read, int m, int H, int W);
+// One launch: y[N][m][H][W] = conv3x3(x[N][c_read][H][W], W .* bin(pm)); dgrad: x = gy, the filter transposed and flipped.  Zero-initialise,
+// then name what the call carries.  Refused before anything is launched: a null slope (CPG_E_INVALID), a residual behind the BatchNorm,
+// ep.pool where cpg_conv3x3_wino_eval_pool_ok answers 0, an addend outside a plain input gradient (CPG_E_INVALID) or where
+// cpg_conv3x3_wino_dgrad_add_ok answers 0, a shape cpg_conv3x3_wino_ok refuses.
+namespace cpg {
+struct WinoCall {
+    int dgrad, N, c_read, m, H, W;
+    int K, C;                         // the layer's weight w is [K][C][3][3]: (m, c_read), dgrad: (c_read, m)
+    const float *x, *w, *pm;
+    float thr;
+    const float *bias;                // forward only, may be null
+    const float *addend;              // plain input gradient only, may be null: gx = dgrad(gy) + addend
+    float *pool_max;                  // forward with stats and no bias only, may be null: receives the 2x2 window maxima of y
+    float *y, *stats;                 // stats (forward only, may be null): [m][tiles][2] partial sums for the BatchNorm
+    const EvalEpilogue *ep;           // forward only, may be null: the inference epilogue (ep->pool: y is the pooled tensor), with the dead-channel skip:
+    int *live;                        // ... its liveness words (may be null): live_words ints, zeroed here, layout of k_c3_pack
+    size_t live_words;                //     (cpg_conv3x3_fwd_eval copies ep.skip_stats out of them)
+    PackedOperand packed;             // launches without ep on the one- and two-wave kernels stream it; the others pack for themselves
+    void *ws;                         // cpg_conv3x3_wino_pack_bytes + (for the tail pieces; without: the single launch) cpg_conv3x3_wino_tail_bytes
+    size_t ws_bytes;
+    hipStream_t stream;
+    const char *what;                 // the public entry point the caller used, for messages
+};
+}  // namespace cpg
+int cpg_conv3x3_wino_launch(const cpg::WinoCall &c);
+// ... a plain forward (stats may be null) or input gradient, for tools/wino_bench.py
 extern "C" int cpg_conv3x3_wino_run(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w,
                                     const float *pm, float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes,
                                     hipStream_t stream);
-// ... with side arguments.  pool_max (may be null): receives the window maxima of y; needs stats, no bias and cpg_conv3x3_wino_pool_max_ok
-int cpg_conv3x3_wino_run_side(int dgrad, int N, int c_read, int m, int H, int W, int K, int C, const float *x, const float *w, const float *pm,
-                              float thr, const float *bias, float *y, float *stats, void *ws, size_t ws_bytes, hipStream_t stream,
-                              const cpg::PackedOperand &packed, float *pool_max);
-// 1: a forward launch with statistics of this shape can also write the 2x2 window maxima of its output, to the buffer a caller attached
-// with cpg_conv2d_fwd_attach_pool_max (the two-wave kernel on an even map, m a multiple of 64; CPG_NO_POOL_MAX: never)
-extern "C" int cpg_conv3x3_wino_pool_max_ok(int N, int c_read, int m, int H, int W);
-// 1: the inference epilogue is available on the Winograd kernels (not on the cooperative block kernel)
-extern "C" int cpg_conv3x3_wino_eval_ok(int N, int c_read, int m, int H, int W);
-// 1: ... and the pooled one (ep.pool): every such launch of an even map
-extern "C" int cpg_conv3x3_wino_eval_pool_ok(int N, int c_read, int m, int H, int W);
-// forward with ep in the epilogue (BN_EVAL without a residual, or PRELU; a null slope is refused; ep.pool where cpg_conv3x3_wino_eval_pool_ok
-// answers 0 is refused before anything is launched) and the dead-channel skip;
-// live (may be null): live_words ints, zeroed here, layout of k_c3_pack (cpg_conv3x3_fwd_eval copies ep.skip_stats out of them)
-int cpg_conv3x3_wino_run_eval(int N, int C, int K, int H, int W, const float *x, const float *w, const float *pm, float thr, const float *bias,
-                              const cpg::EvalEpilogue &ep, int *live, size_t live_words, float *y, void *ws, size_t ws_bytes, hipStream_t stream,
-                              const char *what);
-// input gradient + addend (gx = dgrad(gy) + addend): the two-wave kernel's launches (>= 64 channels on both sides, or an odd map)
-extern "C" int cpg_conv3x3_wino_dgrad_add_ok(int N, int c_read, int m, int H, int W);
-int cpg_conv3x3_wino_dgrad_add(int N, int c_read, int m, int H, int W, int K, int C, const float *gy, const float *w, const float *pm, float thr,
-                               const float *addend, float *gx, void *ws, size_t ws_bytes, hipStream_t stream, const cpg::PackedOperand &packed);
 
 // ---- conv3x3_wino_wgrad.hip: Winograd F(2x2, 3x3) weight gradient (maps 14 or a multiple of 28 wide, channel counts multiples of 32) -------
 extern "C" int cpg_conv3x3_wino_wgrad_ok(const cpg_conv_desc *d);

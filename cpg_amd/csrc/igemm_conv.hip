@@ -901,8 +901,13 @@ extern "C" int cpg_conv2d_dgrad_add(const cpg_conv_desc *d, const float *gy, con
     if (!cpg_conv2d_dgrad_add_supported(d))
         return fail(CPG_E_UNSUPPORTED, "cpg_conv2d_dgrad_add: dense 1x1 layers and the 3x3 layers of the two-wave Winograd kernel fuse the addend");
     CPG_REQUIRE(addend != nullptr && gy && w && gx, "cpg_conv2d_dgrad_add: null pointer");
-    if (cpg_conv3x3_supported(d))
-        return cpg_conv3x3_wino_dgrad_add(d->N, d->K, d->C, d->H, d->W, d->K, d->C, gy, w, pm, thr, addend, gx, ws, ws_bytes, (hipStream_t)stream, packed);
+    if (cpg_conv3x3_supported(d)) {      // reads gy (K channels), produces gx (C channels)
+        cpg::WinoCall c{};
+        c.dgrad = 1, c.N = d->N, c.c_read = d->K, c.m = d->C, c.H = d->H, c.W = d->W, c.K = d->K, c.C = d->C;
+        c.x = gy, c.w = w, c.pm = pm, c.thr = thr, c.addend = addend, c.y = gx, c.packed = packed;
+        c.ws = ws, c.ws_bytes = ws_bytes, c.stream = (hipStream_t)stream, c.what = "cpg_conv2d_dgrad_add";
+        return cpg_conv3x3_wino_launch(c);
+    }
     return cpg_conv1x1_dgrad(d, gy, w, pm, thr, gx, ws, ws_bytes, (hipStream_t)stream, packed, addend);
 }
 

@@ -471,6 +471,41 @@ def winograd_tail_pieces_equal_the_single_launch(N, C, K, H, bias, libopt, buf=P
     return kept
 
 
+def winograd_tail_degrades_to_the_single_launch(libopt, buf=PLAIN):
+    """cpg_conv2d_fwd of (11, 96, 128, 56 x 56) through the raw C ABI: 270 four-wave blocks against 256 slots -- 14 blocks left, 12 pieces each,
+    a 19.3 MB tail.  (a) the workspace cpg_conv2d_workspace_bytes asks for, (b) the same under CPG_WINO_TAIL=0, (c) a workspace of exactly
+    cpg_conv2d_pack_bytes(d, 0) bytes under the default options: room for the packed filter, none for the tail pieces."""
+    from cpg_amd import _lib as L
+    lib = L.lib()
+    N, C, K, H = 11, 96, 128, 56
+    assert (N, C, K, H, False) in WINOGRAD_TAIL_CASES
+    g = torch.Generator(device=DEV).manual_seed(N + C + K + H)
+    x = buf.put(torch.randn(N, C, H, H, generator=g, device=DEV))
+    w = buf.put(torch.randn(K, C, 3, 3, generator=g, device=DEV) * (2.0 / (C * 9)) ** 0.5)
+    d = L.ConvDesc()
+    d.N, d.C, d.H, d.W, d.K, d.R, d.S = N, C, H, H, K, 3, 3
+    d.stride_h = d.stride_w = d.pad_h = d.pad_w = d.dil_h = d.dil_w = d.groups = 1
+    full, packed = int(lib.cpg_conv2d_workspace_bytes(ctypes.byref(d))), int(lib.cpg_conv2d_pack_bytes(ctypes.byref(d), 0))
+    assert lib.cpg_conv2d_winograd(ctypes.byref(d), 0) == 1 and 0 < packed < full
+
+    def fwd(nbytes):
+        ws, nb = L.workspace(nbytes, x.device)
+        assert nbytes <= nb < nbytes + 4
+        y = buf.empty((N, K, H, H))
+        rc = lib.cpg_conv2d_fwd(ctypes.byref(d), L.dptr(x), L.dptr(w), None, 0.0, None, L.dptr(y), L.dptr(ws), nbytes, L.stream_ptr())
+        return rc, y
+    rc_a, a = fwd(full)
+    libopt.set('CPG_WINO_TAIL', 0)
+    rc_b, b = fwd(full)
+    libopt.set('CPG_WINO_TAIL', None)
+    rc_c, c = fwd(packed)
+    assert (rc_a, rc_b, rc_c) == (L.CPG_OK, L.CPG_OK, L.CPG_OK), lib.cpg_last_error()
+    assert torch.equal(c, b)                       # no room for the pieces: the single launch, bit for bit
+    assert not torch.equal(a, b)                   # another association of the channel sum: the tail really ran in (a)
+    assert torch.equal(a[:5], b[:5])               # the full rounds are untouched
+    return [a, b, c]
+
+
 # --------------------------------------------------------------------------- fused BatchNorm -> ReLU (SURVEY 8f.2)
 BN_RELU_SHAPES = [(8, 64, 56, 56), (4, 16, 224, 224), (16, 512, 14, 14), (3, 5, 7, 9), (2, 3, 1, 1),
                   # planes of >= 16 * 256 items that are no multiple of 4: the scalar large-plane walk, and with 129 x 129 its 16-trip flush

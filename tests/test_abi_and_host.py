@@ -120,7 +120,7 @@ def test_cross_file_helpers_are_declared_once():
     header = open(os.path.join(csrc, 'cpg_dispatch.h')).read()
     declared = [m.group(0).split('(')[0].split()[-1] for m in proto.finditer(header)]
     assert len(declared) == len(set(declared)) >= 60, sorted(n for n in declared if declared.count(n) > 1)
-    for name in ('cpg_conv3x3_wino_run', 'cpg_conv3x3_wino_run_eval', 'cpg_conv3x3_wino_wgrad', 'cpg_conv1x1_fwd', 'cpg_pw_gemm_nn_ok'):
+    for name in ('cpg_conv3x3_wino_run', 'cpg_conv3x3_wino_launch', 'cpg_conv3x3_wino_wgrad', 'cpg_conv1x1_fwd', 'cpg_pw_gemm_nn_ok'):
         assert name in declared
 
 

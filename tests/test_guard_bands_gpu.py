@@ -163,6 +163,12 @@ def test_winograd_tail_guarded(libopt):
         finish(led, PC.winograd_tail_pieces_equal_the_single_launch(N, C, K, H, bias, libopt, buf=BUF))
 
 
+def test_winograd_tail_degrade_guarded(libopt):
+    """... and the launch in a workspace that ends behind the packed filter writes no tail piece past it."""
+    with guarding() as led:
+        finish(led, PC.winograd_tail_degrades_to_the_single_launch(libopt, buf=BUF))
+
+
 # --------------------------------------------------------------------------- linear
 @pytest.mark.parametrize('B,I,O,pm', [(7, 513, 129, True), (1, 64, 5, False)])
 def test_linear_oracle_guarded(B, I, O, pm):

@@ -481,6 +481,13 @@ def test_winograd_tail_pieces_equal_the_single_launch(N, C, K, H, bias, libopt):
     PC.winograd_tail_pieces_equal_the_single_launch(N, C, K, H, bias, libopt)
 
 
+def test_winograd_tail_degrades_to_the_single_launch_in_a_short_workspace(libopt):
+    """A caller whose workspace holds the packed filter but not the tail pieces gets the single launch: cpg_conv2d_fwd with exactly
+    cpg_conv2d_pack_bytes(d, 0) bytes returns CPG_OK and the bits of the CPG_WINO_TAIL=0 launch, while the full workspace runs the tail
+    (other bits behind the full rounds, the same bits in the first five images).  Bit comparisons between launches of the same kernels:
+    no tolerance."""
+    PC.winograd_tail_degrades_to_the_single_launch(libopt)
+
 
 @pytest.mark.parametrize('hint', [0, 1])
 def test_winograd_kernels_repeat_bit_for_bit_at_full_occupancy(hint):

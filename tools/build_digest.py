@@ -4,12 +4,12 @@
   device   for each .hip of cpg_amd.build.SOURCES the sha256 of the .text, .rodata and .note sections of its gfx950 device ELF
            (code, constants, kernel descriptors and metadata; the ELF as a whole also carries a per-compile __hip_cuid_* symbol)
   planner  a sha256 over the answers of every host-only query entry point of the C ABI, for a fixed sweep of conv descriptors under
-           the default option table, every boolean CPG_* switch set one at a time, and CPG_WINO_KERNEL 0-3; `pairs` counts the
-           (descriptor, option setting) pairs
+           the default option table, every boolean CPG_* switch set one at a time, CPG_WINO_KERNEL 0-3 and every --set NAME=VALUE
+           (the integer switches: each one more setting of the sweep, applied alone); `pairs` counts the (descriptor, option setting) pairs
 
 Two trees whose digests agree launch the same device code with the same plans.  Needs hipcc and a built library, no GPU.
 
-    python tools/build_digest.py [--no-device] [--no-planner]
+    python tools/build_digest.py [--no-device] [--no-planner] [--set CPG_WINO_TAIL=0 --set CPG_WINO_NW=8 ...]
 """
 import argparse
 import ctypes
@@ -89,15 +89,15 @@ def descriptors():
 LINEAR = [(b, i, o) for b in (256, 32) for i, o in ((25088, 4096), (4096, 4096), (4096, 1000), (2048, 1000), (512 * 7 * 6, 512), (512, 10))]
 
 
-def option_settings():
+def option_settings(extra=()):
     # the boolean switches of cpg_common.h's Opt enum are the OPT_NO_* / OPT_DISABLE_* entries; OPT_X is spelled CPG_X
     text = open(os.path.join(build.CSRC, 'cpg_common.h')).read()
     enum = text[text.index('enum Opt {'):text.index('OPT_COUNT')]
     booleans = ['CPG_' + n for n in re.findall(r'^\s*OPT_((?:NO|DISABLE)_\w+),', enum, re.M)]
-    return [None] + [(b, 1) for b in booleans] + [('CPG_WINO_KERNEL', v) for v in range(4)]
+    return [None] + [(b, 1) for b in booleans] + [('CPG_WINO_KERNEL', v) for v in range(4)] + list(extra)
 
 
-def planner_digest():
+def planner_digest(extra=()):
     from cpg_amd import _lib as L
     lib = L.lib()
     descs = []
@@ -117,7 +117,8 @@ def planner_digest():
                                                'cpg_stem_bn_wgrad_workspace')]
     h = hashlib.sha256()
     pairs = 0
-    for setting in option_settings():
+    settings = option_settings(extra)
+    for setting in settings:
         if setting is not None:
             L.set_option(*setting)
         for d in descs:
@@ -127,19 +128,27 @@ def planner_digest():
             h.update(('%d\n' % lib.cpg_linear_workspace_bytes(*shape)).encode())
         if setting is not None:
             L.set_option(setting[0], None)
-    return {'sha256': h.hexdigest(), 'pairs': pairs, 'descriptors': len(descs), 'option_settings': len(option_settings())}
+    return {'sha256': h.hexdigest(), 'pairs': pairs, 'descriptors': len(descs), 'option_settings': len(settings)}
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--no-device', action='store_true')
     ap.add_argument('--no-planner', action='store_true')
+    ap.add_argument('--set', action='append', default=[], metavar='NAME=VALUE', dest='settings',
+                    help='one more option setting of the planner sweep, applied alone (repeatable)')
     a = ap.parse_args()
+    extra = []
+    for s in a.settings:
+        name, eq, value = s.partition('=')
+        if not eq or not name.startswith('CPG_') or not re.fullmatch(r'-?\d+', value):
+            ap.error('--set takes NAME=VALUE with a CPG_* switch and an integer, not %r' % s)
+        extra.append((name, int(value)))
     out = {}
     if not a.no_device:
         out['device'] = device_digest()
     if not a.no_planner:
-        out['planner'] = planner_digest()
+        out['planner'] = planner_digest(extra)
     print(json.dumps(out, indent=1, sort_keys=True))
 
 
