@@ -106,6 +106,12 @@ _SIGNATURES = {
     'cpg_adam_route_step_multi': (_int, [ctypes.POINTER(AdamItem), _i32, _i32, _i32, _f64, _f64, _f64, _f64, _i32, _vp]),
     'cpg_sgd_route_zero_step': (_int, [_vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _i32, _i32, _i64, _vp]),
     'cpg_sgd_route_zero_step_multi': (_int, [ctypes.POINTER(SgdItem), _i32, _i32, _f32, _f32, _f32, _i32, _i32, _vp]),
+    'cpg_step_stats_workspace_bytes': (_sz, [ctypes.POINTER(_i64), _i32]),
+    'cpg_sgd_route_step_multi_stats': (_int, [ctypes.POINTER(SgdItem), _i32, _i32, _f32, _f32, _f32, _i32, _i32, _i64, _vp, _vp, _sz, _vp, _vp]),
+    'cpg_sgd_route_zero_step_multi_stats': (_int, [ctypes.POINTER(SgdItem), _i32, _i32, _f32, _f32, _f32, _i32, _i32, _i64, _vp, _vp, _sz, _vp,
+                                                   _vp]),
+    'cpg_adam_route_step_multi_stats': (_int, [ctypes.POINTER(AdamItem), _i32, _i32, _i32, _f64, _f64, _f64, _f64, _i32, _f32, _i64, _vp, _vp,
+                                               _sz, _vp, _vp]),
     'cpg_adam_route_step': (_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _f64, _f64, _i32, _i64, _vp]),
     'cpg_bn_workspace_bytes': (_sz, [_i32, _i32, _i32]),
     'cpg_bn_relu_fwd_train': (_int, [_vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),

@@ -187,16 +187,20 @@ class _Net(object):
 
 
 class BaselineSession(object):
-    def __init__(self, arch='vgg16_bn_cifar100', device='cuda', seed=None, sgd_mode='fused', args=None, policy=None):
+    def __init__(self, arch='vgg16_bn_cifar100', device='cuda', seed=None, sgd_mode='fused', args=None, policy=None, telemetry=False,
+                 stop_on_nonfinite=False):
         """arch: a name cpg_amd.packnet_models.factory knows, or a callable (dataset_history=, dataset2num_classes=) -> model with the
         packnet_models.VGG interface.  seed: torch.manual_seed before every model construction (the reference seeds each process, :60).
-        sgd_mode: utils.fused_sgd.PackNetSGD's mode.  policy: a key of POLICIES; default ARCH_POLICY's entry for `arch`, else 'cifar'."""
+        sgd_mode: utils.fused_sgd.PackNetSGD's mode.  policy: a key of POLICIES; default ARCH_POLICY's entry for `arch`, else 'cifar'.
+        telemetry / stop_on_nonfinite: OPT-IN, every Manager of this session trains with step telemetry (utils/telemetry.py; needs a
+        fused sgd_mode) and, with the second, raises TrainingDiverged out of the flows once a step went non-finite."""
         self.factory = packnet_models.factory(arch) if isinstance(arch, str) else arch
         self.policy_name = policy or (ARCH_POLICY.get(arch, 'cifar') if isinstance(arch, str) else 'cifar')
         self.policy = POLICIES[self.policy_name]
         self.device = torch.device(device)
         self.seed, self.sgd_mode = seed, sgd_mode
         self.args = args or default_args()
+        self.telemetry, self.stop_on_nonfinite = bool(telemetry), bool(stop_on_nonfinite)
         self.models = {}            # dataset -> _Net of the scratch / finetune flows (one model per task)
         self.packnet = None         # the one shared _Net of the packnet flow
         self.records = {}           # dataset -> TaskRecord of the last flow run for it
@@ -217,6 +221,8 @@ class BaselineSession(object):
     def _manager(self, holder, dataset, mode, train_loader, val_loader):
         args = copy.copy(self.args)
         args.dataset, args.mode = dataset, mode
+        args.telemetry = self.telemetry or getattr(args, 'telemetry', False)
+        args.stop_on_nonfinite = self.stop_on_nonfinite or getattr(args, 'stop_on_nonfinite', False)
         return Manager(args, holder.model, holder.shared_layer_info, holder.masks, train_loader, val_loader)
 
     def make_optimizers(self, holder, mgr, lr):

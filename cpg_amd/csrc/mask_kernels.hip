@@ -395,6 +395,240 @@ __global__ __launch_bounds__(kThreads) void k_adam_route_multi(const AdamItems i
                     AdamHyper{cur, mode, step_size, omb1, beta2, omb2, eps, bc2_sqrt});
 }
 
+// ---------------------------------------------------------------- STATS forms of the multi-tensor passes (step telemetry)
+// The same update, element for element (sgd_route_one / adam_route_one are called, never restated), and a reduction of what the pass
+// has in registers anyway into one record of kStatFields doubles per piece (include/cpg_hip.h: cpg_sgd_step_stats / cpg_pm_step_stats).
+// Separate kernels: the plain ones above keep their registers and their schedule.  Three stages, no atomics anywhere, so a record is
+// bit-reproducible:  thread (sums in fp64 -- the square of an fp32 value is exact there --, maxima fp32, counts integers; the
+// thread's elements in ascending order)  ->  block (xor butterfly over the wave, then the four waves in order through LDS; one
+// record per piece, plain stores to partials[piece])  ->  k_step_stats_finalize (one wave per item: lane l adds pieces l, l + 64, ...,
+// then the same butterfly) and k_step_health (the sticky record).
+constexpr int kStatFields = 8;
+constexpr unsigned kSgdMaxFields = (1u << 3) | (1u << 7);       // g_absmax, w_absmax: merged by maximum, every other field by sum
+constexpr unsigned kPmMaxFields = 1u << 2;                      // g_absmax
+
+struct SgdAcc {
+    double g_sumsq = 0, dw_sumsq = 0, w_sumsq = 0;
+    float g_absmax = 0, w_absmax = 0;
+    unsigned n_routed = 0, g_nonfinite = 0, w_nonfinite = 0;
+    __device__ __forceinline__ void record(double (&r)[kStatFields]) const {
+        r[0] = n_routed, r[1] = g_nonfinite, r[2] = g_sumsq, r[3] = g_absmax, r[4] = w_nonfinite, r[5] = dw_sumsq, r[6] = w_sumsq, r[7] = w_absmax;
+    }
+};
+struct PmAcc {
+    double g_sumsq = 0, dpm_sumsq = 0;
+    float g_absmax = 0;
+    unsigned n_routed = 0, flips_on = 0, flips_off = 0, picked = 0, pm_nonfinite = 0;
+    __device__ __forceinline__ void record(double (&r)[kStatFields]) const {
+        r[0] = n_routed, r[1] = g_sumsq, r[2] = g_absmax, r[3] = dpm_sumsq, r[4] = flips_on, r[5] = flips_off, r[6] = picked, r[7] = pm_nonfinite;
+    }
+};
+
+// sum of x^2 and max |x| over the finite values: the square is formed in fp64 (a finite fp32 whose square overflows fp32 still counts)
+__device__ __forceinline__ void add_square(double &sumsq, double x) {
+#pragma clang fp contract(off)
+    const double sq = x * x;
+    sumsq += sq;
+}
+
+template <bool ZERO>
+__device__ __forceinline__ void sgd_route_one_stats(float &wv, float &gv, float &bv, int o, const SgdHyper h, SgdAcc &a) {
+    const float w0 = wv;
+    sgd_route_one<ZERO>(wv, gv, bv, o, h);
+    if (o == h.cur) {
+        a.n_routed++;
+        if (__builtin_isfinite(gv)) {
+            add_square(a.g_sumsq, (double)gv);
+            a.g_absmax = fmaxf(a.g_absmax, fabsf(gv));
+        } else {
+            a.g_nonfinite++;
+        }
+    }
+    if (__builtin_isfinite(wv)) {
+        add_square(a.w_sumsq, (double)wv);
+        a.w_absmax = fmaxf(a.w_absmax, fabsf(wv));
+        if (__builtin_isfinite(w0)) add_square(a.dw_sumsq, (double)wv - (double)w0);
+    } else {
+        a.w_nonfinite++;
+    }
+}
+
+__device__ __forceinline__ void adam_route_one_stats(float &p, float &g, float &m1, float &m2, int o, const AdamHyper h, float thr, PmAcc &a) {
+    const float p0 = p;
+    adam_route_one(p, g, m1, m2, o, h);
+    if (h.mode == CPG_MODE_FINETUNE && o != 0 && o < h.cur) {
+        a.n_routed++;
+        if (__builtin_isfinite(g)) {
+            add_square(a.g_sumsq, (double)g);
+            a.g_absmax = fmaxf(a.g_absmax, fabsf(g));
+        }
+        const bool on0 = p0 > thr, on1 = p > thr;      // the Binarizer's compare: false for NaN
+        a.flips_on += !on0 && on1;
+        a.flips_off += on0 && !on1;
+        a.picked += on1;
+    }
+    if (__builtin_isfinite(p)) {
+        if (__builtin_isfinite(p0)) add_square(a.dpm_sumsq, (double)p - (double)p0);
+    } else {
+        a.pm_nonfinite++;
+    }
+}
+
+template <bool ZERO>
+__device__ __forceinline__ void sgd_route_span_stats(float *w, float *gw, float *buf, const uint8_t *owner, int64_t begin, int64_t end,
+                                                     int64_t first, int64_t stride, int vec_ok, const SgdHyper h, SgdAcc &a) {
+    walk4(begin, end, first, stride, vec_ok,
+          [&](int64_t i) {
+              const uint32_t o4 = reinterpret_cast<const uint32_t *>(owner)[i];
+              F4 wv = reinterpret_cast<F4 *>(w)[i], gv = reinterpret_cast<F4 *>(gw)[i];
+              F4 bv = h.first ? F4{0.f, 0.f, 0.f, 0.f} : reinterpret_cast<F4 *>(buf)[i];
+              sgd_route_one_stats<ZERO>(wv.x, gv.x, bv.x, o4 & 255, h, a);
+              sgd_route_one_stats<ZERO>(wv.y, gv.y, bv.y, (o4 >> 8) & 255, h, a);
+              sgd_route_one_stats<ZERO>(wv.z, gv.z, bv.z, (o4 >> 16) & 255, h, a);
+              sgd_route_one_stats<ZERO>(wv.w, gv.w, bv.w, o4 >> 24, h, a);
+              reinterpret_cast<F4 *>(w)[i] = wv;
+              reinterpret_cast<F4 *>(gw)[i] = gv;
+              reinterpret_cast<F4 *>(buf)[i] = bv;
+          },
+          [&](int64_t i) {
+              float bv = h.first ? 0.f : buf[i];
+              sgd_route_one_stats<ZERO>(w[i], gw[i], bv, owner[i], h, a);
+              buf[i] = bv;
+          });
+}
+
+__device__ __forceinline__ void adam_route_span_stats(float *pm, float *gpm, float *m1, float *m2, const uint8_t *owner, int64_t begin,
+                                                      int64_t end, int64_t first, int64_t stride, int vec_ok, const AdamHyper h, float thr,
+                                                      PmAcc &a) {
+    walk4(begin, end, first, stride, vec_ok,
+          [&](int64_t i) {
+              const uint32_t o4 = reinterpret_cast<const uint32_t *>(owner)[i];
+              F4 pv = reinterpret_cast<F4 *>(pm)[i], gv = reinterpret_cast<F4 *>(gpm)[i];
+              F4 av = reinterpret_cast<F4 *>(m1)[i], bv = reinterpret_cast<F4 *>(m2)[i];
+              adam_route_one_stats(pv.x, gv.x, av.x, bv.x, o4 & 255, h, thr, a);
+              adam_route_one_stats(pv.y, gv.y, av.y, bv.y, (o4 >> 8) & 255, h, thr, a);
+              adam_route_one_stats(pv.z, gv.z, av.z, bv.z, (o4 >> 16) & 255, h, thr, a);
+              adam_route_one_stats(pv.w, gv.w, av.w, bv.w, o4 >> 24, h, thr, a);
+              reinterpret_cast<F4 *>(pm)[i] = pv;
+              reinterpret_cast<F4 *>(gpm)[i] = gv;
+              reinterpret_cast<F4 *>(m1)[i] = av;
+              reinterpret_cast<F4 *>(m2)[i] = bv;
+          },
+          [&](int64_t i) { adam_route_one_stats(pm[i], gpm[i], m1[i], m2[i], owner[i], h, thr, a); });
+}
+
+// every lane ends with the wave's merged record: partner lanes add (or take the maximum of) the same two values, so all agree bit for bit
+template <unsigned MAXMASK>
+__device__ __forceinline__ void wave_merge(double (&r)[kStatFields]) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+        for (int f = 0; f < kStatFields; ++f) {
+            const double other = __shfl_xor(r[f], m);
+            r[f] = ((MAXMASK >> f) & 1) ? fmax(r[f], other) : r[f] + other;
+        }
+    }
+}
+
+// the block's record (kThreads = 4 waves) to out[0 .. kStatFields): the waves are merged in order 0, 1, 2, 3 by threads 0 .. 7, one field each
+template <unsigned MAXMASK>
+__device__ __forceinline__ void block_merge_store(double (&r)[kStatFields], double *out) {
+    __shared__ double red[kThreads / 64][kStatFields];
+    wave_merge<MAXMASK>(r);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int f = 0; f < kStatFields; ++f) red[threadIdx.x >> 6][f] = r[f];
+    }
+    __syncthreads();
+    if (threadIdx.x < kStatFields) {
+        const int f = threadIdx.x;
+        double v = red[0][f];
+        for (int wv = 1; wv < kThreads / 64; ++wv) v = ((MAXMASK >> f) & 1) ? fmax(v, red[wv][f]) : v + red[wv][f];
+        out[f] = v;
+    }
+}
+
+template <bool ZERO>
+__global__ __launch_bounds__(kThreads) void k_sgd_route_multi_stats(const SgdItems it, int cur, float wd, float lr, float momentum, int nesterov,
+                                                                    int first, double *partials, int piece_base) {
+    int64_t begin, end;
+    const int item = find_piece(it, begin, end);
+    SgdAcc a;
+    sgd_route_span_stats<ZERO>(it.w[item], it.gw[item], it.buf[item], it.owner[item], begin, end, threadIdx.x, kThreads, it.vec[item],
+                               SgdHyper{cur, wd, lr, momentum, nesterov, first}, a);
+    double r[kStatFields];
+    a.record(r);
+    block_merge_store<kSgdMaxFields>(r, partials + ((size_t)piece_base + blockIdx.x) * kStatFields);
+}
+
+__global__ __launch_bounds__(kThreads) void k_adam_route_multi_stats(const AdamItems it, int cur, int mode, float step_size, float omb1,
+                                                                     float beta2, float omb2, float eps, float bc2_sqrt, float thr,
+                                                                     double *partials, int piece_base) {
+    int64_t begin, end;
+    const int item = find_piece(it, begin, end);
+    PmAcc a;
+    adam_route_span_stats(it.pm[item], it.gpm[item], it.m1[item], it.m2[item], it.owner[item], begin, end, threadIdx.x, kThreads, it.vec[item],
+                          AdamHyper{cur, mode, step_size, omb1, beta2, omb2, eps, bc2_sqrt}, thr, a);
+    double r[kStatFields];
+    a.record(r);
+    block_merge_store<kPmMaxFields>(r, partials + ((size_t)piece_base + blockIdx.x) * kStatFields);
+}
+
+// Finalize: block b (one wave) merges the pieces [first_piece[b], first_piece[b + 1]) of item item_base + b, in a fixed order, into
+// stats[item]; an item without pieces (n == 0) gets the all-zero record.  The table travels by value, kFinMax items per launch.
+constexpr int kFinMax = 256;
+struct FinItems {
+    int first_piece[kFinMax + 1];
+    int count, item_base;
+};
+
+template <unsigned MAXMASK>
+__global__ __launch_bounds__(64) void k_step_stats_finalize(const FinItems it, const double *__restrict__ partials, double *__restrict__ stats) {
+    const int row = blockIdx.x;
+    double r[kStatFields] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int p = it.first_piece[row] + (int)threadIdx.x; p < it.first_piece[row + 1]; p += 64) {
+#pragma unroll
+        for (int f = 0; f < kStatFields; ++f) {
+            const double v = partials[(size_t)p * kStatFields + f];
+            r[f] = ((MAXMASK >> f) & 1) ? fmax(r[f], v) : r[f] + v;
+        }
+    }
+    wave_merge<MAXMASK>(r);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int f = 0; f < kStatFields; ++f) stats[(size_t)(it.item_base + row) * kStatFields + f] = r[f];
+    }
+}
+
+// The sticky health record {first_bad_step, first_bad_item, kind, bad_steps} from the finalized records of one step: the lowest bad
+// item of the step; kind 1 = a non-finite routed gradient (SGD records: g_nonfinite), 2 = a non-finite weight / piggymask after the step.
+template <bool SGD>
+__global__ __launch_bounds__(kThreads) void k_step_health(const double *__restrict__ stats, int n_items, long long step,
+                                                          long long *__restrict__ health) {
+    __shared__ int lowest[kThreads / 64];
+    auto bad = [&](int i) {
+        const double *s = stats + (size_t)i * kStatFields;
+        return SGD ? (s[1] > 0 || s[4] > 0) : s[7] > 0;
+    };
+    int best = INT32_MAX;
+    for (int i = threadIdx.x; i < n_items; i += kThreads)
+        if (i < best && bad(i)) best = i;
+    for (int m = 32; m >= 1; m >>= 1) best = min(best, __shfl_xor(best, m));
+    if ((threadIdx.x & 63) == 0) lowest[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int wv = 1; wv < kThreads / 64; ++wv) best = min(best, lowest[wv]);
+        if (best != INT32_MAX) {
+            if (health[0] == 0) {
+                health[0] = step;
+                health[1] = best;
+                health[2] = (SGD && stats[(size_t)best * kStatFields + 1] > 0) ? 1 : 2;
+            }
+            health[3] += 1;
+        }
+    }
+}
+
 // one row of a multi-tensor table: is it usable, and its copy into slot i of the kernel's argument struct with its float4 flag
 inline bool row_ok(const cpg_sgd_item &s) { return s.n >= 0 && (s.n == 0 || (s.w && s.gw && s.momentum_buf && s.owner)); }
 inline bool row_ok(const cpg_adam_item &s) { return s.n >= 0 && (s.n == 0 || (s.pm && s.gpm && s.exp_avg && s.exp_avg_sq && s.owner)); }
@@ -409,8 +643,8 @@ inline void set_row(AdamItems &it, int i, const cpg_adam_item &s) {
 
 // The table walk of the three multi entry points: kMultiMax non-empty rows per `launch(items, blocks)`.  Every row is checked before
 // the first launch (pointers, sizes, and the grid of the launch it will fall into, cut as below): a bad table changes nothing.
-template <class Items, class Row, class Launch>
-int route_multi(const char *fn, const Row *rows, int32_t n_rows, Launch launch) {
+template <class Row>
+int check_rows(const char *fn, const Row *rows, int32_t n_rows) {
     CPG_REQUIRE(n_rows >= 0 && (n_rows == 0 || rows), "%s: null item table or negative count", fn);
     for (int32_t at = 0, count = 0, blocks = 0; at < n_rows; ++at) {
         const Row &s = rows[at];
@@ -421,6 +655,11 @@ int route_multi(const char *fn, const Row *rows, int32_t n_rows, Launch launch) 
         CPG_REQUIRE(blocks + pieces < (1ll << 30), "%s: item %d is too large for one launch", fn, at);
         blocks += (int)pieces, ++count;
     }
+    return CPG_OK;
+}
+
+template <class Items, class Row, class Launch>
+int launch_rows(const char *fn, const Row *rows, int32_t n_rows, Launch launch) {
     for (int32_t at = 0; at < n_rows;) {
         Items it;
         int blocks = 0;
@@ -441,6 +680,12 @@ int route_multi(const char *fn, const Row *rows, int32_t n_rows, Launch launch) 
     return CPG_OK;
 }
 
+template <class Items, class Row, class Launch>
+int route_multi(const char *fn, const Row *rows, int32_t n_rows, Launch launch) {
+    if (const int rc = check_rows(fn, rows, n_rows)) return rc;
+    return launch_rows<Items>(fn, rows, n_rows, launch);
+}
+
 template <bool ZERO>
 int sgd_route_multi(const char *fn, const cpg_sgd_item *items_host, int32_t n_items, int32_t cur, float wd, float lr, float momentum,
                     int32_t nesterov, int32_t first_step, void *stream) {
@@ -449,6 +694,68 @@ int sgd_route_multi(const char *fn, const cpg_sgd_item *items_host, int32_t n_it
         hipLaunchKernelGGL(k_sgd_route_multi<ZERO>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, it, cur, wd, lr, momentum, nesterov,
                            first_step);
     });
+}
+
+// ---- the host side of the STATS entry points
+struct StatsArgs {
+    int64_t step;
+    void *stats, *partials;
+    size_t partials_bytes;
+    int64_t *health;
+};
+
+inline int64_t pieces_of(int64_t n) { return (n + kChunk - 1) / kChunk; }
+
+// what a _stats call adds to its plain twin's checks; runs after check_rows (every n is >= 0) and before the first launch
+template <class Row>
+int check_stats(const char *fn, const Row *rows, int32_t n_rows, const StatsArgs &a) {
+    CPG_REQUIRE(a.step >= 1, "%s: step %lld: the 1-based number of the step", fn, (long long)a.step);
+    CPG_REQUIRE(a.health != nullptr, "%s: null health record", fn);
+    int64_t pieces = 0;
+    for (int32_t at = 0; at < n_rows; ++at) pieces += pieces_of(rows[at].n);
+    CPG_REQUIRE(pieces < (1ll << 31), "%s: %lld pieces are too many for one call", fn, (long long)pieces);
+    const size_t need = (size_t)pieces * kStatFields * sizeof(double);
+    if (a.partials_bytes < need) return fail(CPG_E_WORKSPACE, "%s: partials buffer %zu < %zu bytes", fn, a.partials_bytes, need);
+    CPG_REQUIRE(a.stats && aligned16(a.stats) && a.partials && aligned16(a.partials), "%s: stats / partials null or not 16-byte aligned", fn);
+    return CPG_OK;
+}
+
+// after the step's launches, on the same stream: the records of all rows, then the health record
+template <unsigned MAXMASK, bool SGD, class Row>
+int finalize_stats(const char *fn, const Row *rows, int32_t n_rows, const StatsArgs &a, void *stream) {
+    int piece = 0;
+    for (int32_t at = 0; at < n_rows;) {
+        FinItems f;
+        f.count = 0, f.item_base = at;
+        for (; at < n_rows && f.count < kFinMax; ++at) {
+            f.first_piece[f.count++] = piece;
+            piece += (int)pieces_of(rows[at].n);
+        }
+        f.first_piece[f.count] = piece;
+        hipLaunchKernelGGL(k_step_stats_finalize<MAXMASK>, dim3(f.count), dim3(64), 0, (hipStream_t)stream, f, (const double *)a.partials,
+                           (double *)a.stats);
+        CPG_CHECK_LAUNCH(fn);
+    }
+    if (n_rows == 0) return CPG_OK;
+    hipLaunchKernelGGL(k_step_health<SGD>, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, (const double *)a.stats, (int)n_rows,
+                       (long long)a.step, (long long *)a.health);
+    CPG_CHECK_LAUNCH(fn);
+    return CPG_OK;
+}
+
+template <bool ZERO>
+int sgd_route_multi_stats(const char *fn, const cpg_sgd_item *items_host, int32_t n_items, int32_t cur, float wd, float lr, float momentum,
+                          int32_t nesterov, int32_t first_step, const StatsArgs &a, void *stream) {
+    CPG_REQUIRE(cur >= 0 && cur <= 255, "%s: owner id %d out of uint8 range", fn, cur);
+    if (const int rc = check_rows(fn, items_host, n_items)) return rc;
+    if (const int rc = check_stats(fn, items_host, n_items, a)) return rc;
+    int piece_base = 0;                          // one running piece index over the launches of a long table
+    const int rc = launch_rows<SgdItems>(fn, items_host, n_items, [&](const SgdItems &it, int blocks) {
+        hipLaunchKernelGGL(k_sgd_route_multi_stats<ZERO>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, it, cur, wd, lr, momentum,
+                           nesterov, first_step, (double *)a.partials, piece_base);
+        piece_base += blocks;
+    });
+    return rc ? rc : finalize_stats<kSgdMaxFields, true>(fn, items_host, n_items, a, stream);
 }
 
 template <bool ZERO>
@@ -487,6 +794,48 @@ extern "C" int cpg_adam_route_step_multi(const cpg_adam_item *items_host, int32_
         hipLaunchKernelGGL(k_adam_route_multi, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, it, cur, mode, (float)(lr / bc1),
                            (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)sqrt(bc2));
     });
+}
+
+extern "C" size_t cpg_step_stats_workspace_bytes(const int64_t *n_host, int32_t n_items) {
+    size_t pieces = 0;
+    for (int32_t i = 0; n_host && i < n_items; ++i)
+        if (n_host[i] > 0) pieces += (size_t)pieces_of(n_host[i]);
+    return pieces * kStatFields * sizeof(double);
+}
+
+extern "C" int cpg_sgd_route_step_multi_stats(const cpg_sgd_item *items_host, int32_t n_items, int32_t cur, float wd, float lr, float momentum,
+                                              int32_t nesterov, int32_t first_step, int64_t step, void *stats, void *partials,
+                                              size_t partials_bytes, int64_t *health, void *stream) {
+    return sgd_route_multi_stats<false>("cpg_sgd_route_step_multi_stats", items_host, n_items, cur, wd, lr, momentum, nesterov, first_step,
+                                        StatsArgs{step, stats, partials, partials_bytes, health}, stream);
+}
+
+extern "C" int cpg_sgd_route_zero_step_multi_stats(const cpg_sgd_item *items_host, int32_t n_items, int32_t cur, float wd, float lr,
+                                                   float momentum, int32_t nesterov, int32_t first_step, int64_t step, void *stats,
+                                                   void *partials, size_t partials_bytes, int64_t *health, void *stream) {
+    return sgd_route_multi_stats<true>("cpg_sgd_route_zero_step_multi_stats", items_host, n_items, cur, wd, lr, momentum, nesterov, first_step,
+                                       StatsArgs{step, stats, partials, partials_bytes, health}, stream);
+}
+
+// (`adam_step` is cpg_adam_route_step_multi's `step`, Adam's bias-correction count; `step` the telemetry's step number)
+extern "C" int cpg_adam_route_step_multi_stats(const cpg_adam_item *items_host, int32_t n_items, int32_t cur, int32_t mode, double lr,
+                                               double beta1, double beta2, double eps, int32_t adam_step, float thr, int64_t step, void *stats,
+                                               void *partials, size_t partials_bytes, int64_t *health, void *stream) {
+    const char *fn = "cpg_adam_route_step_multi_stats";
+    CPG_REQUIRE(mode == CPG_MODE_FINETUNE || mode == CPG_MODE_PRUNE, "%s: unknown mode %d", fn, mode);
+    CPG_REQUIRE(cur >= 0 && cur <= 255 && adam_step >= 1, "%s: owner id %d / step %d out of range", fn, cur, adam_step);
+    const StatsArgs a{step, stats, partials, partials_bytes, health};
+    if (const int rc = check_rows(fn, items_host, n_items)) return rc;
+    if (const int rc = check_stats(fn, items_host, n_items, a)) return rc;
+    const double bc1 = 1.0 - pow(beta1, (double)adam_step), bc2 = 1.0 - pow(beta2, (double)adam_step);
+    int piece_base = 0;
+    const int rc = launch_rows<AdamItems>(fn, items_host, n_items, [&](const AdamItems &it, int blocks) {
+        hipLaunchKernelGGL(k_adam_route_multi_stats, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, it, cur, mode, (float)(lr / bc1),
+                           (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)sqrt(bc2), thr, (double *)partials,
+                           piece_base);
+        piece_base += blocks;
+    });
+    return rc ? rc : finalize_stats<kPmMaxFields, false>(fn, items_host, n_items, a, stream);
 }
 
 extern "C" int cpg_adam_route_step(float *pm, float *gpm, float *exp_avg, float *exp_avg_sq, const uint8_t *owner, int32_t cur,

@@ -48,7 +48,7 @@ def default_args(**over):
     a = dict(mode='finetune', dataset='task1', finetune_again=False, target_sparsity=0.1, initial_sparsity=0.0,
              pruning_frequency=10, pruning_interval=4, weight_decay=4e-5, network_width_multiplier=1.0, cuda=True,
              log_path=None, progress=False, lr=1e-2, lr_mask=5e-4, checkpoint_format='{save_folder}/checkpoint-{epoch}.pth.tar',
-             fused_loss=False)
+             fused_loss=False, telemetry=False, stop_on_nonfinite=False)
     a.update(over)
     return types.SimpleNamespace(**a)
 
@@ -100,7 +100,8 @@ class CPGSession(object):
     """Holds everything the reference passes between processes through checkpoint files."""
 
     def __init__(self, arch='custom_vgg_cifar100', width=None, device='cuda', cfg=VGG16_CFG, data_parallel=True,
-                 fused_optimizers=True, seed=None, freeze_gc=False, width_multiplier=None, fused_loss=False):
+                 fused_optimizers=True, seed=None, freeze_gc=False, width_multiplier=None, fused_loss=False, telemetry=False,
+                 stop_on_nonfinite=False):
         """width_multiplier: the RAW multiplier of the reference's command line (--network_width_multiplier, before main() takes its
         square root); `width`: the rooted, model-space value the constructors see.  Give one of them (neither: 1.0)."""
         assert width is None or width_multiplier is None, 'give the rooted width OR the raw width_multiplier'
@@ -120,6 +121,11 @@ class CPGSession(object):
         # OPT-IN: every Manager of this session takes loss, accuracy and the first gradient from the loss-head kernels (args.fused_loss of
         # utils/manager.py; an `args` that sets the flag itself does the same for its own phases)
         self.fused_loss = bool(fused_loss)
+        # OPT-IN: every Manager of this session trains with step telemetry (args.telemetry of utils/manager.py: `last_telemetry`), and
+        # with stop_on_nonfinite raises utils.telemetry.TrainingDiverged out of finetune / prune / run_task once a step went non-finite.
+        # That exception is NOT one of the reference's exit codes: a diverged finetune never reaches run_task's "capacity exhausted"
+        # branch, so it cannot make the network grow
+        self.telemetry, self.stop_on_nonfinite = bool(telemetry), bool(stop_on_nonfinite)
         self.shared_layer_info = {}
         self.masks = {}
         self.model = None
@@ -287,6 +293,10 @@ class CPGSession(object):
         if self.fused_loss:
             args = copy.copy(args)
             args.fused_loss = True
+        if self.telemetry or self.stop_on_nonfinite:
+            args = copy.copy(args)
+            args.telemetry = self.telemetry or getattr(args, 'telemetry', False)
+            args.stop_on_nonfinite = self.stop_on_nonfinite or getattr(args, 'stop_on_nonfinite', False)
         return Manager(args, self.model, self.shared_layer_info, self.masks, train_loader, val_loader, begin, end)
 
     def _validate(self, mgr, epoch):

@@ -15,7 +15,12 @@ Usage (drop-in for CPG_cifar100_main_normal.py:339-341 + utils/manager.py:67-70)
 
 While a MaskedSGD is attached, `do_weight_decay_and_make_grads_zero()` skips the weight part (piggymask
 gradients are still routed there) and step() does it fused; `.grad` ends up routed exactly as before.
+
+OPT-IN step telemetry: `telemetry=StepTelemetry()` (utils/telemetry.py) makes step() call the entry points' `_stats` twins -- the same
+update bit for bit, plus one record per layer and a sticky health record reduced in the same pass.  Each optimizer gets its own tables
+inside the telemetry object.  Default None: the plain entry points, as ever.
 """
+import functools
 import os
 
 import torch
@@ -31,6 +36,7 @@ class _RoutedSGD(torch.optim.SGD):
     through `_launch` -- decay, routing and the momentum step in the library's one pass -- and leaves the rest to torch's own SGD."""
 
     def __init__(self, params, pruner, lr, momentum, nesterov, kw):
+        self.telemetry = kw.pop('telemetry', None)
         if kw.get('weight_decay', 0.0) != 0.0 or kw.get('dampening', 0.0) != 0.0:
             raise ValueError('%s mirrors the reference optimizer: weight_decay = dampening = 0 '
                              '(the decay is applied with the gradient routing)' % type(self).__name__)
@@ -38,8 +44,9 @@ class _RoutedSGD(torch.optim.SGD):
         self.pruner = pruner
         self._masked = {}                        # id(param) -> mask name
 
-    def _launch(self, rows, hyper, s):
-        """Step the (w, grad, momentum, owner, n) rows of one launch; hyper = (cur, wd, lr, momentum, nesterov, first_step)."""
+    def _launch(self, rows, hyper, s, stats=None):
+        """Step the (w, grad, momentum, owner, n) rows of one launch; hyper = (cur, wd, lr, momentum, nesterov, first_step).  stats: None, or
+        a telemetry step's `stats(entry, multi)` (_launch_stats with the rows bound), which makes the `_stats` twin of `entry` step them."""
         raise NotImplementedError
 
     @torch.no_grad()
@@ -49,10 +56,14 @@ class _RoutedSGD(torch.optim.SGD):
             self._masked = {id(module.weight): name for name, module in pr._layers()}
         s = _lib.stream_ptr()
         held = []
-        for group in self.param_groups:
+        tab = self.telemetry.tables(self, 'sgd') if self.telemetry is not None else None
+        if tab is not None:
+            tab.begin()
+        for gi, group in enumerate(self.param_groups):
             # every covered weight of the group that shares `first` (no momentum buffer yet / has one) goes into ONE multi-tensor launch
             # (cpg_sgd_route_step_multi: 53 layers of ResNet-50 = 2 launches instead of 53)
             batches = {True: [], False: []}
+            names = {True: [], False: []}
             for p in group['params']:
                 name = self._masked.get(id(p))
                 if name is None or p.grad is None:
@@ -65,12 +76,16 @@ class _RoutedSGD(torch.optim.SGD):
                 batches[first].append((_lib.dptr(p.data, name='weight').value, _lib.dptr(p.grad, name='weight.grad').value,
                                        _lib.dptr(state['momentum_buffer'], name='momentum').value,
                                        _lib.dptr(owner, torch.uint8, 'mask').value, p.numel()))
+                names[first].append(name)
                 held.append((p, p.grad))
                 p.grad = None                    # hide from torch's SGD for the rest of this step
             for first, rows in batches.items():
                 if rows:
-                    self._launch(rows, (int(pr.current_dataset_idx), float(pr.args.weight_decay), float(group['lr']), float(group['momentum']),
-                                        int(bool(group['nesterov'])), int(first)), s)
+                    hyper = (int(pr.current_dataset_idx), float(pr.args.weight_decay), float(group['lr']), float(group['momentum']),
+                             int(bool(group['nesterov'])), int(first))
+                    stats = None if tab is None else functools.partial(_launch_stats, tab, _lib.SgdItem, rows, names[first], hyper, (s,),
+                                                                       (gi, first), held[-1][0].device)
+                    self._launch(rows, hyper, s, stats)
         loss = super().step(closure)
         for p, g in held:
             p.grad = g
@@ -81,6 +96,15 @@ def _launch_multi(entry, rows, hyper, s):
     _lib.call(entry, (_lib.SgdItem * len(rows))(*rows), len(rows), *hyper, s)
 
 
+def _launch_stats(tab, item_type, rows, names, before, after, slot, device, entry, multi):
+    """The `_stats` twin of the multi-tensor `entry` on a telemetry step's tables (utils.telemetry._Tables): one call for the rows, or
+    (multi False: CPG_MULTI_TENSOR=0 where the plain path honours it) one one-row call per layer, each with a health slot of its own."""
+    if multi:
+        return tab.call(entry + '_stats', (item_type * len(rows))(*rows), rows, names, before, after, slot, device)
+    for row, name in zip(rows, names):
+        tab.call(entry + '_stats', (item_type * 1)(row), [row], [name], before, after, (slot, name), device)
+
+
 class MaskedSGD(_RoutedSGD):
     """The CPG step: every SharableConv2d / SharableLinear `.weight` through cpg_sgd_route_step_multi."""
 
@@ -88,7 +112,9 @@ class MaskedSGD(_RoutedSGD):
         super().__init__(params, pruner, lr, momentum, nesterov, kw)
         pruner.fused_weight_step = True          # tells the pruner to leave masked-weight grads to us
 
-    def _launch(self, rows, hyper, s):
+    def _launch(self, rows, hyper, s, stats=None):
+        if stats is not None:
+            return stats('cpg_sgd_route_step_multi', MULTI_TENSOR)
         if MULTI_TENSOR:
             return _launch_multi('cpg_sgd_route_step_multi', rows, hyper, s)
         for w_, g_, b_, o_, n_ in rows:
@@ -102,7 +128,8 @@ class MaskedAdam(torch.optim.Adam):
     MaskedAdam is attached, `do_weight_decay_and_make_grads_zero()` leaves piggymask gradients alone; `.grad` ends up
     routed exactly as before, and the optimizer state keeps torch's keys (step, exp_avg, exp_avg_sq)."""
 
-    def __init__(self, params, pruner, lr, betas=(0.9, 0.999), eps=1e-8, **kw):
+    def __init__(self, params, pruner, lr, betas=(0.9, 0.999), eps=1e-8, telemetry=None, **kw):
+        self.telemetry = telemetry
         if kw.get('weight_decay', 0.0) != 0.0 or kw.get('amsgrad', False) or kw.get('maximize', False):
             raise ValueError('MaskedAdam mirrors the reference optimizer: weight_decay = 0, amsgrad = maximize = False')
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=0.0)
@@ -120,9 +147,13 @@ class MaskedAdam(torch.optim.Adam):
         pr = self.pruner
         mode = {'finetune': _lib.MODE_FINETUNE, 'prune': _lib.MODE_PRUNE}.get(pr.args.mode)
         held, idle = [], []
-        for group in self.param_groups:
+        tab = self.telemetry.tables(self, 'pm') if self.telemetry is not None else None
+        if tab is not None:
+            tab.begin()
+        for gi, group in enumerate(self.param_groups):
             beta1, beta2 = group['betas']
             batches = {}                         # Adam step count -> rows of one multi-tensor launch
+            names = {}
             for p in group['params']:
                 name = self._masked.get(id(p))
                 if name is None or p.grad is None or mode is None:
@@ -142,6 +173,11 @@ class MaskedAdam(torch.optim.Adam):
                     # still exactly zero: Adam's update is then m = v = 0, pm -= step_size * 0 / eps -- nothing changes, bit for bit.
                     # The whole prune phase of the reference (lr_mask 0, a fresh optimizer per phase) is this case: only the routed
                     # gradient (all zeros) has to be left in .grad -- 4 B per element instead of the 37 B of the full pass.
+                    # Telemetry: no kernel runs, so the record is made up on the host when it is read -- all zeros, which is what the
+                    # STATS kernel reports for ANY prune-mode step (the kept set of cpg_pm_step_stats is empty outside finetune mode):
+                    # zero flips, and `picked` 0 of 0 kept slots (picked_ratio None), the same before and after the moments wake up.
+                    if tab is not None:
+                        tab.idle.append(name)
                     idle.append(p.grad)
                     p.grad = None
                     continue
@@ -151,8 +187,14 @@ class MaskedAdam(torch.optim.Adam):
                     (_lib.dptr(p.data, name='piggymask').value, _lib.dptr(p.grad, name='piggymask.grad').value,
                      _lib.dptr(state['exp_avg']).value, _lib.dptr(state['exp_avg_sq']).value,
                      _lib.dptr(owner, torch.uint8, 'mask').value, p.numel()))
+                names.setdefault(int(state['step']), []).append(name)
                 p.grad = None
-            for step, rows in batches.items():   # (cpg_adam_route_step_multi: every piggymask of the group in one launch)
+            for bi, (step, rows) in enumerate(batches.items()):   # (cpg_adam_route_step_multi: every piggymask of the group in one launch)
+                if tab is not None:
+                    _launch_stats(tab, _lib.AdamItem, rows, names[step],
+                                  (int(pr.current_dataset_idx), mode, float(group['lr']), float(beta1), float(beta2), float(group['eps']), step,
+                                   self.telemetry.thr), (s,), (gi, bi), held[-1][0].device, 'cpg_adam_route_step_multi', MULTI_TENSOR)
+                    continue
                 if not MULTI_TENSOR:
                     for p_, g_, a_, b_, o_, n_ in rows:
                         _lib.call('cpg_adam_route_step', p_, g_, a_, b_, o_, int(pr.current_dataset_idx), mode, float(group['lr']), float(beta1),
@@ -192,6 +234,8 @@ class PackNetSGD(_RoutedSGD):
     def __init__(self, params, pruner, lr, momentum=0.9, nesterov=True, mode='fused', **kw):
         if mode not in self.MODES:
             raise ValueError('PackNetSGD mode must be one of %s, got %r' % (', '.join(self.MODES), mode))
+        if mode == 'unfused' and kw.get('telemetry') is not None:
+            raise ValueError("PackNetSGD mode 'unfused' steps through torch's own SGD: there is no pass for the step telemetry to ride in")
         super().__init__(params, pruner, lr, momentum, nesterov, kw)
         self.mode = mode
         pruner.fused_weight_step = mode != 'unfused'
@@ -200,14 +244,21 @@ class PackNetSGD(_RoutedSGD):
         """Hand decay, routing and zeroing back to the pruner's own methods (another optimizer takes over)."""
         self.pruner.fused_weight_step = False
 
-    def _launch(self, rows, hyper, s):
-        if self.mode == 'fused':
+    def _launch(self, rows, hyper, s, stats=None):
+        if stats is not None:            # ('step+zero': the records describe the weights before the zero pin below)
+            stats('cpg_sgd_route_zero_step_multi' if self.mode == 'fused' else 'cpg_sgd_route_step_multi', True)
+            if self.mode == 'fused':
+                return
+        elif self.mode == 'fused':
             return _launch_multi('cpg_sgd_route_zero_step_multi', rows, hyper, s)
-        _launch_multi('cpg_sgd_route_step_multi', rows, hyper, s)
+        else:
+            _launch_multi('cpg_sgd_route_step_multi', rows, hyper, s)
         for w_, _, _, o_, n_ in rows:
             _lib.call('cpg_zero_pruned', w_, o_, n_, s)
 
     def step(self, closure=None):
         if self.mode == 'unfused':
+            if self.telemetry is not None:
+                raise RuntimeError("PackNetSGD mode 'unfused' cannot feed a StepTelemetry")
             return torch.optim.SGD.step(self, closure)
         return super().step(closure)

@@ -82,6 +82,30 @@ class ManagerBase(object):
         # AngleLoss / class-weighted / plain cross-entropy; stock torch unless args.fused_loss
         self.fused_loss = bool(getattr(args, 'fused_loss', False))
         self.criterion = make_criterion(args)
+        # OPT-IN (args.telemetry / args.stop_on_nonfinite; default off, no counterpart in the reference): the masked optimizers handed to
+        # train() step through the `_stats` twins of their passes (utils/telemetry.py) -- per-layer records of the epoch's last step in
+        # `last_telemetry`, and, with stop_on_nonfinite, TrainingDiverged out of train() once a step went non-finite
+        self.stop_on_nonfinite = bool(getattr(args, 'stop_on_nonfinite', False))
+        self.telemetry = None
+        self.last_telemetry = None
+        if getattr(args, 'telemetry', False) or self.stop_on_nonfinite:
+            from .telemetry import StepTelemetry
+            self.telemetry = StepTelemetry()
+
+    def _telemetry_attach(self, optimizers):
+        if self.telemetry is not None:
+            self.telemetry.attach(optimizers)
+
+    def _telemetry_guard(self):
+        """Raise TrainingDiverged if a step so far went non-finite.  Reads the device: called where the progress line is refreshed and
+        at the end of an epoch, never per step."""
+        if self.stop_on_nonfinite:
+            self.telemetry.check()
+
+    def _telemetry_epoch_end(self):
+        if self.telemetry is not None:
+            self.last_telemetry = self.telemetry.read()
+            self._telemetry_guard()
 
     def _root(self):
         return ckpt._root(self.model)
@@ -183,6 +207,7 @@ class Manager(ManagerBase):
     def train(self, optimizers, epoch_idx, curr_lrs, curr_prune_step):
         """One epoch of the hot loop (utils/manager.py:39-100). Returns (avg_train_acc, curr_prune_step)."""
         self.model.train()
+        self._telemetry_attach(optimizers)
         train_loss = Metric('train_loss')
         train_accuracy = Metric('train_accuracy')
         last_post = 0.0
@@ -215,7 +240,9 @@ class Manager(ManagerBase):
                                    'lr': curr_lrs[0],
                                    'sparsity': self.last_stats['sparsity'],
                                    'network_width_mpl': self.args.network_width_multiplier})
+                    self._telemetry_guard()
                 t.update(1)
+        self._telemetry_epoch_end()
         if getattr(self.model, '_world', 1) > 1:        # data parallel: metrics of the GLOBAL batches, the same on every rank
             pg = getattr(self.model, 'process_group', None)
             train_loss.all_reduce_(pg)

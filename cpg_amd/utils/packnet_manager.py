@@ -52,6 +52,7 @@ class Manager(ManagerBase):
     def train(self, optimizers, epoch_idx, curr_lrs):
         """One epoch (utils/packnet_manager.py:35-76).  Returns the average train accuracy."""
         self.model.train()
+        self._telemetry_attach(optimizers)
         train_loss, train_accuracy = Metric('train_loss'), Metric('train_accuracy')
         last_post, nbatches = 0.0, len(self.train_loader)
         with self._bar(nbatches, 'Train Epoch #{}: '.format(epoch_idx + 1)) as t:
@@ -72,7 +73,9 @@ class Manager(ManagerBase):
                     last_post = time.time()
                     t.set_postfix({'loss': train_loss.avg.item(), 'accuracy': '{:.2f}'.format(100. * train_accuracy.avg.item()),
                                    'lr': curr_lrs[0], 'sparsity': self.last_stats['sparsity']})
+                    self._telemetry_guard()
                 t.update(1)
+        self._telemetry_epoch_end()
         acc = train_accuracy.avg.item()
         if getattr(self.args, 'log_path', None):
             logging.info('In train()-> Train Ep. #{} loss: {:.3f}, accuracy: {:.2f}, lr: {}'.format(

@@ -372,6 +372,50 @@ int cpg_sgd_route_zero_step(float *w, float *gw, float *momentum_buf, const uint
 int cpg_sgd_route_zero_step_multi(const cpg_sgd_item *items_host, int32_t n_items, int32_t cur, float wd, float lr, float momentum,
                                   int32_t nesterov, int32_t first_step, void *stream);
 
+/* ---- step telemetry: the STATS forms of the three multi-tensor passes (no counterpart in the reference, which has no way to see a
+ * run diverge while it trains) ----
+ * Each performs its plain twin's update, bit for bit, and reduces what the pass holds in registers anyway into one record per item:
+ * stats[i] describes row i of the table (a row with n == 0: all zeros).  A record is 8 doubles; counts are integers held in doubles.
+ * The reduction is thread (fp64 sums of the fp32 values: a square is exact, only the order of additions can move a bit) -> block
+ * (one record per 4096-element piece, plain stores into `partials`) -> a finalize launch on the same stream that merges every item's
+ * pieces in a fixed order.  No atomics: stats and partials are bit-reproducible from run to run.
+ * `partials`: at least cpg_step_stats_workspace_bytes of the table's n column (64 bytes per piece; 0 for an empty table), contents
+ * undefined afterwards.  `step` is the caller's 1-based step number.  `health` is a DEVICE int64[4] the caller owns and zeroes once:
+ * {first_bad_step, first_bad_item, kind, bad_steps}.  kind 1: a non-finite routed gradient, 2: a non-finite weight / piggymask after
+ * the step (an item with both reports 1; the piggymask record has no gradient count, so the Adam form only ever reports 2).  The
+ * first three are written only while first_bad_step == 0, with the lowest bad item of that step; bad_steps grows by one per call
+ * that saw any bad item.  Checks, in this order and all before the first launch (a refused call changes nothing): the plain twin's,
+ * step < 1 or a null health (CPG_E_INVALID), partials_bytes below the query's answer (CPG_E_WORKSPACE), stats or partials null or not
+ * 16-byte aligned (CPG_E_INVALID).  Tables longer than cpg_multi_tensor_max non-empty rows run as several launches with one running
+ * piece index.  Callers probe for the symbols (CPG_ABI_VERSION stays 3). */
+typedef struct cpg_sgd_step_stats {   /* routed := owner == cur; g: the routed gradient as written back; w': the weight after the step */
+    double n_routed;                  /* routed slots                                                     */
+    double g_nonfinite;               /* routed slots with a non-finite g                                 */
+    double g_sumsq, g_absmax;         /* sum g^2, max |g| over the routed slots with a finite g (0: none) */
+    double w_nonfinite;               /* ALL slots with a non-finite w'                                   */
+    double dw_sumsq;                  /* sum (w' - w)^2 where both are finite, the difference in fp64     */
+    double w_sumsq, w_absmax;         /* over the finite w'                                               */
+} cpg_sgd_step_stats;
+typedef struct cpg_pm_step_stats {    /* keep := mode == finetune && owner != 0 && owner < cur; on: x > thr in fp32, false for NaN */
+    double n_routed;                  /* kept slots                                                       */
+    double g_sumsq, g_absmax;         /* over the kept slots with a finite routed gradient                */
+    double dpm_sumsq;                 /* sum (pm' - pm)^2 where both are finite                           */
+    double flips_on, flips_off;       /* kept slots that went off -> on, on -> off                        */
+    double picked;                    /* kept slots that are on after the step                            */
+    double pm_nonfinite;              /* ALL slots with a non-finite pm'                                  */
+} cpg_pm_step_stats;
+size_t cpg_step_stats_workspace_bytes(const int64_t *n_host, int32_t n_items);
+int cpg_sgd_route_step_multi_stats(const cpg_sgd_item *items_host, int32_t n_items, int32_t cur, float wd, float lr, float momentum,
+                                   int32_t nesterov, int32_t first_step, int64_t step, void *stats, void *partials, size_t partials_bytes,
+                                   int64_t *health, void *stream);
+int cpg_sgd_route_zero_step_multi_stats(const cpg_sgd_item *items_host, int32_t n_items, int32_t cur, float wd, float lr, float momentum,
+                                        int32_t nesterov, int32_t first_step, int64_t step, void *stats, void *partials,
+                                        size_t partials_bytes, int64_t *health, void *stream);
+/* adam_step: the plain twin's `step` (Adam's 1-based bias-correction count); thr: the Binarizer threshold of flips and picked */
+int cpg_adam_route_step_multi_stats(const cpg_adam_item *items_host, int32_t n_items, int32_t cur, int32_t mode, double lr, double beta1,
+                                    double beta2, double eps, int32_t adam_step, float thr, int64_t step, void *stats, void *partials,
+                                    size_t partials_bytes, int64_t *health, void *stream);
+
 /* ---- nn.BatchNorm2d -> nn.ReLU(inplace) after each masked conv ----
  * (models/vgg.py:137-141: `layers += [conv2d, nn.BatchNorm2d(c), nn.ReLU(inplace=True)]`).
  * x, y, gy, gx: NCHW fp32 with HW = H*W; gamma/beta/mean/invstd/running_*: C floats.
